@@ -30,8 +30,6 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # (toothgroupnetwork_amd/_lib.py: the schedule's streams each want a hardware queue)
-
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
@@ -39,6 +37,65 @@ from toothgroupnetwork_amd import hotpath, launch, sharding, synth  # noqa: E402
 
 METRIC = "meshes/sec (24k-pt FPS+ball_query+group fwd)"
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6290 GB/s measured-achievable
+
+
+DUMP_BUDGET_BYTES = 60_000_000     # --dump-outputs: the .npy payloads of one run stay under 64 MB
+
+
+def step_outputs(levels, fused):
+    """What one HotPath step hands its caller, by name: per level l the FPS indices, the sampled centroids, the ball-query
+    indices of every branch and the grouped tensor of every branch (fused: the level's set-abstraction output)."""
+    out = {}
+    for li, lv in enumerate(levels):
+        tag = f"l{li + 1}"
+        out[f"{tag}_fps_idx"] = lv["fps_idx"]
+        out[f"{tag}_new_xyz"] = lv["new_xyz"]
+        for bi, br in enumerate(lv["branches"]):
+            bt = f"{tag}" + (f"_b{bi + 1}" if len(lv["branches"]) > 1 else "")
+            out[f"{bt}_group_idx"] = br["group_idx"]
+            if not fused:
+                out[f"{bt}_grouped"] = br["grouped"]
+        if fused:
+            out[f"{tag}_sa_out"] = lv["out"]
+    return out
+
+
+def sample_outputs(arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Host copies of `arrays` (device tensors whose first two dims are (scan, sample)) within `budget` bytes in all: integer
+    tensors become float64 (exact), floating ones float32.  The smallest arrays are kept whole; an array that does not fit its
+    share of what is left keeps a fixed, seeded set of its (scan, sample) rows -- the leading rows of one seeded permutation
+    per row count, so the same rows in every run.  Returns {name: ndarray} and {name: description}."""
+    def dtype_of(t):
+        return torch.float32 if t.is_floating_point() else torch.float64
+    def row_bytes(t):
+        return (t.numel() // max(t.shape[0] * t.shape[1], 1)) * (4 if t.is_floating_point() else 8)
+    order = sorted(arrays, key=lambda k: arrays[k].numel() * (4 if arrays[k].is_floating_point() else 8))
+    host, info, left = {}, {}, budget
+    for i, name in enumerate(order):
+        t = arrays[name]
+        rows = t.shape[0] * t.shape[1]
+        share = left // (len(order) - i)
+        keep = min(rows, max(share // max(row_bytes(t), 1), 1))
+        if keep == rows:
+            a = t.detach().to(dtype_of(t)).cpu().numpy()
+            info[name] = {"shape": list(t.shape), "rows": "all"}
+        else:
+            sel = np.sort(np.random.default_rng([seed, rows]).permutation(rows)[:keep])
+            flat = t.detach().reshape(rows, *t.shape[2:])
+            a = flat.index_select(0, torch.from_numpy(sel).to(t.device)).to(dtype_of(t)).cpu().numpy()
+            info[name] = {"shape": list(t.shape), "rows": f"{keep} of {rows}: row scan * {t.shape[1]} + sample, the sorted first "
+                                                          f"{keep} of numpy.random.default_rng([{seed}, {rows}]).permutation({rows})"}
+        host[name] = a
+        left -= a.nbytes
+    return host, info
+
+
+def write_outputs(dirname, host, info, meta):
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    with open(os.path.join(dirname, "manifest.json"), "w") as f:
+        json.dump({**meta, "arrays": info}, f)
 
 
 _SCANS = {}
@@ -234,7 +291,12 @@ def main(argv=None):
     ap.add_argument("--fps23", default="bucket", choices=["bucket", "plain"], help="FPS levels 2-3 on the bucket-skipping kernel (few vector "
                     "instructions beside the ball queries) or the plain register-resident one")
     ap.add_argument("--secondary-timeout", type=float, default=420.0, help="seconds the secondary child process may take")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step "
+                    "computed as DIR/<name>.npy (float32, indices as float64; a fixed, seeded sample of the rows of the large "
+                    "arrays, under 64 MB in all) and DIR/manifest.json; rank 0 only")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if argv is None:
         # `python bench.py --gpus N` (no torchrun): this process runs N ranks of the same command line under torchrun and exits with
@@ -269,10 +331,15 @@ def main(argv=None):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for k in range(args.steps):
-        hp.run(xyz, feats, inputs_on_current_stream=False, more=k + 1 < args.steps)   # (the last step is told that nothing follows it)
+        last = hp.run(xyz, feats, inputs_on_current_stream=False, more=k + 1 < args.steps)   # (the last step is told that nothing follows it)
     torch.cuda.synchronize()
     sharding.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # copied now: the steps after the timed region reuse the two buffer sets
+        host, info = sample_outputs(step_outputs(last, bool(args.fused)))
+        write_outputs(args.dump_outputs, host, info, {"shape": args.shape, "fused": bool(args.fused), "batch": B, "unique": args.unique,
+                                                      "seed": 100, "steps": args.steps, "step_dumped": args.steps})
     launch.stage("gather", seconds=round(elapsed, 6))
     per_rank_s = sharding.gather_metrics([elapsed], device=device).reshape(-1).cpu().tolist()   # the one collective of the run
     elapsed = max(per_rank_s)

@@ -8,6 +8,7 @@ import os
 import re
 import shutil
 import subprocess
+import tempfile
 
 import pytest
 
@@ -65,10 +66,11 @@ def test_fps_and_group_kernels_can_share_a_cu():
 
 
 def _isa(src):
-    out = os.path.join("/tmp", "tgn_isa_" + src.replace(".hip", ".s"))
-    subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-munsafe-fp-atomics",
-                    "-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, src)], check=True, capture_output=True)
-    return open(out).read()
+    with tempfile.TemporaryDirectory(prefix="tgn_isa_") as d:
+        out = os.path.join(d, src.replace(".hip", ".s"))
+        subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-munsafe-fp-atomics",
+                        "-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, src)], check=True, capture_output=True)
+        return open(out).read()
 
 
 def _kernel_body(isa, mangled_prefix):

@@ -20,6 +20,7 @@ def _worker(rank, world, port, q):
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port))
     from toothgroupnetwork_amd import sharding
+    torch.cuda.is_available = lambda: False     # the CPU ranks' path, also on a machine with GPUs (this child process only)
     r, lr, w, device = sharding.init_from_env(backend="gloo")
     assert (r, w) == (rank, world) and device.type == "cpu"
     items = list(range(11))

@@ -8,12 +8,10 @@ import ctypes
 import os
 import threading
 
-# The HIP runtime multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and two streams that share a
-# queue run one after the other.  The phased HotPath schedule alone keeps four streams busy; with the caller's own stream and a
-# copy stream that is six, and a second HotPath in the process used to lose its overlap entirely (7.7 instead of 4.9 ms per
-# step, profiles/r06_hw_queues.txt).  The runtime reads the variable once, when the first HIP call initialises it -- after this
-# import in every entry point of the package.  An explicit setting of the caller's wins.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# The HIP runtime multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues, and two streams that share a queue run
+# one after the other (profiles/r06_hw_queues.txt).  The package does not set the variable: the number of hardware queues a
+# process may open is the host's policy, read once when the first HIP call initialises the runtime.  With fewer queues than
+# the phased HotPath schedule has streams the results are the same and the steps overlap less.
 
 import torch  # noqa: E402
 
