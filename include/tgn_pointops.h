@@ -66,20 +66,17 @@ void tgn_set_default_stream(tgn_stream_t stream);
 void tgn_set_fps_mode(int flags);
 int tgn_get_fps_mode(void);
 /*
- * Kernel-variant switches for experiments, A/B runs and the parity tests that must reach every variant.  One table of
- * atomics inside the library, read with a relaxed load on the launch paths (no getenv there); the legacy TGN_* environment
- * names seed it once, when the library is loaded.  Thread-safe; a change applies to launches enqueued after the call.
- *   "fps_plain"          1 = plain register-resident / streaming FPS kernels, no bucket skipping        (TGN_FPS_V1)
- *   "fps_config"         NT * 256 + P forces an instantiated plain-kernel shape, 0 = pick               (TGN_FPS_CONFIG=NT,P)
- *   "fps_bucket_config"  NT * 256 + P forces a bucket-kernel shape, 0 = pick                            (TGN_FPS_BUCKET_CONFIG=NT,P)
- *   "fps_cell_bits"      4 (default) or 5: bits per axis of the bucket kernel's Z-order cell code       (TGN_FPS_CELL_BITS)
- *   "fps_bucket_min"     smallest cloud the bucket kernel takes, -1 = built-in thresholds               (TGN_FPS_BUCKET_MIN)
- *   "ball_bitmap"        0 = rank-select ball-query kernel instead of the bitmap one                    (TGN_BALL_BITMAP)
+ * Kernel-variant switches for A/B runs and the parity tests that must reach every kernel.  One table of atomics inside the
+ * library, read with a relaxed load on the launch paths (no getenv there); the legacy TGN_* environment names seed it once,
+ * when the library is loaded.  Thread-safe; a change applies to launches enqueued after the call.
+ *   "fps_bucket_min"     smallest cloud the bucket kernel takes, -1 = built-in thresholds; values above 4097 act as 4097:
+ *                        a cloud of more than 4096 points always takes the bucket kernel                (TGN_FPS_BUCKET_MIN)
+ *   "fps_lean"           0 = no lean kernel, 1 = lean kernel for 257 .. 2048 points (default), 2 = up to 4096     (TGN_FPS_LEAN)
+ *   "ball_bitmap"        0 = rank-select ball-query kernel, any other value = the chunked bitmap kernel (default 2)
+ *                                                                                                        (TGN_BALL_BITMAP)
  *   "sa_tile"            0 = pick, 128 / 256 = force the workgroup tile of tgn_sa_mlp2_max_bf16x3                (TGN_SA_TILE)
- *   "gather_v4"          gather family: bit 0 forward kernels with 16-byte lanes, bit 1 backward kernels with 16-byte lanes,
- *                        bit 2 subtraction / aggregation backward with owner-side sums on dword lanes (default 5)    (TGN_GATHER_V4)
- *   "knn_memset"         1 = clear the kNN redo counter with hipMemsetAsync (reproduces a graph fault)  (TGN_KNN_MEMSET)
- *   "knn_grid_scale"     kNN grid cell, per mille of the estimated k-neighbour radius (1000)            (TGN_KNN_GRID_SCALE)
+ *   "gather_v4"          gather family: bit 0 forward kernels with 16-byte lanes, bit 2 subtraction / aggregation backward
+ *                        with owner-side sums (default 5); other bits are ignored                      (TGN_GATHER_V4)
  * tgn_set_tuning returns TGN_ERR_INVALID_ARGUMENT for an unknown key; tgn_get_tuning returns `fallback` for one.
  */
 int tgn_set_tuning(const char *key, int value);

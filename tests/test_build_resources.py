@@ -29,9 +29,9 @@ def _usage(src):
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
-def test_fps_and_group_kernels_can_share_a_cu():
+def test_fps_bucket_and_group_kernels_can_share_a_cu():
     fps = _usage("fps_bucket.hip")
-    vgpr, scratch, lds = fps["tgn::fps_bucket_kernel<512, 48, 0, false, 4>"]
+    vgpr, scratch, lds = fps["tgn::fps_bucket_kernel<512, 48, 0>"]
     assert scratch == 0, "the 24 000-point FPS kernel must not spill"
     assert vgpr <= 232, f"FPS level-1 kernel uses {vgpr} VGPRs: no room left for a grouping wave per SIMD (needs <= 232)"
     assert lds <= 66 * 1024, f"FPS level-1 kernel holds {lds} B of LDS: the row-piece grouping kernel no longer fits 4 waves beside it"
@@ -61,7 +61,7 @@ def test_fps_and_group_kernels_can_share_a_cu():
     for name, (v, s_, _) in g.items():
         assert s_ == 0, f"{name} spills"
     for name, (v, s, _) in fps.items():
-        if ", 0, false, 4>" in name and "56" not in name:
+        if name.startswith("tgn::fps_bucket_kernel<") and name.endswith(", 0>") and "56" not in name:
             assert s == 0, f"{name} spills"
 
 
@@ -79,13 +79,14 @@ def _kernel_body(isa, mangled_prefix):
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
-def test_wide_builtin_loads_are_not_narrowed():
+def test_wide_builtin_loads_of_the_launched_kernels_are_not_narrowed():
     """hipcc 7.2 has narrowed `raw_buffer_load_b64 / _b96 / _b128` whose components are used one by one to a single dword
      -- silently wrong data.  The kernels that rely on 16-byte builtin loads must still contain them."""
     ball = _isa("ball_query.hip")
     for idx_t in ("i", "x"):
-        body = _kernel_body(ball, f"_ZN3tgn29ball_grid_query_bitmap_kernelI{idx_t}EE")
-        assert body.count("buffer_load_dwordx4") >= 3, "the record loads of the ball query were narrowed"
+        for nq in (1, 2, 3, 4):
+            body = _kernel_body(ball, f"_ZN3tgn28ball_grid_query_chunk_kernelI{idx_t}Li{nq}EEE")
+            assert body.count("buffer_load_dwordx4") >= 3, "the record loads of the ball query were narrowed"
     sa = _isa("sa.hip")
     for name in ("_ZN3tgn20sa_gather_max_kernelIiEE", "_ZN3tgn20sa_gather_max_kernelIxEE"):
         assert _kernel_body(sa, name).count("buffer_load_dwordx4") >= 1, name

@@ -34,7 +34,8 @@ def test_fps_dense_matches_golden(dev, golden):
 @pytest.mark.parametrize("bucket_min", [2048, 1000000])
 def test_fps_every_kernel_shape_vs_oracle(dev, oracle, n, m, bucket_min):
     """One cloud per launch configuration (threads x points-per-lane), incl. exact-capacity edges; every shape
-    of the bucket-skipping kernel (bucket_min=2048) and of the plain kernel (bucket_min huge)."""
+    of the bucket-skipping kernel (bucket_min=2048) and of the plain kernel (bucket_min huge, clouds of up to 4096 points).
+    Above 4096 points there is no plain kernel: a huge bucket_min is capped and the cloud still takes the bucket kernel."""
     from toothgroupnetwork_amd import _lib, pointops as P
     xyz = synth.uniform_cloud(n, seed=n)
     off, noff = np.array([n], np.int32), np.array([m], np.int32)
@@ -65,13 +66,24 @@ def test_fps_bucket_kernel_ties_nan_and_modes(dev, oracle, mode):
     assert np.array_equal(out.cpu().numpy(), oracle.furthestsampling(xyz_np, off_np, noff_np, mode=mode))
 
 
-def test_fps_bucket_kernel_equals_plain_kernel(dev):
-    from toothgroupnetwork_amd import _lib, pointnet2_utils as U
-    xyz = T(np.stack([synth.arch_cloud(24000, s, False) for s in (40, 41)]), dev)
-    a = U.farthest_point_sample(xyz, 4096)
-    with _lib.tuning(fps_plain=1):
-        b = U.farthest_point_sample(xyz, 4096)
-    assert torch.equal(a, b)
+def test_fps_bucket_kernel_equals_throughput_kernel_and_oracle(dev, oracle):
+    """24 000-point scans: the default launch (register-resident bucket kernel) against the TGN_FPS_THROUGHPUT launch (the
+    owner-wave kernel out of the L2-resident workspace) and the oracle."""
+    from toothgroupnetwork_amd import _lib
+    L = _lib.lib()
+    xyz_np = np.stack([synth.arch_cloud(24000, s, False) for s in (40, 41)])
+    xyz = T(xyz_np, dev)
+    nbytes = int(L.tgn_fps_throughput_workspace_bytes(2, 24000))
+    assert nbytes > 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    outs = []
+    for flags, w, wb in ((0, None, 0), (_lib.FPS_THROUGHPUT, _lib.ptr(ws), nbytes)):
+        idx = torch.full((2, 4096), -7, dtype=torch.int32, device=dev)
+        _lib.check(L.tgn_furthestsampling_dense_ws(2, 24000, 4096, _lib.ptr(xyz), w, wb, _lib.ptr(idx), None,
+                                                   flags | _lib.FPS_LOCAL_INDEX, _lib.stream()), "fps")
+        outs.append(idx.cpu().numpy())
+    assert np.array_equal(outs[0], outs[1])
+    assert np.array_equal(outs[0], oracle.farthest_point_sample(xyz_np, 4096))
 
 
 def test_fps_low_valu_hint_changes_the_kernel_not_the_result(dev, oracle):
@@ -417,7 +429,7 @@ def test_ball_query_dense_balls_and_large_clouds(dev, oracle):
 
 @pytest.mark.parametrize("variant", [2, 1, 0])
 def test_ball_query_every_grid_kernel_ragged_chunks_and_bad_queries(dev, oracle, variant):
-    """The three grid kernels (2: chunks of 16 queries, the default; 1: round 2's bitmap kernel; 0: rank-select) on shapes that
+    """The two grid kernels (2, or any other nonzero value such as 1: chunks of 16 queries, the default; 0: rank-select) on shapes that
     exercise the chunking: S not a multiple of 16, fewer queries than a chunk, many clouds (chunks never straddle two), every
     bitmap size (N <= 8192, 16384, 24576, 32768), NaN / Inf queries in the middle of a chunk (index-order scan for those
     queries only), a NaN point in one cloud of the batch (that cloud takes the scan path, its neighbours do not), K = 256."""
@@ -1031,11 +1043,11 @@ def test_pointops_cuda_shim_runs_reference_style_code(dev, oracle):
     assert np.array_equal(out.cpu().numpy(), xyz_np[oi])
 
 
-@pytest.mark.parametrize("variant", [0, 3, 5])
+@pytest.mark.parametrize("variant", [0, 1, 3, 4, 5])
 @pytest.mark.parametrize("shape", [(600, 12, 32, 4), (257, 7, 64, 8), (300, 5, 16, 16), (200, 9, 128, 16), (150, 6, 10, 5), (90, 4, 36, 12)])
 def test_gather_family_every_kernel_variant_matches_a_float64_evaluation(dev, variant, shape):
-    """The gather family's kernel variants (tgn_set_tuning "gather_v4": 0 = dword lanes and atomics everywhere, 3 = 16-byte lanes
-    forward and backward, 5 = the default: 16-byte lanes forward, owner-side sums backward) at channel counts that take the fast
+    """The gather family's kernel variants (tgn_set_tuning "gather_v4": 0 = dword lanes and atomics everywhere, 1 = 16-byte lanes
+    forward, 4 = owner-side sums backward, 5 = the default: both; 3 = 1 with the retired bit 1, which is ignored) at channel counts that take the fast
     paths (c % 4 == 0, powers of two) and that do not, against the operators' definitions (grouping_cuda_kernel.cu:5-25,
     subtraction_cuda_kernel.cu:5-30, aggregation_cuda_kernel.cu:5-39, interpolation_cuda_kernel.cu:5-33) evaluated in float64.
     Outputs the reference accumulates into are handed over pre-filled: what was there must still be added to."""

@@ -358,17 +358,20 @@ def test_config_object_is_the_one_place_for_python_side_switches():
     assert fresh.fused_sa and fresh.sa_bf16x3 and fresh.knn_grid_min_points == 3000 and fresh.index_check == "sync"
 
 
-def test_tuning_table_round_trip_and_unknown_key():
-    """tgn_set_tuning / tgn_get_tuning (include/tgn_pointops.h): host-side table, no GPU needed.  Known keys round-trip, (nt, p) pairs
-    pack as nt * 256 + p, the context manager restores, an unknown key is an error (not silently a no-op)."""
+def test_tuning_table_round_trip_and_retired_keys_rejected():
+    """tgn_set_tuning / tgn_get_tuning (include/tgn_pointops.h): host-side table, no GPU needed.  Known keys round-trip, the context
+    manager restores, an unknown key -- a retired one included -- is an error (not silently a no-op)."""
     from toothgroupnetwork_amd import _lib
     L = _lib.lib()
-    for key, default in (("fps_plain", 0), ("fps_bucket_min", -1), ("fps_cell_bits", 4), ("ball_bitmap", 2), ("sa_tile", 0), ("knn_grid_scale", 1000), ("gather_v4", 5)):
+    live = (("fps_bucket_min", -1), ("fps_lean", 1), ("ball_bitmap", 2), ("sa_tile", 0), ("gather_v4", 5))
+    for key, default in live:
         assert L.tgn_get_tuning(key.encode(), -12345) == default, key
-    with _lib.tuning(fps_bucket_config=(512, 48), fps_plain=1):
-        assert L.tgn_get_tuning(b"fps_bucket_config", 0) == 512 * 256 + 48
-        assert L.tgn_get_tuning(b"fps_plain", 0) == 1
-    assert L.tgn_get_tuning(b"fps_bucket_config", -1) == 0 and L.tgn_get_tuning(b"fps_plain", -1) == 0
+    with _lib.tuning(fps_bucket_min=2048, fps_lean=2, ball_bitmap=0, sa_tile=128, gather_v4=1):
+        assert [L.tgn_get_tuning(k.encode(), -1) for k, _ in live] == [2048, 2, 0, 128, 1]
+    assert [L.tgn_get_tuning(k.encode(), -12345) for k, _ in live] == [d for _, d in live]
+    for key in ("fps_plain", "fps_config", "fps_bucket_config", "fps_cell_bits", "knn_memset", "knn_grid_scale"):
+        assert L.tgn_set_tuning(key.encode(), 1) == _lib.ERR_INVALID_ARGUMENT and key.encode() in L.tgn_last_error(), key
+        assert L.tgn_get_tuning(key.encode(), 77) == 77, key
     assert L.tgn_set_tuning(b"no_such_switch", 1) != 0 and b"no_such_switch" in L.tgn_last_error()
     assert L.tgn_get_tuning(b"no_such_switch", 77) == 77
     with pytest.raises(RuntimeError):

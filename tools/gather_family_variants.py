@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""secondary_bench.gather_family under each "gather_v4" variant (0: dword lanes + atomics, 3: 16-byte lanes, 5: default)."""
+"""secondary_bench.gather_family under each "gather_v4" variant (0: dword lanes + atomics, 5: default)."""
 import importlib.util
 import os
 import sys
@@ -14,7 +14,7 @@ spec = importlib.util.spec_from_file_location("secondary_bench", os.path.join(RE
 S = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(S)
 dev = torch.device("cuda", 0)
-variants = [int(v) for v in (sys.argv[1:] or ["0", "3", "5"])]
+variants = [int(v) for v in (sys.argv[1:] or ["0", "5"])]
 res = {}
 for v in variants:
     with _lib.tuning(gather_v4=v):

@@ -104,7 +104,7 @@ def main():
         "chain_f_alone": timed(chain_f),
         "chain_h_alone": timed(None, chain_h),
         "phase2_both": timed(chain_f, lambda: chain_h(True)),
-        "tuning": {k: int(L.tgn_get_tuning(k.encode(), -999)) for k in ("fps_plain", "fps_bucket_min", "ball_bitmap")},
+        "tuning": {k: int(L.tgn_get_tuning(k.encode(), -999)) for k in ("fps_bucket_min", "ball_bitmap")},
         "env": {k: v for k, v in os.environ.items() if k.startswith("TGN_")},
     }
     print(json.dumps(out))

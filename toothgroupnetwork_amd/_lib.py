@@ -163,11 +163,8 @@ def get_fps_mode():
 
 
 def set_tuning(key, value):
-    """Select a kernel variant inside the library (include/tgn_pointops.h: tgn_set_tuning; keys "fps_plain", "fps_config",
-    "fps_bucket_config", "fps_cell_bits", "fps_bucket_min", "ball_bitmap", "sa_tile", "knn_memset", "knn_grid_scale").
-    (nt, p) pairs are given as tuples.  Returns the previous value.  Experiments and parity tests only."""
-    if isinstance(value, (tuple, list)):
-        value = int(value[0]) * 256 + int(value[1])
+    """Select a kernel variant inside the library (include/tgn_pointops.h: tgn_set_tuning; keys "fps_bucket_min", "fps_lean",
+    "ball_bitmap", "sa_tile", "gather_v4").  Returns the previous value.  A/B runs and parity tests only."""
     k = key.encode()
     prev = lib().tgn_get_tuning(k, 0)
     check(lib().tgn_set_tuning(k, int(value)), "tgn_set_tuning")
@@ -175,7 +172,7 @@ def set_tuning(key, value):
 
 
 class tuning:
-    """`with tuning(fps_plain=1, fps_bucket_min=2048): ...` -- kernel-variant switches for the duration of a block."""
+    """`with tuning(fps_lean=0, fps_bucket_min=2048): ...` -- kernel-variant switches for the duration of a block."""
 
     def __init__(self, **kv):
         self.kv, self.prev = kv, {}

@@ -419,31 +419,30 @@ __global__ __launch_bounds__(256) void ball_grid_query_kernel(int B, int N, int 
 
 
 // ------------------------------------------------------------------------------------------------
-// grid path, bitmap selection (clouds of up to 32 768 points: every Shape-A / Shape-B level)
+// grid path, chunked bitmap kernel (round 6; clouds of up to 32 768 points -- the default)
 // ------------------------------------------------------------------------------------------------
 // The answer of a query is "the nsample smallest indices among its hits, ascending".  ball_grid_query_kernel gets there by
-// rank-selecting the hit list (every lane compares its hit with every other one: ~3 instructions per hit and lane-slot,
-// a third of the kernel).  Here the hits are ALSO dropped into a bitmap over the cloud's index range (one LDS `or` per
-// candidate step); the rank of a hit is then the number of set bits below it:
-//   * lane l owns the words of indices [l*W*32, (l+1)*W*32), W = 4*nquad: it counts its bits (one v_bcnt per word), a wave
-//     scan over the lane totals gives every 128-index group its base rank (gbase);
-//   * the lane that holds hit v reads gbase[v >> 7] and the group's four words and counts the bits below v: ~20
-//     instructions whatever the number of hits; ranks < nsample are stored, rank 0 is the pad value (pointnet2_utils.py:138-141);
-//   * the owners wipe their words (three 16-byte LDS stores per lane at N = 24 000).
-// Candidates are walked one x-run per 16-lane row (a run holds ~15 records on a scan surface) instead of as one flattened
-// list: the run a lane serves is a constant of the step, so there is no per-lane search for "which run does candidate g
-// belong to" (16 of the ~60 instructions of a step before).  More hits than the list holds (kBmHitCap) are handled by
-// walking the candidates a second time and ranking each hit straight from the bitmap.
-// Same cells, same test, same arithmetic as above: the results are identical.
+// rank-selecting the hit list (every lane compares its hit with every other one).  Here the hits are ALSO dropped into a bitmap
+// over the cloud's index range (one LDS `or` per candidate step), and the rank of a hit is the number of set bits below it.  Same
+// cells, same test, same arithmetic: the results are identical.  The kernel runs at the VALU issue limit (one wave64 instruction
+// per 4 cycles and SIMD), so it is written for few instructions per query (round 2's one-query-per-wave form issued ~370;
+// profiles/r06_ball_sq_by_stage.txt):
+//   * ONE wave per workgroup, its LDS at fixed offsets: every LDS address is a register plus an instruction offset;
+//   * a wave takes CHUNKS of 16 consecutive queries of one cloud.  The per-query bookkeeping -- three cell coordinates, nine
+//     cell-table look-ups, the prefix sum of the nine run lengths -- is done once per chunk with a lane per (query, dy):
+//     16 x 4 lanes, three passes (dz); ends and record offsets of the runs go to a 64-byte block per query in LDS, next to the
+//     query's coordinates and squared norm;
+//   * candidate g of the flattened list finds its run by a three-step binary search over that block's ends in LDS (three
+//     dependent ds_read_u16 + 8 vector instructions) plus one compare for the last run;
+//   * records, cell table, queries and the output row go through buffer descriptors (32-bit offsets, out-of-range lanes read 0);
+//   * the record carries |p|^2 (ball_grid_build_kernel), the test is 3 fma + 3 add + 1 compare;
+//   * ranks come from a per-WORD exclusive prefix of the bitmap's popcounts (u16, built by the 64 word owners with chained
+//     v_bcnt + one wave scan): rank(v) = base[v >> 5] + bcnt(word & below(v)) -- two LDS reads and ~8 instructions per 64 hits.
+// More hits than the list holds (kBmHitCap) are handled by walking the candidates a second time and ranking each hit straight
+// from the bitmap.
 constexpr int kBmMaxN = 32768;
 constexpr int kBmHitCap = 256;
 
-// Cost: the kernel is bound by vector-ALU issue (a wave64 instruction holds its SIMD for 4 cycles; the rank-select kernel
-// spends ~430 of them per query), so this one is written for few instructions on the common path:
-//   * the candidates are one flattened list over the <= 9 runs; the first 192 of them (three per lane) are requested at
-//     once, so the common query never loops and pays one record-load latency;
-//   * records, cell table and the output row go through buffer descriptors (32-bit offsets, out-of-range lanes read 0);
-//   * the cell-table look-ups of the wave's NEXT query are issued before the current one is processed.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t ball_rsrc(const void *base, unsigned bytes) {   // wave-uniform base
     const unsigned long long a = (unsigned long long)base;
     const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a);
@@ -452,264 +451,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t ball_rsrc(const void *base, un
                                              __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
 }
 
-struct BallRuns {      // what a query needs to start: lanes 0..8 hold the record range of one x-run each
-    float cx, cy, cz;  // wave-uniform
-    int rs, re;
-    int b;             // scan (cloud) of the query
-    bool scan;         // wave-uniform: the cloud has no grid / the query is not finite -> index-order scan
-};
-
-template <typename IdxT>
-__global__ __launch_bounds__(256) void ball_grid_query_bitmap_kernel(int B, int N, int S, int K, float r2,
-                                                                      const float *__restrict__ xyz,
-                                                                      const float *__restrict__ new_xyz,
-                                                                      const unsigned char *__restrict__ ws,
-                                                                      IdxT *__restrict__ out, long long q_per_xcd) {
-    extern __shared__ __attribute__((aligned(16))) unsigned bm_dyn[];   // per wave: bitmap [nquad*256], gbase [nquad*64], hits [kBmHitCap]
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-    const int nquad = (N + 8191) >> 13;   // 16-byte quads (128 indices) per lane: lane l owns quads [l*nquad, (l+1)*nquad)
-    const int per_wave = nquad * 256 + nquad * 64 + kBmHitCap;
-    unsigned *bm = bm_dyn + wv * per_wave;
-    unsigned *gbase = bm + nquad * 256;
-    int *hits = (int *)(gbase + nquad * 64);
-    for (int t = 0; t < nquad; ++t) *(u32x4 *)&bm[(lane * nquad + t) * 4] = u32x4{0u, 0u, 0u, 0u};
-    const long long total = (long long)B * S;
-    const size_t cloud_bytes = grid_cloud_bytes(N);
-    const size_t rec_off = kGridRecOff;
-    const int dy = lane % 3 - 1, dz = lane / 3 - 1;   // lanes 0..8: the (dy, dz) x-run this lane looks up
-    // XCD x (hardware block i runs on XCD i % 8) owns the contiguous query range [x*q_per_xcd, (x+1)*q_per_xcd) -- whole
-    // clouds when there are at least 8 -- and its blocks, no more than are resident at a time, walk it together: a cloud's
-    // grid (cell table + records, 0.45 MB at N = 24 000, read ~20 times over by its queries) is pulled into ONE L2 once
-    // (PMC: 963 MB of HBM reads per level-1 launch when every wave strode over 16 clouds, 4.4x the algorithmic bytes).
-    const unsigned xcd = blockIdx.x & 7u;
-    const long long stride = (long long)(gridDim.x >> 3) * 4;
-    long long q_end = (long long)(xcd + 1) * q_per_xcd;
-    if (q_end > total) q_end = total;
-
-    // (the scan a query belongs to is tracked incrementally: a 64-bit division per query costs ~100 instructions)
-    auto lookup = [&](long long q, int bq) -> BallRuns {   // issues the two cell-table loads of query q (lanes 0..8) of scan bq
-        BallRuns r;
-        r.b = bq;
-        const unsigned char *base = ws + (size_t)r.b * cloud_bytes;
-        const GridHeader *hdr = (const GridHeader *)base;
-        r.cx = new_xyz[q * 3 + 0];
-        r.cy = new_xyz[q * 3 + 1];
-        r.cz = new_xyz[q * 3 + 2];
-        const bool q_finite = fabsf(r.cx) <= 3.0e38f && fabsf(r.cy) <= 3.0e38f && fabsf(r.cz) <= 3.0e38f;
-        r.scan = hdr->use_scan || !q_finite;
-        r.rs = r.re = 0;
-        if (r.scan) return r;
-        const __amdgpu_buffer_rsrc_t rs_cells = ball_rsrc(base + sizeof(GridHeader), (kGridCells + 1) * 4u);
-        const int gx = hdr->g[0], gy = hdr->g[1], gz = hdr->g[2];
-        const float inv_h = hdr->inv_h;
-        const int qx = cell_coord(r.cx, hdr->lo[0], inv_h, gx);
-        const int qy = cell_coord(r.cy, hdr->lo[1], inv_h, gy);
-        const int qz = cell_coord(r.cz, hdr->lo[2], inv_h, gz);
-        const int x0 = max(qx - 1, 0), x1 = min(qx + 1, gx - 1);
-        const int yy = qy + dy, zz = qz + dz;
-        const bool ok = lane < 9 && x0 <= x1 && yy >= 0 && yy < gy && zz >= 0 && zz < gz;
-        const unsigned c0 = (unsigned)((zz * gy + yy) * gx);
-        // lanes without a run read out of range: the hardware returns 0 for both ends -> an empty run
-        r.rs = (int)__builtin_amdgcn_raw_buffer_load_b32(rs_cells, ok ? (c0 + (unsigned)x0) * 4u : 0xFFFFFFF0u, 0, 0);
-        r.re = (int)__builtin_amdgcn_raw_buffer_load_b32(rs_cells, ok ? (c0 + (unsigned)x1 + 1u) * 4u : 0xFFFFFFF0u, 0, 0);
-        return r;
-    };
-
-    long long q = (long long)xcd * q_per_xcd + (long long)(blockIdx.x >> 3) * 4 + wv;
-    if (q >= q_end) return;
-    int bcur = __builtin_amdgcn_readfirstlane((int)(q / S));
-    int rcur = __builtin_amdgcn_readfirstlane((int)(q - (long long)bcur * S));     // q = bcur*S + rcur
-    const int db = __builtin_amdgcn_readfirstlane((int)(stride / S));
-    const int dr = __builtin_amdgcn_readfirstlane((int)(stride - (long long)db * S));
-    BallRuns cur = lookup(q, bcur);
-    for (; q < q_end; q += stride) {
-        const long long qn = q + stride;
-        bcur += db;
-        rcur += dr;
-        if (rcur >= S) {
-            rcur -= S;
-            ++bcur;
-        }   // (bcur, rcur) now describe qn
-        if (cur.scan) {  // wave-uniform
-            ball_scan_row<IdxT>(N, K, r2, xyz + (size_t)cur.b * N * 3, cur.cx, cur.cy, cur.cz, out + q * K, lane);
-            if (qn < q_end) cur = lookup(qn, bcur);
-            continue;
-        }
-        const __amdgpu_buffer_rsrc_t rs_rec = ball_rsrc(ws + (size_t)cur.b * cloud_bytes + rec_off, (unsigned)N * 16u);
-        const __amdgpu_buffer_rsrc_t rs_idx = ball_rsrc(ws + (size_t)cur.b * cloud_bytes + grid_idx_off(N), (unsigned)N * 4u);
-        const __amdgpu_buffer_rsrc_t rs_out = ball_rsrc(out + q * K, (unsigned)K * (unsigned)sizeof(IdxT));
-        auto put = [&](int r, int v) {   // orow[r] = v
-            if constexpr (sizeof(IdxT) == 8) {
-                typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-                __builtin_amdgcn_raw_buffer_store_b64(u32x2{(unsigned)v, 0u}, rs_out, (unsigned)r * 8u, 0, 0);   // indices are >= 0
-            } else {
-                __builtin_amdgcn_raw_buffer_store_b32((unsigned)v, rs_out, (unsigned)r * 4u, 0, 0);
-            }
-        };
-        const float cx = cur.cx, cy = cur.cy, cz = cur.cz;
-        const float s1 = sumsq3(cx, cy, cz);
-        // The <= 9 runs are walked as ONE flattened candidate list (on a scan surface the candidates sit in ~3 long runs,
-        // not 9 short ones: fixed lane groups per run leave most lanes idle and the rest looping).  Lane r < 9 holds run
-        // r's [rs, re); pre = records before it (inclusive scan over one DPP row); candidate g lives in run
-        // #{t : ends[t] <= g} at record g + delta[run].  The first 192 candidates are requested at once.
-        const int len = cur.re - cur.rs;
-        int pre = len;
-        pre += (int)dpp_or_zero<0x111, 0xF>((unsigned)pre);
-        pre += (int)dpp_or_zero<0x112, 0xF>((unsigned)pre);
-        pre += (int)dpp_or_zero<0x114, 0xF>((unsigned)pre);
-        pre += (int)dpp_or_zero<0x118, 0xF>((unsigned)pre);
-        const int T = __builtin_amdgcn_readlane(pre, 8);   // lanes 9.. have len 0
-        const int delta = cur.rs - (pre - len);
-        int ends[8];                                        // wave-uniform run ends in the flattened list
-#pragma unroll
-        for (int r = 0; r < 8; ++r) ends[r] = __builtin_amdgcn_readlane(pre, r);
-        auto record_of = [&](int g) -> int {               // flattened candidate -> record index
-            int r = 0;
-#pragma unroll
-            for (int t = 0; t < 8; ++t) r += (g >= ends[t]) ? 1 : 0;
-            return g + __shfl(delta, r);
-        };
-        u32x4 p[3];
-        int pi[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const int g = 64 * i + lane;
-            const int j = record_of(g);
-            p[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_rec, g < T ? (unsigned)j * 16u : 0xFFFFFFF0u, 0, 0);
-            pi[i] = (int)__builtin_amdgcn_raw_buffer_load_b32(rs_idx, g < T ? (unsigned)j * 4u : 0xFFFFFFF0u, 0, 0);
-        }
-        // the next query's cell-table look-ups go out behind them and land while this query is processed
-        BallRuns nxt;
-        nxt.scan = true;
-        nxt.rs = nxt.re = nxt.b = 0;
-        nxt.cx = nxt.cy = nxt.cz = 0.0f;
-        if (qn < q_end) nxt = lookup(qn, bcur);
-
-        int H = 0;
-        auto test = [&](const u32x4 &pp) -> bool {
-            const float px = __uint_as_float(pp[0]), py = __uint_as_float(pp[1]), pz = __uint_as_float(pp[2]);
-            const float d = sqdist_expanded(cx, cy, cz, s1, px, py, pz, __uint_as_float(pp[3]));
-            return !(d > r2);
-        };
-        auto record = [&](bool hit, int pidx) {   // pass 0: set the bit, list the hit
-            const unsigned long long mask = __builtin_amdgcn_ballot_w64(hit);
-            if (hit) {
-                atomicOr(&bm[(unsigned)pidx >> 5], 1u << (pidx & 31));
-                const int pos = H + mbcnt(mask);
-                if (pos < kBmHitCap) hits[pos] = pidx;
-            }
-            H += __popcll(mask);
-        };
-#pragma unroll
-        for (int i = 0; i < 3; ++i) record(64 * i + lane < T && test(p[i]), pi[i]);
-        // rank of index v = number of set bits below it (valid once gbase is up to date)
-        auto rank_of = [&](int v) -> int {
-            const unsigned g = (unsigned)v >> 7, wsel = ((unsigned)v >> 5) & 3u, below = (1u << (v & 31)) - 1u;
-            const u32x4 w = *(const u32x4 *)&bm[g * 4u];
-            int r = (int)gbase[g];
-            r += __popc(w[0] & (wsel > 0u ? ~0u : below));
-            r += __popc(w[1] & (wsel > 1u ? ~0u : wsel == 1u ? below : 0u));
-            r += __popc(w[2] & (wsel > 2u ? ~0u : wsel == 2u ? below : 0u));
-            r += __popc(w[3] & (wsel == 3u ? below : 0u));
-            return r;
-        };
-        int first = 0x7FFFFFFF;   // the hit of rank 0, in the lane that holds it
-        // the candidates beyond the first 192 (pass 0), or every candidate again (pass 1: the hit list overflowed and each
-        // hit is ranked straight from the bitmap)
-        auto walk = [&](const int pass) {
-            for (int g0 = pass == 0 ? 192 : 0; g0 < T; g0 += kWave) {
-                const int g = g0 + lane;
-                const int j = record_of(g);
-                const u32x4 pp = __builtin_amdgcn_raw_buffer_load_b128(rs_rec, g < T ? (unsigned)j * 16u : 0xFFFFFFF0u, 0, 0);
-                const int pidx = (int)__builtin_amdgcn_raw_buffer_load_b32(rs_idx, g < T ? (unsigned)j * 4u : 0xFFFFFFF0u, 0, 0);
-                const bool hit = g < T && test(pp);
-                if (pass == 0) {
-                    record(hit, pidx);
-                } else if (hit) {
-                    const int r = rank_of(pidx);
-                    if (r < K) put(r, pidx);
-                    if (r == 0) first = pidx;
-                }
-            }
-        };
-        if (T > 192) walk(0);
-        if (H == 0) {   // wave-uniform; the bitmap is still clean
-            for (int j = lane; j < K; j += kWave) put(j, N);  // no hit at all -> N (:136-141)
-            cur = nxt;
-            continue;
-        }
-        wave_lds_fence();   // the bits were set by whichever lanes held the hits
-        {   // base rank of every 128-index group
-            unsigned c[4] = {0u, 0u, 0u, 0u};   // nquad <= 4
-            unsigned tot = 0;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                if (t < nquad) {
-                    const u32x4 w = *(const u32x4 *)&bm[(lane * nquad + t) * 4];
-                    c[t] = (unsigned)(__popc(w[0]) + __popc(w[1]) + __popc(w[2]) + __popc(w[3]));
-                    tot += c[t];
-                }
-            }
-            unsigned incl = tot;   // inclusive scan over the 64 lanes
-            incl += dpp_or_zero<0x111, 0xF>(incl);
-            incl += dpp_or_zero<0x112, 0xF>(incl);
-            incl += dpp_or_zero<0x114, 0xF>(incl);
-            incl += dpp_or_zero<0x118, 0xF>(incl);
-            incl += dpp_or_zero<0x142, 0xA>(incl);   // row_bcast:15 into rows 1, 3
-            incl += dpp_or_zero<0x143, 0xC>(incl);   // row_bcast:31 into rows 2, 3
-            unsigned run_ = incl - tot;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                if (t < nquad) {
-                    gbase[lane * nquad + t] = run_;
-                    run_ += c[t];
-                }
-            }
-        }
-        wave_lds_fence();   // gbase and the hit list cross lanes
-        if (H <= kBmHitCap) {
-            for (int i = lane; i < H; i += kWave) {
-                const int v = hits[i];
-                const int r = rank_of(v);
-                if (r < K) put(r, v);
-                if (r == 0) first = v;
-            }
-        } else {
-            walk(1);
-        }
-        if (H < K) {   // pad with the first hit = the smallest index (:138-141)
-            const unsigned long long fm = __ballot(first != 0x7FFFFFFF);
-            const int fv = __builtin_amdgcn_readlane(first, (int)__builtin_ctzll(fm));
-            for (int j = H + lane; j < K; j += kWave) put(j, fv);
-        }
-        wave_lds_fence();   // every rank has been read: the bitmap can be wiped for the next query
-        for (int t = 0; t < nquad; ++t) *(u32x4 *)&bm[(lane * nquad + t) * 4] = u32x4{0u, 0u, 0u, 0u};
-        wave_lds_fence();
-        cur = nxt;
-    }
-}
-
-
-// ------------------------------------------------------------------------------------------------
-// grid path, chunked bitmap kernel (round 6; clouds of up to 32 768 points -- the default)
-// ------------------------------------------------------------------------------------------------
-// ball_grid_query_bitmap_kernel issues ~370 vector instructions per query and runs at the VALU issue limit (one wave64 instruction
-// per 4 cycles and SIMD): every instruction removed is time.  Same cells, same test, same arithmetic, same results; what changed
-// is where the instructions go (profiles/r06_ball_sq_by_stage.txt):
-//   * ONE wave per workgroup, its LDS at fixed offsets: every LDS address is a register plus an instruction offset;
-//   * a wave takes CHUNKS of 16 consecutive queries of one cloud.  The per-query bookkeeping that was wave-uniform work on the
-//     vector ALU -- three cell coordinates, nine cell-table look-ups, the prefix sum of the nine run lengths -- is done once per
-//     chunk with a lane per (query, dy): 16 x 4 lanes, three passes (dz); ends and record offsets of the runs go to a 64-byte
-//     block per query in LDS, next to the query's coordinates and squared norm;
-//   * candidate g of the flattened list finds its run by a three-step binary search over that block's ends in LDS (three
-//     dependent ds_read_u16 + 8 vector instructions) plus one compare for the last run, instead of eight compare/add pairs on
-//     nine v_readlane'd ends per 64 candidates;
-//   * the record carries |p|^2 (ball_grid_build_kernel), the test is 3 fma + 3 add + 1 compare;
-//   * ranks come from a per-WORD exclusive prefix of the bitmap's popcounts (u16, built by the 64 word owners with chained
-//     v_bcnt + one wave scan): rank(v) = base[v >> 5] + bcnt(word & below(v)) -- two LDS reads and ~8 instructions per 64 hits,
-//     where the per-128-index bases needed four masked popcounts (~33).
 constexpr int kChunkQ = 16;            // queries per chunk
 constexpr int kQBlk = 64;              // bytes per query block: 9 run entries (end u16 | delta i16 << 16), pad, (cx, cy, cz, |c|^2) at +48
 
@@ -1035,8 +776,8 @@ static int ball_query_impl(int B, int N, int S, int nsample, float r2, const flo
             if (int rc = check_launch("ball_grid_build_kernel")) return rc;
         }
         if (!query) return TGN_OK;
-        const int bitmap_ok = tuning(kTuneBallBitmap);   // 2: the chunked bitmap kernel; 1: round 2's bitmap kernel; 0: rank-select (experiments)
-        if (bitmap_ok >= 2 && N <= kBmMaxN) {
+        // "ball_bitmap": 0 = the rank-select kernel (the fallback for larger clouds) for every cloud (parity tests)
+        if (tuning(kTuneBallBitmap) && N <= kBmMaxN) {
             const int nquad = (N + 8191) >> 13;
             const int cpc = (S + kChunkQ - 1) / kChunkQ;
             const long long total_chunks = (long long)B * cpc;
@@ -1059,21 +800,6 @@ static int ball_query_impl(int B, int N, int S, int nsample, float r2, const flo
             }
 #undef TGN_BALL_CHUNK
             return check_launch("ball_grid_query_chunk_kernel");
-        }
-        if (bitmap_ok && N <= kBmMaxN) {
-            const int nquad = (N + 8191) >> 13;
-            const size_t lds = (size_t)4 * (nquad * 256 + nquad * 64 + kBmHitCap) * sizeof(unsigned);   // <= 24 KiB per workgroup
-            const long long q_per_xcd = B >= 8 ? (long long)((B + 7) / 8) * S : ((total + 7) / 8 + 3) / 4 * 4;
-            long long nbx = (q_per_xcd + 3) / 4;   // blocks per XCD: what is resident at a time (32 CUs x 8), not more
-            if (nbx > 256) nbx = 256;
-            const unsigned grid = (unsigned)(nbx * 8);
-            if (idx_is_int64)
-                hipLaunchKernelGGL((ball_grid_query_bitmap_kernel<long long>), dim3(grid), dim3(256), lds, st, B, N, S,
-                                   nsample, r2, xyz, new_xyz, (const unsigned char *)workspace, (long long *)idx, q_per_xcd);
-            else
-                hipLaunchKernelGGL((ball_grid_query_bitmap_kernel<int>), dim3(grid), dim3(256), lds, st, B, N, S, nsample,
-                                   r2, xyz, new_xyz, (const unsigned char *)workspace, (int *)idx, q_per_xcd);
-            return check_launch("ball_grid_query_bitmap_kernel");
         }
         if (idx_is_int64)
             hipLaunchKernelGGL((ball_grid_query_kernel<long long>), dim3((unsigned)blocks), dim3(256), 0, st, B, N, S,

@@ -71,25 +71,14 @@ struct TuneEntry {
     int def;
 };
 static const TuneEntry kTune[kTuneCount] = {
-    {"fps_plain", "TGN_FPS_V1", 0},           {"fps_config", "TGN_FPS_CONFIG", 0},       {"fps_bucket_config", "TGN_FPS_BUCKET_CONFIG", 0},
-    {"fps_cell_bits", "TGN_FPS_CELL_BITS", 4}, {"fps_bucket_min", "TGN_FPS_BUCKET_MIN", -1}, {"ball_bitmap", "TGN_BALL_BITMAP", 2},
-    {"knn_memset", "TGN_KNN_MEMSET", 0},      {"knn_grid_scale", "TGN_KNN_GRID_SCALE", 1000}, {"sa_tile", "TGN_SA_TILE", 0},
-    {"gather_v4", "TGN_GATHER_V4", 5},        {"fps_lean", "TGN_FPS_LEAN", 1},
+    {"fps_bucket_min", "TGN_FPS_BUCKET_MIN", -1}, {"fps_lean", "TGN_FPS_LEAN", 1}, {"ball_bitmap", "TGN_BALL_BITMAP", 2},
+    {"sa_tile", "TGN_SA_TILE", 0},                {"gather_v4", "TGN_GATHER_V4", 5},
 };
 static std::atomic<int> g_tune[kTuneCount];
 static const bool g_tune_seeded = [] {   // runs once, at load time, before any launch can read the table
     for (int i = 0; i < kTuneCount; ++i) {
-        int v = kTune[i].def;
-        if (const char *e = getenv(kTune[i].env)) {
-            int a = 0, b = 0;
-            if (i == kTuneFpsConfig || i == kTuneFpsBucketConfig)
-                v = sscanf(e, "%d,%d", &a, &b) == 2 ? a * 256 + b : 0;
-            else if (i == kTuneKnnGridScale)
-                v = (int)(atof(e) * 1000.0 + 0.5);
-            else
-                v = atoi(e);
-        }
-        g_tune[i].store(v, std::memory_order_relaxed);
+        const char *e = getenv(kTune[i].env);
+        g_tune[i].store(e ? atoi(e) : kTune[i].def, std::memory_order_relaxed);
     }
     return true;
 }();
@@ -98,7 +87,7 @@ int tuning(Tuning t) { return g_tune[t].load(std::memory_order_relaxed); }
 
 }  // namespace tgn
 
-// Select a kernel variant (experiments, A/B runs, the parity tests that must reach every variant).  Thread-safe; takes effect
+// Select a kernel variant (A/B runs and the parity tests that must reach every kernel).  Thread-safe; takes effect
 // for launches enqueued after the call.  Returns TGN_ERR_INVALID_ARGUMENT for an unknown key.
 TGN_API int tgn_set_tuning(const char *key, int value) {
     if (key)

@@ -400,43 +400,25 @@ struct FpsConfig {
     int nt, p;
 };
 
-// Ordered by capacity; of two shapes with the same capacity the first is taken.  Fewer waves mean a cheaper hand-off:
-// measured per iteration at 4096 points 256x16 0.71 us, 512x8 0.73, 1024x4 0.74; at 2048 points 256x8 0.55, 512x8 0.73.
-#define TGN_FPS_CONFIGS(X) \
-    X(64, 1) X(64, 2) X(64, 4) X(64, 8) X(64, 16) X(256, 8) X(256, 16) X(512, 8) \
-    X(512, 16) X(512, 24) X(512, 32) X(1024, 24) X(512, 48) X(512, 56)
+// Ordered by capacity.  Fewer waves mean a cheaper hand-off: measured per iteration at 4096 points 256x16 0.71 us, 512x8 0.73,
+// 1024x4 0.74; at 2048 points 256x8 0.55, 512x8 0.73.  Larger clouds take the bucket kernel (fps_bucket.hip).
+#define TGN_FPS_CONFIGS(X) X(64, 1) X(64, 2) X(64, 4) X(64, 8) X(64, 16) X(256, 8) X(256, 16)
 
-static const FpsConfig kConfigs[] = {
+static constexpr FpsConfig kConfigs[] = {
 #define X(NT_, P_) {NT_, P_},
     TGN_FPS_CONFIGS(X)
 #undef X
 };
 constexpr int kNumConfigs = sizeof(kConfigs) / sizeof(kConfigs[0]);
-
-static int fps_capacity() {
-    int c = 0;
-    for (int i = 0; i < kNumConfigs; ++i) c = kConfigs[i].nt * kConfigs[i].p > c ? kConfigs[i].nt * kConfigs[i].p : c;
-    return c;
-}
+static_assert(kConfigs[kNumConfigs - 1].nt * kConfigs[kNumConfigs - 1].p == kFpsPlainMaxN, "the largest plain shape");
 
 static bool fps_pick(int n_max, FpsConfig &out) {
-    // experiments: tgn_set_tuning("fps_config", NT * 256 + P) forces an instantiated shape when it is large enough
-    if (const int forced = tuning(kTuneFpsConfig)) {
-        const int nt = forced >> 8, p = forced & 255;
-        for (int i = 0; i < kNumConfigs; ++i)
-            if (kConfigs[i].nt == nt && kConfigs[i].p == p && nt * p >= n_max) {
-                out = kConfigs[i];
-                return true;
-            }
-    }
-    int best = -1;
-    for (int i = 0; i < kNumConfigs; ++i) {
-        const int cap = kConfigs[i].nt * kConfigs[i].p;
-        if (cap >= n_max && (best < 0 || cap < kConfigs[best].nt * kConfigs[best].p)) best = i;
-    }
-    if (best < 0) return false;
-    out = kConfigs[best];
-    return true;
+    for (int i = 0; i < kNumConfigs; ++i)
+        if (kConfigs[i].nt * kConfigs[i].p >= n_max) {
+            out = kConfigs[i];
+            return true;
+        }
+    return false;
 }
 
 template <int MODE>
@@ -447,15 +429,13 @@ static int fps_launch(int b, int n_max, const FpsArgs &a, hipStream_t stream) {
         if (rc >= 0) return rc;
     }
     {
-        if (!tuning(kTuneFpsPlain)) {   // experiments: "fps_plain" forces the plain (no skipping) kernels
-            const int rc = fps_bucket_launch(MODE, b, n_max, a, stream);
-            if (rc >= 0) return rc;
-        }
+        const int rc = fps_bucket_launch(MODE, b, n_max, a, stream);
+        if (rc >= 0) return rc;
     }
     {
         // small clouds: the lean kernel ("fps_lean": 0 = off, 1 = clouds of 257 .. 2048 points, 2 = up to 4096)
         const int lean = tuning(kTuneFpsLean);
-        if (lean && n_max > 256 && n_max <= (lean >= 2 ? 4096 : 2048) && !tuning(kTuneFpsConfig)) {
+        if (lean && n_max > 256 && n_max <= (lean >= 2 ? 4096 : 2048)) {
 #define X(NT_, P_)                                                                                      \
     if (n_max <= NT_ * P_) {                                                                            \
         hipLaunchKernelGGL((fps_lean_kernel<NT_, P_, MODE>), dim3(b), dim3(NT_), 0, stream, a);       \
@@ -480,7 +460,7 @@ static int fps_launch(int b, int n_max, const FpsArgs &a, hipStream_t stream) {
     }
     if (!a.tmp) {
         set_error("tgn_furthestsampling: cloud of %d points exceeds the resident capacity (%d) and tmp is NULL",
-                  n_max, fps_capacity());
+                  n_max, kFpsResidentCapacity);
         return TGN_ERR_INVALID_ARGUMENT;
     }
     hipLaunchKernelGGL((fps_streaming_kernel<MODE>), dim3(b), dim3(1024), 0, stream, a);
@@ -522,7 +502,7 @@ static int fps_dispatch(int b, int n_max, FpsArgs a, hipStream_t stream) {
 
 using namespace tgn;
 
-TGN_API int tgn_fps_resident_capacity(void) { return fps_capacity(); }
+TGN_API int tgn_fps_resident_capacity(void) { return kFpsResidentCapacity; }
 
 TGN_API int tgn_furthestsampling(int b, int n_max, const float *xyz, const int *offset, const int *new_offset,
                                  float *tmp, void *idx, float *new_xyz, int flags, tgn_stream_t stream) {
@@ -540,7 +520,7 @@ TGN_API size_t tgn_fps_throughput_workspace_bytes(int b, int n_max) {
 }
 
 TGN_API size_t tgn_fps_workspace_bytes(int b, int n_max) {
-    if (n_max <= fps_capacity()) return 0;
+    if (n_max <= kFpsResidentCapacity) return 0;
     return fps_stream_workspace_bytes(b, n_max);
 }
 

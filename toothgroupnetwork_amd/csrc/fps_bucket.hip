@@ -76,19 +76,19 @@ constexpr int next_pow2(int v) {
     return p;
 }
 
-template <int NT, int P, int MODE, bool DBG = false, int CB = 4>
+template <int NT, int P, int MODE>
 __global__ __launch_bounds__(NT) void fps_bucket_kernel(FpsArgs a) {
     constexpr bool FMA = (MODE & 1) != 0, TREE = (MODE & 2) != 0, CERT = (MODE & kFpsModeCert) != 0;
     constexpr int NW = NT / kWave;
     constexpr int CAP = NT * P;
     static_assert(P <= kWave, "bucket metadata lives in lanes 0..P-1");
     static_assert(CAP <= 32768, "15-bit local indices");
-    // Set-up: 32 768 Z-order cells, two 16-bit counters per word (a cloud has < 65 536 points); once the points are
-    // placed the same 64 KiB hold the result staging buffer and the bucket arg-max planes.
-    // CB = bits per axis of the Z-order cell code.  4 (default): 4096 cells, 8 KiB of counters; 5: 32 768 cells, 64 KiB.
-    // The order only decides which bucket a point lands in, never a result, and 12 bits are as good as 15 for buckets of
-    // 64 points (24 000 -> 4096: 3.76 vs 3.75 ms per 256 scans) -- but the workgroup then holds 63 KiB of LDS instead of
+    // Set-up: 4096 Z-order cells (CB = 4 bits per axis), two 16-bit counters per word (a cloud has < 65 536 points); once the
+    // points are placed the same LDS holds the result staging buffer and the bucket arg-max planes.
+    // The order only decides which bucket a point lands in, never a result, and 12 bits are as good as round 1's 15 for buckets
+    // of 64 points (24 000 -> 4096: 3.76 vs 3.75 ms per 256 scans) -- but the workgroup then holds 63 KiB of LDS instead of
     // 116, which is what lets four waves of the row-piece grouping kernel (19 KiB each) run beside it.
+    constexpr int CB = 4;
     constexpr int kCellWords = (1 << (3 * CB)) / 2;
     constexpr int kAliasWords = NT * 4 + 4 * NW * P;
     constexpr int kLdsWords = kCellWords > kAliasWords ? kCellWords : kAliasWords;
@@ -274,21 +274,12 @@ __global__ __launch_bounds__(NT) void fps_bucket_kernel(FpsArgs a) {
     unsigned wr_off = (unsigned)wave * 32u, rd_off = (unsigned)(lane & (NW - 1)) * 32u;
     bool dirty = true;  // bucket maxima only shrink: the candidate changes only when ITS bucket's arg-max changes
 
-    // optional instrumentation (flag 0x100 + tmp): touched-bucket census and per-phase cycles of one wave
-    // compile-time switch: even never-taken `if (dbg)` branches cost a lone wave ~10 cycles each per iteration
-    constexpr bool dbg = DBG;
     // The hand-off record is written by EVERY lane of the wave (same address, same data) in the 8-wave kernels: the
     // lane-0 form costs an exec save / branch / restore on the chain everybody waits for (3.39 -> 3.32 ms for 24 000 -> 4096;
     // the 4-wave kernels, which run beside the level-1 ball query, measured no better with it and keep lane 0)
     constexpr bool kRecAllLanes = NT >= 512;
-    unsigned long long st_skip = 0, st_touched = 0, st_waves = 0, cyA = 0, cyU = 0, cyB = 0, cyC = 0, cyC1 = 0, cyC2 = 0;
-    unsigned long long dbg_sum_max = 0, dbg_crit_is_winner = 0, dbg_crit_dirty = 0, dbg_crit_touched = 0, dbg_sum_winner = 0;
-    unsigned dbg_prev_winner = 0;
-    bool dbg_dirty = false;
 
     for (int j = 1; j < m; ++j) {
-        long long t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-        if (dbg) t0 = clock64();
         // ---- A. which of my buckets can the new sample change? (monotone lower bound, exact) -------------
         // (x, y) as packed fp32 pairs: a lone wave pays per instruction, not per lane-operation
         typedef float f2 __attribute__((ext_vector_type(2)));
@@ -302,11 +293,6 @@ __global__ __launch_bounds__(NT) void fps_bucket_kernel(FpsArgs a) {
         // makes the compiler rebuild the mask through a 0/1 select)
         constexpr unsigned long long kSlotMask = P >= 64 ? ~0ull : ((1ull << P) - 1ull);
         const unsigned long long mask = ballot64(!(L >= bmax)) & kSlotMask;
-        if (dbg) {
-            t1 = clock64();
-            st_touched += __popcll(mask);
-            st_waves += mask ? 1 : 0;
-        }
         if (mask) {  // wave-uniform
             // A lone wave issues roughly one instruction per 5 cycles whatever its kind, so the mask is walked
             // hierarchically (groups of 8 slots, 32-bit tests: 2 scalar instructions per test) rather than bit by bit.
@@ -328,7 +314,6 @@ __global__ __launch_bounds__(NT) void fps_bucket_kernel(FpsArgs a) {
                             const bool unchanged = TGN_REFRESH_SKIP && ballot64(d[s] == bold && dd < d[s]) == 0;  // wave-uniform
                             const float nd = vmin_f32(dd, d[s]);  // min(d, tmp[k]) sampling_cuda_kernel.cu:55
                             d[s] = nd;
-                            if (dbg && unchanged) ++st_skip;
                             if (!unchanged) {
                             // the lane's tie key (original index), wanted by the winner only: issued first so that the
                             // LDS round trip hides behind the reduction
@@ -359,9 +344,7 @@ __global__ __launch_bounds__(NT) void fps_bucket_kernel(FpsArgs a) {
                 }
             }
         }
-        if (dbg) t2 = clock64();
         // ---- B. wave candidate = max over my bucket maxima (recomputed only if a bucket changed) ---------
-        if (dbg) dbg_dirty = dirty;
         if (dirty) {
             // the arg-max records of ALL my buckets (coordinates, tie key) are requested BEFORE the reduction that says which
             // one is wanted: the LDS round trip then hides behind the six DPP steps instead of following them (this is the
@@ -387,7 +370,6 @@ __global__ __launch_bounds__(NT) void fps_bucket_kernel(FpsArgs a) {
             pub_key = wm < 0.0f ? 0xFFFFFFFFu : wkey;
             dirty = false;
         }
-        if (dbg) t3 = clock64();
         // ---- C. block argmax over the wave candidates: one LDS record per wave, ONE barrier ------------------
         unsigned kwin;
         if constexpr (NW == 1) {
@@ -401,43 +383,11 @@ __global__ __launch_bounds__(NT) void fps_bucket_kernel(FpsArgs a) {
                 *(uint2 *)(recb + wr_off) = make_uint2(pub_bits, pub_key);
                 *(float3 *)(recb + wr_off + 16) = make_float3(wx, wy, wz);
             }
-            long long tc1 = 0, tc2 = 0;
-            if (dbg) {
-                tc1 = clock64();
-                // (instrumented build) my pre-barrier time, my touched / refreshed bucket counts and whether I searched for a
-                // new candidate, into the spare bytes of my record
-                if (lane == 0)
-                    *(uint2 *)(recb + wr_off + 8) = make_uint2((unsigned)(tc1 - t0), (unsigned)__popcll(mask) | (dbg_dirty ? 0x100u : 0u));
-            }
             __syncthreads();
-            if (dbg) {
-                tc2 = clock64();
-                cyC1 += tc1 - t3;
-                cyC2 += tc2 - tc1;
-            }
             // distances are >= 0: their bit patterns order like unsigned integers
             // every lane reads record lane % NW (no exec juggling); lanes 0..NW-1 are the ones that count
             const uint2 r0 = *(const uint2 *)(recb + rd_off);
             const float3 r1 = *(const float3 *)(recb + rd_off + 16);  // same LDS round trip
-            if (dbg && wave == 0) {   // who was the slowest wave of this iteration, and was it last iteration's winner?
-                const uint2 dd_ = *(const uint2 *)(recb + rd_off + 8);
-                unsigned tmax = 0, wmax_ = 0, info = 0;
-                for (int w = 0; w < NW; ++w) {
-                    const unsigned tw = (unsigned)__builtin_amdgcn_readlane((int)dd_.x, w);
-                    const unsigned iw = (unsigned)__builtin_amdgcn_readlane((int)dd_.y, w);
-                    if (tw > tmax) {
-                        tmax = tw;
-                        wmax_ = (unsigned)w;
-                        info = iw;
-                    }
-                }
-                dbg_sum_max += tmax;
-                dbg_crit_is_winner += (wmax_ == dbg_prev_winner) ? 1 : 0;
-                dbg_crit_dirty += (info >> 8) & 1u;
-                dbg_crit_touched += info & 0xFFu;
-                const unsigned tw_ = (unsigned)__builtin_amdgcn_readlane((int)dd_.x, (int)dbg_prev_winner);
-                dbg_sum_winner += tw_;
-            }
             rd_off ^= kRecParity;  // double-buffered by iteration parity: one barrier per iteration is enough
             wr_off ^= kRecParity;
             const unsigned vb = r0.x;
@@ -463,7 +413,6 @@ __global__ __launch_bounds__(NT) void fps_bucket_kernel(FpsArgs a) {
                 const unsigned kmin = __builtin_amdgcn_readfirstlane(wave_min_u32_shfl(kk));
                 wl = __builtin_ctzll(ballot64(kk == kmin));
             }
-            if (dbg) dbg_prev_winner = (unsigned)wl;
             kwin = (unsigned)__builtin_amdgcn_readlane((int)r0.y, wl);
             qx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(r1.x), wl));
             qy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(r1.y), wl));
@@ -478,13 +427,6 @@ __global__ __launch_bounds__(NT) void fps_bucket_kernel(FpsArgs a) {
             fps_emit(a, start_m + j - (NT - 1) + tid, start_n, __float_as_int(o.x), o.y, o.z, o.w);
             __syncthreads();
         }
-        if (dbg) {
-            const long long t4 = clock64();
-            cyA += t1 - t0;
-            cyU += t2 - t1;
-            cyB += t3 - t2;
-            cyC += t4 - t3;
-        }
     }
     if (((m - 1) & (NT - 1)) != NT - 1) {  // rows of the last, partial chunk
         __syncthreads();
@@ -495,28 +437,6 @@ __global__ __launch_bounds__(NT) void fps_bucket_kernel(FpsArgs a) {
         }
     }
     if (a.prefix_out && tid == 0) a.prefix_out[blockIdx.x] = CERT ? cert.value(m) : 1;  // not tracked: no claim
-    if (dbg && lane == 0) {
-        unsigned long long *st = (unsigned long long *)a.tmp;
-        atomicAdd(&st[0], st_touched);
-        atomicAdd(&st[1], st_waves);
-        if (wave == 0 && blockIdx.x == 0) {
-            st[2] = cyA;
-            st[3] = cyU;
-            st[4] = cyB;
-            st[5] = cyC;
-            st[6] = (unsigned long long)(m - 1);
-            st[7] = cyC1;
-            st[8] = cyC2;
-            st[10] = dbg_sum_max;
-            st[11] = dbg_crit_is_winner;
-            st[12] = dbg_crit_dirty;
-            st[13] = dbg_crit_touched;
-            st[14] = dbg_sum_winner;
-        }
-        atomicAdd(&st[9], st_skip);
-        if (false) {
-        }
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -938,45 +858,31 @@ int fps_bucket_owner_small_launch(int mode, int b, int n_max, const FpsArgs &a, 
 
 #define TGN_FPS_BUCKET_CONFIGS(X) X(256, 8) X(256, 16) X(512, 16) X(512, 24) X(512, 32) X(512, 48) X(512, 56)
 
+constexpr int fps_bucket_capacity() {
+    int c = 0;
+#define X(NT_, P_) c = NT_ * P_ > c ? NT_ * P_ : c;
+    TGN_FPS_BUCKET_CONFIGS(X)
+#undef X
+    return c;
+}
+static_assert(fps_bucket_capacity() == kFpsResidentCapacity, "the largest bucket shape is the capacity without a workspace");
+
 template <int MODE>
 static int bucket_launch_mode(int b, int n_max, const FpsArgs &a, hipStream_t stream) {
-    int nt = 0, p = 0;
-    if (const int forced = tuning(kTuneFpsBucketConfig)) {  // experiments: force a shape
-        nt = forced >> 8, p = forced & 255;
-        if (nt * p < n_max) nt = p = 0;
-    }
-    if (!nt) {
-        int best = 1 << 30;
+    int nt = 0, p = 0, best = 1 << 30;
 #define X(NT_, P_)                                             \
     if (NT_ * P_ >= n_max && NT_ * P_ < best) {                \
         best = NT_ * P_;                                       \
         nt = NT_;                                              \
         p = P_;                                                \
     }
-        TGN_FPS_BUCKET_CONFIGS(X)
+    TGN_FPS_BUCKET_CONFIGS(X)
 #undef X
-        // beside the ball queries of the phased schedule (TGN_FPS_LOW_VALU) a 2049..4096-point cloud is better off on EIGHT waves
-        // with half-empty slot sets than on four full ones: 0.81 against 0.86 ms for 4096 -> 1024 beside the level-1 query, and the
-        // step 4.51 against 4.55 ms (profiles/r06_phase2_experiments.txt; it lost in round 2, when the query beside it issued
-        // 2.4 times the vector instructions)
-        if ((a.flags & TGN_FPS_LOW_VALU) && nt == 256 && p == 16) nt = 512;
-    }
-    if constexpr (MODE == 0) {   // experiments: "fps_cell_bits" = 5 selects the 15-bit cell codes of round 1 (116 KiB of LDS)
-        const int cell_bits = tuning(kTuneFpsCellBits);
-#define X(NT_, P_)                                                                                              \
-    if (cell_bits == 5 && nt == NT_ && p == P_ && !(a.flags & 0x100)) {                                          \
-        hipLaunchKernelGGL((fps_bucket_kernel<NT_, P_, MODE, false, 5>), dim3(b), dim3(NT_), 0, stream, a);     \
-        return check_launch("fps_bucket_kernel<cb5>");                                                           \
-    }
-        TGN_FPS_BUCKET_CONFIGS(X)
-#undef X
-    }
-    if constexpr (MODE == 0) {
-        if ((a.flags & 0x100) && a.tmp && nt == 512 && p == 48) {  // instrumented build (tools/fps_stats.py)
-            hipLaunchKernelGGL((fps_bucket_kernel<512, 48, 0, true>), dim3(b), dim3(512), 0, stream, a);
-            return check_launch("fps_bucket_kernel<dbg>");
-        }
-    }
+    // beside the ball queries of the phased schedule (TGN_FPS_LOW_VALU) a 2049..4096-point cloud is better off on EIGHT waves
+    // with half-empty slot sets than on four full ones: 0.81 against 0.86 ms for 4096 -> 1024 beside the level-1 query, and the
+    // step 4.51 against 4.55 ms (profiles/r06_phase2_experiments.txt; it lost in round 2, when the query beside it issued
+    // 2.4 times the vector instructions)
+    if ((a.flags & TGN_FPS_LOW_VALU) && nt == 256 && p == 16) nt = 512;
 #define X(NT_, P_)                                                                                   \
     if (nt == NT_ && p == P_) {                                                                      \
         hipLaunchKernelGGL((fps_bucket_kernel<NT_, P_, MODE>), dim3(b), dim3(NT_), 0, stream, a);    \
@@ -990,9 +896,10 @@ static int bucket_launch_mode(int b, int n_max, const FpsArgs &a, hipStream_t st
 int fps_bucket_launch(int mode, int b, int n_max, const FpsArgs &a, hipStream_t stream) {
     // Measured (profiles/r01_fps_bucket_sweep.txt): 24 000 points 0.89 vs 2.25 us per iteration, 6000 points 0.79 vs
     // 0.98, 4096 points 0.78 vs 0.72 -- there the plain kernel wins (8 points per lane: its whole iteration is already
-    // fixed cost).  tgn_set_tuning("fps_bucket_min") overrides.
+    // fixed cost).  tgn_set_tuning("fps_bucket_min") overrides, but never above kFpsPlainMaxN + 1: fps.hip has no plain kernel
+    // for a larger cloud.
     int min_n = (a.flags & TGN_FPS_LOW_VALU) ? 2048 : 4097;
-    if (const int forced = tuning(kTuneFpsBucketMin); forced >= 0) min_n = forced;
+    if (const int forced = tuning(kTuneFpsBucketMin); forced >= 0) min_n = forced <= kFpsPlainMaxN ? forced : kFpsPlainMaxN + 1;
     if (n_max < min_n) return -1;
     switch (mode) {  // bit 0 FMA, bit 1 tree ties, bit 2 certificate tracking (never with tree ties)
         case 0: return bucket_launch_mode<0>(b, n_max, a, stream);

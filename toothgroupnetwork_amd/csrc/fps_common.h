@@ -227,6 +227,12 @@ __device__ __forceinline__ unsigned fps_block_argmax(float best, unsigned key, u
     }
 }
 
+// The plain register-resident kernels of fps.hip cover clouds of up to kFpsPlainMaxN points; every larger cloud takes the
+// bucket-skipping kernel of fps_bucket.hip, whose largest shape holds kFpsResidentCapacity points: the largest cloud that needs
+// no workspace (tgn_fps_resident_capacity).
+constexpr int kFpsPlainMaxN = 4096;
+constexpr int kFpsResidentCapacity = 512 * 56;
+
 // fps_bucket.hip: launches the bucket-skipping kernel when a shape covers n_max; returns -1 if none does.
 int fps_bucket_launch(int mode, int b, int n_max, const FpsArgs &a, hipStream_t stream);
 // large clouds through a cell-sorted workspace; -1 if the workspace is missing / too small / cloud too large

@@ -169,16 +169,13 @@ __global__ __launch_bounds__(256) void aggregation_bwd_kernel(long long rows, in
     }
 }
 
-// ---- the same eight kernels with 16-byte lanes --------------------------------------------------------
+// ---- the four forward kernels with 16-byte lanes -------------------------------------------------------
 // Taken when c % 4 == 0 and every row base is 16-byte aligned (the shapes of the Point-Transformer stages: c = 32 ... 512,
 // w_c = c / 8).  A lane owns FOUR consecutive channels (global_load/store_dwordx4), a group of cx = 2^cx_log2 lanes owns a row.
-//   * forward gathers (grouping, subtraction) walk the OUTPUT rows, four rows per lane in flight;
-//   * the reductions walk the POINTS: a lane group keeps the sum over a point's nsample neighbours (aggregation forward, in the
-//     reference's j order: bit-identical) or over its rows (subtraction backward: grad_input1 is ONE read-modify-write per point
-//     instead of nsample atomics; aggregation backward: grad_weight is summed over the c / w_c channels that share a weight
-//     across the lanes and added once) -- every such element has exactly one owner, so no atomics; what the caller pre-filled is
-//     still accumulated into, like the reference's atomicAdd onto a zeroed buffer;
-//   * the scatters (grad of a gathered operand) stay hardware fp32 atomics: their targets are data dependent.
+//   * the gathers (grouping, subtraction) walk the OUTPUT rows, four rows per lane in flight;
+//   * aggregation walks the POINTS: a lane group keeps the sum over a point's nsample neighbours in the reference's j order
+//     (bit-identical) and adds it once to what the caller pre-filled, like the reference's accumulation into a zeroed buffer.
+// The backward kernels keep dword lanes (the owner-side kernels below; docs/NEGATIVE_RESULTS.md: 16-byte lanes for the scatters).
 typedef float f4 __attribute__((ext_vector_type(4)));
 
 struct Vec4Shape {
@@ -208,13 +205,6 @@ static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 
     const int tx = threadIdx.x & (cx - 1);  \
     const int ty = threadIdx.x >> cx_log2;  \
     const int ry = blockDim.x >> cx_log2;
-
-__device__ __forceinline__ void atomic_add4(float *dst, f4 v) {
-    atomicAdd(dst + 0, v.x);
-    atomicAdd(dst + 1, v.y);
-    atomicAdd(dst + 2, v.z);
-    atomicAdd(dst + 3, v.w);
-}
 
 constexpr int kV4Rows = 4;  // output rows a lane keeps in flight
 
@@ -252,16 +242,6 @@ __global__ __launch_bounds__(256) void gather_rows_v4_kernel(long long rows, int
     }
 }
 
-__global__ __launch_bounds__(256) void grouping_bwd_v4_kernel(long long rows, int c4, int cx_log2,
-                                                               const f4 *__restrict__ grad_output,
-                                                               const int *__restrict__ idx, float *__restrict__ grad_input) {
-    TGN_V4_LANES
-    for (long long r = (long long)blockIdx.x * ry + ty; r < rows; r += (long long)gridDim.x * ry) {
-        float *dst = grad_input + (size_t)idx[r] * c4 * 4;
-        for (int ci = tx; ci < c4; ci += cx) atomic_add4(dst + ci * 4, grad_output[(size_t)r * c4 + ci]);
-    }
-}
-
 __global__ __launch_bounds__(256) void interpolation_fwd_v4_kernel(long long rows, int c4, int k, int cx_log2,
                                                                     const f4 *__restrict__ input,
                                                                     const int *__restrict__ idx,
@@ -273,43 +253,6 @@ __global__ __launch_bounds__(256) void interpolation_fwd_v4_kernel(long long row
             f4 acc = output[(size_t)r * c4 + ci];  // the reference accumulates into the (pre-zeroed) output
             for (int i = 0; i < k; ++i) acc = acc + input[(size_t)idx[r * k + i] * c4 + ci] * weight[r * k + i];
             output[(size_t)r * c4 + ci] = acc;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void interpolation_bwd_v4_kernel(long long rows, int c4, int k, int cx_log2,
-                                                                    const f4 *__restrict__ grad_output,
-                                                                    const int *__restrict__ idx,
-                                                                    const float *__restrict__ weight,
-                                                                    float *__restrict__ grad_input) {
-    TGN_V4_LANES
-    for (long long r = (long long)blockIdx.x * ry + ty; r < rows; r += (long long)gridDim.x * ry) {
-        for (int ci = tx; ci < c4; ci += cx) {
-            const f4 g = grad_output[(size_t)r * c4 + ci];
-            for (int i = 0; i < k; ++i)
-                atomic_add4(grad_input + ((size_t)idx[r * k + i] * c4 + ci) * 4, g * weight[r * k + i]);
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void subtraction_bwd_v4_kernel(long long n, int nsample, int c4, int cx_log2,
-                                                                  const int *__restrict__ idx,
-                                                                  const f4 *__restrict__ grad_output,
-                                                                  f4 *__restrict__ grad_input1,
-                                                                  float *__restrict__ grad_input2) {
-    TGN_V4_LANES
-    for (long long p = (long long)blockIdx.x * ry + ty; p < n; p += (long long)gridDim.x * ry) {
-        const int *__restrict__ ip = idx + p * nsample;
-        for (int ci = tx; ci < c4; ci += cx) {
-            const f4 *__restrict__ src = grad_output + (size_t)p * nsample * c4 + ci;
-            f4 s = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll 4
-            for (int j = 0; j < nsample; ++j) {
-                const f4 g = src[(size_t)j * c4];
-                s = s + g;
-                atomic_add4(grad_input2 + ((size_t)ip[j] * c4 + ci) * 4, -g);
-            }
-            grad_input1[(size_t)p * c4 + ci] = grad_input1[(size_t)p * c4 + ci] + s;  // the point's only owner: no atomic
         }
     }
 }
@@ -335,46 +278,11 @@ __global__ __launch_bounds__(256) void aggregation_fwd_v4_kernel(long long n, in
     }
 }
 
-__global__ __launch_bounds__(256) void aggregation_bwd_v4_kernel(long long n, int nsample, int w4, int cx_log2,
-                                                                  const f4 *__restrict__ input,
-                                                                  const f4 *__restrict__ position,
-                                                                  const f4 *__restrict__ weight,
-                                                                  const int *__restrict__ idx,
-                                                                  const f4 *__restrict__ grad_output,
-                                                                  float *__restrict__ grad_input,
-                                                                  f4 *__restrict__ grad_position,
-                                                                  f4 *__restrict__ grad_weight) {
-    // one lane per channel quad (c4 == cx, a power of two <= 64; w4 a power of two dividing it): the lanes tx, tx + w4, tx + 2 w4 ...
-    // share weight quad tx % w4 -- their products are summed by xor-shuffles over the lane bits >= log2(w4)
-    TGN_V4_LANES
-    const int c4 = cx;
-    const int wq = tx & (w4 - 1);
-    for (long long p = (long long)blockIdx.x * ry + ty; p < n; p += (long long)gridDim.x * ry) {
-        const int *__restrict__ ip = idx + p * nsample;
-        const f4 go = grad_output[(size_t)p * c4 + tx];
-        for (int j = 0; j < nsample; ++j) {
-            const size_t ii = (size_t)p * nsample + j;
-            const f4 w = weight[ii * w4 + wq];
-            const size_t in_i = (size_t)ip[j] * c4 + tx;
-            const f4 gw = go * w;
-            f4 t = go * (input[in_i] + position[ii * c4 + tx]);
-            atomic_add4(grad_input + in_i * 4, gw);
-            grad_position[ii * c4 + tx] = gw;
-            for (int m = w4; m < cx; m <<= 1) {
-                t.x += __shfl_xor(t.x, m, kWave);
-                t.y += __shfl_xor(t.y, m, kWave);
-                t.z += __shfl_xor(t.z, m, kWave);
-                t.w += __shfl_xor(t.w, m, kWave);
-            }
-            if (tx < w4) grad_weight[ii * w4 + tx] = grad_weight[ii * w4 + tx] + t;  // one owner per weight quad
-        }
-    }
-}
-
 // ---- the two reducing backward kernels with one lane per CHANNEL ---------------------------------------------------------
 // An fp32 atomic instruction whose lanes cover whole 128-byte lines (32 consecutive floats of one target row) is one request
-// per line; the 16-byte-lane form above spreads a row over four instructions that each touch every fourth dword.  So the
-// scatters keep dword lanes, and only the owner-side sums (grad_input1, grad_weight) change.
+// per line; a 16-byte-lane form spreads a row over four instructions that each touch every fourth dword.  So the scatters
+// keep dword lanes, and only the owner-side sums (grad_input1 over a point's rows, grad_weight over the c / w_c channels that
+// share a weight) have one owner each and need no atomics.
 __global__ __launch_bounds__(256) void subtraction_bwd_own_kernel(long long n, int nsample, int c, int cx_log2,
                                                                    const int *__restrict__ idx,
                                                                    const float *__restrict__ grad_output,
@@ -643,12 +551,6 @@ TGN_API int tgn_grouping_backward(int m, int nsample, int c, const float *grad_o
                                   float *grad_input, tgn_stream_t stream) {
     const long long rows = (long long)m * nsample;
     if (rows <= 0 || c <= 0) return TGN_OK;
-    if ((tuning(kTuneGatherV4) & 2) && c % 4 == 0 && aligned16(grad_output)) {
-        const Vec4Shape v = vec4_shape(rows, c, 1);
-        hipLaunchKernelGGL(grouping_bwd_v4_kernel, dim3(v.blocks), dim3(256), 0, (hipStream_t)stream, rows, c / 4, v.cx_log2,
-                           (const f4 *)grad_output, idx, grad_input);
-        return check_launch("grouping_bwd_v4_kernel");
-    }
     const RowShape s = row_shape(rows, c);
     hipLaunchKernelGGL(grouping_bwd_kernel, dim3(s.blocks), dim3(256), 0, (hipStream_t)stream, rows, c, s.cx_log2,
                        grad_output, idx, grad_input);
@@ -673,12 +575,6 @@ TGN_API int tgn_interpolation_forward(int n, int c, int k, const float *input, c
 TGN_API int tgn_interpolation_backward(int n, int c, int k, const float *grad_output, const int *idx,
                                        const float *weight, float *grad_input, tgn_stream_t stream) {
     if (n <= 0 || c <= 0) return TGN_OK;
-    if ((tuning(kTuneGatherV4) & 2) && c % 4 == 0 && aligned16(grad_output)) {
-        const Vec4Shape v = vec4_shape(n, c, 1);
-        hipLaunchKernelGGL(interpolation_bwd_v4_kernel, dim3(v.blocks), dim3(256), 0, (hipStream_t)stream, (long long)n, c / 4, k,
-                           v.cx_log2, (const f4 *)grad_output, idx, weight, grad_input);
-        return check_launch("interpolation_bwd_v4_kernel");
-    }
     const RowShape s = row_shape(n, c);
     hipLaunchKernelGGL(interpolation_bwd_kernel, dim3(s.blocks), dim3(256), 0, (hipStream_t)stream, (long long)n, c, k,
                        s.cx_log2, grad_output, idx, weight, grad_input);
@@ -710,12 +606,6 @@ TGN_API int tgn_subtraction_backward(int n, int nsample, int c, const int *idx, 
         hipLaunchKernelGGL(subtraction_bwd_own_kernel, dim3(s.blocks), dim3(256), 0, (hipStream_t)stream, (long long)n, nsample, c,
                            s.cx_log2, idx, grad_output, grad_input1, grad_input2);
         return check_launch("subtraction_bwd_own_kernel");
-    }
-    if ((tuning(kTuneGatherV4) & 2) && c % 4 == 0 && aligned16(grad_output) && aligned16(grad_input1)) {
-        const Vec4Shape v = vec4_shape(n, c, 1);
-        hipLaunchKernelGGL(subtraction_bwd_v4_kernel, dim3(v.blocks), dim3(256), 0, (hipStream_t)stream, (long long)n, nsample,
-                           c / 4, v.cx_log2, idx, (const f4 *)grad_output, (f4 *)grad_input1, grad_input2);
-        return check_launch("subtraction_bwd_v4_kernel");
     }
     const RowShape s = row_shape(rows, c);
     hipLaunchKernelGGL(subtraction_bwd_kernel, dim3(s.blocks), dim3(256), 0, (hipStream_t)stream, rows, nsample, c,
@@ -757,18 +647,6 @@ TGN_API int tgn_aggregation_backward(int n, int nsample, int c, int w_c, const f
         hipLaunchKernelGGL(aggregation_bwd_own_kernel, dim3(s.blocks), dim3(256), 0, (hipStream_t)stream, (long long)n, nsample, w_c,
                            s.cx_log2, input, position, weight, idx, grad_output, grad_input, grad_position, grad_weight);
         return check_launch("aggregation_bwd_own_kernel");
-    }
-    if (tuning(kTuneGatherV4) & 2) {
-        const int c4 = c / 4, w4 = w_c / 4;
-        const bool pow2 = c % 4 == 0 && w_c % 4 == 0 && c4 <= 64 && (c4 & (c4 - 1)) == 0 && (w4 & (w4 - 1)) == 0 && w4 <= c4;
-        if (pow2 && aligned16(input) && aligned16(position) && aligned16(weight) && aligned16(grad_output) &&
-            aligned16(grad_position) && aligned16(grad_weight)) {
-            const Vec4Shape v = vec4_shape(n, c, 1);
-            hipLaunchKernelGGL(aggregation_bwd_v4_kernel, dim3(v.blocks), dim3(256), 0, (hipStream_t)stream, (long long)n,
-                               nsample, w4, v.cx_log2, (const f4 *)input, (const f4 *)position, (const f4 *)weight, idx,
-                               (const f4 *)grad_output, grad_input, (f4 *)grad_position, (f4 *)grad_weight);
-            return check_launch("aggregation_bwd_v4_kernel");
-        }
     }
     const RowShape s = row_shape(n, c);
     hipLaunchKernelGGL(aggregation_bwd_kernel, dim3(s.blocks), dim3(256), 0, (hipStream_t)stream, (long long)n, nsample,

@@ -789,7 +789,6 @@ __global__ void knn_zero_word_kernel(int *w) { *w = 0; }
 // memset node of the HIP graph, and replays of graphs holding such a node on a block of torch's private pool faulted on
 // ROCm 7.2 whenever an eager allocation happened between two replays (tools/experiments/pt_capture_parts.py).
 static int zero_redo(int *redo, hipStream_t st) {
-    if (tuning(kTuneKnnMemset)) return hipMemsetAsync(redo, 0, sizeof(int), st) == hipSuccess ? 0 : 1;
     hipLaunchKernelGGL(knn_zero_word_kernel, dim3(1), dim3(1), 0, st, redo);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
@@ -843,7 +842,7 @@ TGN_API int tgn_knnquery_grid(int b, int n, int m, int nsample, const float *xyz
         set_error("tgn_knnquery_grid: clearing the redo counter failed");
         return TGN_ERR_LAUNCH;
     }
-    const float scale = 0.001f * (float)tuning(kTuneKnnGridScale);  // cell size relative to the estimated k-neighbour radius
+    const float scale = 1.0f;  // cell size relative to the estimated k-neighbour radius
     hipLaunchKernelGGL(knn_grid_build_kernel, dim3(b), dim3(kKnnBuildThreads), 0, st, b, m, nsample, scale, xyz, offset,
                        (unsigned char *)workspace);
     if (int rc = check_launch("knn_grid_build_kernel")) return rc;

@@ -24,18 +24,12 @@ int *index_error_word(hipStream_t stream);
 // Kernel-variant switches (capi.hip; include/tgn_pointops.h: tgn_set_tuning).  One table of atomics, read with a relaxed load on
 // the launch paths -- no getenv() there.  The legacy TGN_* environment names seed the table ONCE, when the library is loaded.
 enum Tuning {
-    kTuneFpsPlain = 0,      // "fps_plain": 1 = the plain register-resident / streaming FPS kernels, no bucket skipping
-    kTuneFpsConfig,         // "fps_config": NT * 256 + P forces an instantiated plain-kernel shape (0 = pick)
-    kTuneFpsBucketConfig,   // "fps_bucket_config": NT * 256 + P forces a bucket-kernel shape (0 = pick)
-    kTuneFpsCellBits,       // "fps_cell_bits": 4 (12-bit cell codes, default) or 5 (round 1's 15-bit codes)
-    kTuneFpsBucketMin,      // "fps_bucket_min": smallest cloud the bucket kernel takes (-1 = the built-in thresholds)
-    kTuneBallBitmap,        // "ball_bitmap": 0 = the rank-select ball-query kernel
-    kTuneKnnMemset,         // "knn_memset": 1 = clear the redo counter with hipMemsetAsync (reproduces the graph-replay fault)
-    kTuneKnnGridScale,      // "knn_grid_scale": kNN grid cell size, per mille of the estimated k-neighbour radius (1000)
-    kTuneSaTile,            // "sa_tile": 0 = pick, 128 / 256 = force the workgroup tile of tgn_sa_mlp2_max_bf16x3
-    kTuneGatherV4,          // "gather_v4": gather-family variants, bit 0: forward kernels with 16-byte lanes; bit 1: backward kernels with
-                            // 16-byte lanes; bit 2: subtraction / aggregation backward with dword lanes and owner-side sums (wins over bit 1)
+    kTuneFpsBucketMin = 0,  // "fps_bucket_min": smallest cloud the bucket kernel takes (-1 = the built-in thresholds; at most 4097)
     kTuneFpsLean,           // "fps_lean": 0 = fps_resident_kernel for small clouds too, 1 = fps_lean_kernel for 257 .. 2048 points, 2 = up to 4096
+    kTuneBallBitmap,        // "ball_bitmap": 0 = the rank-select ball-query kernel, otherwise the chunked bitmap kernel
+    kTuneSaTile,            // "sa_tile": 0 = pick, 128 / 256 = force the workgroup tile of tgn_sa_mlp2_max_bf16x3
+    kTuneGatherV4,          // "gather_v4": gather-family variants, bit 0: forward kernels with 16-byte lanes; bit 2: subtraction /
+                            // aggregation backward with owner-side sums
     kTuneCount
 };
 int tuning(Tuning t);
