@@ -437,6 +437,30 @@ int tgn_take_index_error_device(void);
  * that a bit latched by an earlier UNCHECKED launch is not attributed to it. */
 int tgn_clear_index_error(tgn_stream_t stream);
 
+/*
+ * The crop step between the two stages of tgnet_fps's GroupingNetworkModule (models/modules/grouping_network_module.py:45-72, on the
+ * labelled path): per-label centroids, the k nearest points of every centroid, the centred crops.  The reference runs it on the host
+ * (numpy, an sklearn KDTree, python gathers).  feats (b, c_stride, n) channel-first float32 with xyz in channels 0..2; labels (b, n) int64.
+ *   tgn_label_centroids: counts (b, nlab) int32 and cent (b, nlab, 3) float32 over the labels 0..nlab-1 (-1 = gingiva is skipped), cent
+ *     bit-equal to numpy's xyz[label == t].mean(axis=0): a sequential float32 sum in point order divided by the count (NaN for an absent
+ *     label).  1 <= nlab <= 64.  A label outside [-1, nlab) is ignored and latches bit 1 of the stream's error word (tgn_take_index_error).
+ *   tgn_crop_knn: for crop t (centroid cent (t_total, 3), scan crop_scan[t]) the k nearest points of that scan, idx_out (t_total, k)
+ *     int64, ascending in the float64 squared distance ((0 + dx*dx) + dy*dy) + dz*dz (dx = double(x) - double(cx), unfused: sklearn's
+ *     euclidean rdist on KDTree's float64 copy), equal distances by ascending point index (KDTree leaves their order unspecified).
+ *     1 <= k <= min(n, 4096).  A crop_scan value outside [0, b) latches bit 1 and writes index 0.
+ *   tgn_crop_gather_center: out (t_total, c, k) = feats[crop_scan[t]][:, idx[t]] with channels 0..2 minus their mean over the k points
+ *     (float64 sum in a fixed order, the mean rounded once to float32, subtracted in float32: ops_utils.centering_object); out_labels
+ *     (t_total, 1, k) int64 = labels[crop_scan[t]][idx[t]] with every value >= 0 set to 0 (NULL: not written).  An index outside [0, n)
+ *     reads point 0 and latches bit 1.
+ * Deterministic: no atomic whose order reaches an output.  t_total = 0 launches nothing.
+ */
+int tgn_label_centroids(int b, int n, int c_stride, const float *feats, const long long *labels, int nlab, int *counts, float *cent,
+                        tgn_stream_t stream);
+int tgn_crop_knn(int b, int n, int c_stride, const float *feats, int t_total, const int *crop_scan, const float *cent, int k,
+                 long long *idx_out, tgn_stream_t stream);
+int tgn_crop_gather_center(int b, int n, int c, int t_total, int k, const float *feats, const int *crop_scan, const long long *idx,
+                           const long long *labels, float *out, long long *out_labels, tgn_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * 4. Mesh input of the preprocess path (HOST pointers, CPU code): gen_utils.read_txt_obj_ls (gen_utils.py:207-233).
  * ---------------------------------------------------------------------------------------- */

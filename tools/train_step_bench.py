@@ -215,6 +215,54 @@ def run(net, opt, feat, xyz, label, steps, amp):
     return out
 
 
+def run_grouping_module(n, steps, dev):
+    """A training step of nets.GroupingNetworkModule (models/modules/grouping_network_module.py; train_configs/tgnet_fps.py) on one
+    labelled arch scan: both stages, the tooth crops on the GPU (crops.tooth_crops, one host synchronisation), class losses of both
+    stages plus the first stage's offset term, backward, SGD.  Also times the crop step alone next to the fp32 square_distance + topk
+    crop of TwoStage at the same T and k (neither includes the centring)."""
+    from toothgroupnetwork_amd import crops, nets
+    rows, lab = synth.labelled_arch(n, 14, seed=3)
+    feat = torch.from_numpy(np.ascontiguousarray(rows.T))[None].to(dev)
+    gt = torch.from_numpy(lab).to(dev)
+    half = gt.clone()
+    half[half >= 9] -= 8
+    k = min(3072, n // 2)
+    cfg = {"model_parameter": {"input_feat": 6, "stride": [1, 4, 4, 4, 4], "nsample": [36, 24, 24, 24, 24], "blocks": [2, 3, 4, 6, 3],
+                               "block_num": 5, "planes": [32, 64, 128, 256, 512], "crop_sample_size": k}}
+    torch.manual_seed(0)
+    net = nets.GroupingNetworkModule(cfg).to(dev).train()
+    opt = torch.optim.SGD(net.parameters(), lr=1e-3, momentum=0.9)
+
+    def step():
+        o = net([feat, gt.view(1, 1, -1)])
+        loss = F.cross_entropy(o["sem_1"], (half + 1)[None]) + F.cross_entropy(o["sem_2"], o["cluster_gt_seg_label"][:, 0] + 1) \
+            + 0.03 * o["offset_1"].square().sum(1).mean()
+        opt.zero_grad(set_to_none=False)
+        loss.backward()
+        opt.step()
+        return float(loss.detach()), o["sem_2"].shape[0]
+
+    def timed(fn, reps):
+        out, ms = [], []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            r = fn()
+            b.record()
+            torch.cuda.synchronize()
+            out.append(r)
+            ms.append(a.elapsed_time(b))
+        return out, ms
+    r, ms = timed(step, steps + 1)
+    _, crop_ms = timed(lambda: crops.tooth_crops(feat, gt[None], k=k), 20)
+    xyz = feat[0, :3].T.contiguous()
+    cent = torch.cat(crops.tooth_crops(feat, gt[None], k=k).centroids)
+    _, topk_ms = timed(lambda: U.square_distance(cent[None], xyz[None])[0].topk(k, dim=1, largest=False)[1], 20)
+    return dict(ms_per_step=float(np.median(ms[1:])), first_loss=r[0][0], last_loss=r[-1][0], crops=f"{r[0][1]} x {k}",
+                crop_step_ms=float(np.median(crop_ms[1:])), square_distance_topk_ms=float(np.median(topk_ms[1:])),
+                params=sum(p.numel() for p in net.parameters()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=24000)
@@ -222,6 +270,8 @@ def main():
     ap.add_argument("--small", action="store_true", help="reduced widths / depths (tests)")
     ap.add_argument("--two-stage", action="store_true", help="also time the full two-stage step (first-stage network + ~14 crops of 3072 "
                     "points through a second U-Net, grouping_network_module.py:16-101), eager and as a HIP graph")
+    ap.add_argument("--two-stage-module", action="store_true", help="also time a training step of nets.GroupingNetworkModule (fp32, eager, "
+                    "a labelled arch scan with its real tooth count; on-device crops) and its crop step against square_distance + topk")
     ap.add_argument("--graph", action="store_true", help="also capture the whole step in a HIP graph and time its replays")
     ap.add_argument("--profile", action="store_true", help="print the top GPU kernels of one bf16-autocast step (torch.profiler)")
     args = ap.parse_args()
@@ -262,6 +312,8 @@ def main():
                     params=sum(p.numel() for p in net2.parameters()))
             except Exception as e:  # noqa: BLE001
                 res[f"two_stage_fp32_{'graph' if graph else 'eager'}"] = f"failed: {type(e).__name__} {str(e)[:300]}"
+    if args.two_stage_module:
+        res["two_stage_module_fp32_eager"] = run_grouping_module(args.points, args.steps, dev)
     if args.profile:
         from torch.profiler import ProfilerActivity, profile
         with profile(activities=[ProfilerActivity.CUDA, ProfilerActivity.CPU]) as prof:

@@ -112,6 +112,9 @@ SIGNATURES = {
     "tgn_take_index_error_device": (c_int, []),
     "tgn_clear_index_error": (c_int, [_P]),
     "tgn_square_distance": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P]),
+    "tgn_label_centroids": (c_int, [c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P]),
+    "tgn_crop_knn": (c_int, [c_int, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P]),
+    "tgn_crop_gather_center": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
     # section 4 (host pointers)
     "tgn_obj_count": (c_int, [ctypes.c_char_p, _P, _P]),
     "tgn_obj_read": (c_int, [ctypes.c_char_p, _P, _P, ctypes.c_longlong, ctypes.c_longlong, _P, _P]),

@@ -1,0 +1,94 @@
+"""On-device tooth crops: the step between the two stages of tgnet_fps's GroupingNetworkModule
+(models/modules/grouping_network_module.py:45-72, labelled path).  The reference does it on the host -- numpy per-label means, an
+sklearn KDTree queried for k points (ops_utils.get_nearest_neighbor_idx), fancy-index gathers (get_indexed_features) and a centring
+loop (centering_object); here it is three HIP kernels (csrc/crop.hip, include/tgn_pointops.h):
+
+  centroids   bit-equal to numpy's xyz[label == t].mean(axis=0) for every label t != -1 present in the scan, ascending (np.unique)
+  crops       the k nearest points of each centroid in ascending float64 squared distance, equal distances by ascending index
+              (KDTree leaves that order unspecified; the index set and the distance sequence are the same)
+  centring    channels 0..2 minus their mean over the crop: a float64 sum rounded once to float32, subtracted in float32
+
+Centroids from clustering (the unlabelled path: ops_utils.get_clustering_labels, sklearn DBSCAN) are not computed here; a caller that
+has them passes them as `centroids`.
+"""
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import _lib
+
+NUM_LABELS = 16          # tooth labels 0..15, -1 = gingiva (generator.py:46-47)
+MAX_K = 4096             # ops_utils.get_nearest_neighbor_idx's default crop_num; the kernel's limit
+_CROP_ERROR = 2          # bit 1 of the stream's error word (include/tgn_pointops.h: tgn_label_centroids)
+
+ToothCrops = namedtuple("ToothCrops", "cropped nn_crop_indexes cluster_gt_seg_label centroids")
+
+
+def _labels_2d(labels, B, N):
+    if labels.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"labels must be int32 or int64, got {labels.dtype}")
+    if labels.dim() == 3 and labels.shape[1] == 1:
+        labels = labels[:, 0]
+    if tuple(labels.shape) != (B, N):
+        raise ValueError(f"labels must be (B, N) or (B, 1, N) = ({B}, {N}), got {tuple(labels.shape)}")
+    return labels.to(torch.int64).contiguous()
+
+
+def tooth_crops(feats, labels=None, centroids=None, k=3072, num_labels=NUM_LABELS):
+    """feats (B, C, N) float32 with xyz in channels 0..2; labels (B, N) or (B, 1, N), int32 or int64, -1 = gingiva, teeth
+    0..num_labels-1.  Returns ToothCrops:
+      cropped               (T, C, k) float32, scan-major, teeth ascending: the reference's centred cropped_feature_ls
+      nn_crop_indexes       list over scans of (T_b, k) int64 device tensors (the reference's list of KDTree results)
+      cluster_gt_seg_label  (T, 1, k) int64, every label >= 0 set to 0 (gingiva stays -1); None without labels
+      centroids             list over scans of (T_b, 3) float32 device tensors (the reference's cluster_centroids)
+    `centroids` (a list over scans of (T_b, 3) arrays or tensors) replaces the label centroids, e.g. cluster centres.
+
+    ONE host synchronisation, with labels and no centroids: reading the per-label point counts to learn T and which teeth are
+    present -- the reference has to know that on the host as well (np.unique).  The label check behind it reads the stream's error
+    word, which by then waits on nothing.  Raises ValueError for labels outside [-1, num_labels) and when no tooth is present."""
+    _lib.require_cuda(feats, labels if isinstance(labels, torch.Tensor) else None)
+    if labels is None and centroids is None:
+        raise ValueError("tooth_crops needs labels or centroids: centroids from clustering (ops_utils.get_clustering_labels, sklearn "
+                         "DBSCAN on the moved foreground points) are the caller's to compute -- out of scope here (SURVEY.md section 2)")
+    if feats.dim() != 3 or feats.shape[1] < 3:
+        raise ValueError(f"feats must be (B, C >= 3, N), got {tuple(feats.shape)}")
+    if feats.dtype != torch.float32:
+        raise TypeError(f"feats must be float32, got {feats.dtype}")
+    feats = feats.detach().contiguous()
+    B, C, N = feats.shape
+    k = int(k)
+    if not 1 <= k <= min(N, MAX_K):
+        raise ValueError(f"k = {k} must satisfy 1 <= k <= min(N, {MAX_K}) = {min(N, MAX_K)} (KDTree.query raises for k > N too)")
+    L, dev, st = _lib.lib(), feats.device, _lib.stream()
+    lab = _labels_2d(labels, B, N) if labels is not None else None
+    if centroids is None:
+        counts = torch.empty(B, num_labels, dtype=torch.int32, device=dev)
+        cent_all = torch.empty(B, num_labels, 3, dtype=torch.float32, device=dev)
+        _lib.check(L.tgn_clear_index_error(st), "tgn_clear_index_error")
+        _lib.check(L.tgn_label_centroids(B, N, C, _lib.ptr(feats), _lib.ptr(lab), num_labels, _lib.ptr(counts), _lib.ptr(cent_all), st),
+                   "tgn_label_centroids")
+        present = counts.cpu().numpy() > 0                                        # the one synchronisation
+        if L.tgn_take_index_error(st) & _CROP_ERROR:
+            raise ValueError(f"tooth_crops: a label outside [-1, {num_labels}) (gingiva -1, teeth 0..{num_labels - 1})")
+        per_scan = present.sum(1).tolist()
+        rows = torch.from_numpy(np.flatnonzero(present.reshape(-1))).to(dev, non_blocking=True)
+        cent = cent_all.view(-1, 3).index_select(0, rows).contiguous()
+    else:
+        if len(centroids) != B:
+            raise ValueError(f"centroids must be a list of {B} per-scan (T_b, 3) arrays")
+        parts = [torch.as_tensor(np.asarray(c, np.float32) if not isinstance(c, torch.Tensor) else c).to(dev, torch.float32).reshape(-1, 3)
+                 for c in centroids]
+        per_scan = [int(p.shape[0]) for p in parts]
+        cent = torch.cat(parts).contiguous()
+    T = int(sum(per_scan))
+    if T == 0:
+        raise ValueError("tooth_crops: no tooth in the batch (every point is gingiva, label -1)")
+    scan = torch.from_numpy(np.repeat(np.arange(B, dtype=np.int32), per_scan)).to(dev, non_blocking=True)
+    idx = torch.empty(T, k, dtype=torch.int64, device=dev)
+    cropped = torch.empty(T, C, k, dtype=torch.float32, device=dev)
+    crop_lab = torch.empty(T, 1, k, dtype=torch.int64, device=dev) if lab is not None else None
+    _lib.check(L.tgn_crop_knn(B, N, C, _lib.ptr(feats), T, _lib.ptr(scan), _lib.ptr(cent), k, _lib.ptr(idx), st), "tgn_crop_knn")
+    _lib.check(L.tgn_crop_gather_center(B, N, C, T, k, _lib.ptr(feats), _lib.ptr(scan), _lib.ptr(idx), _lib.ptr(lab), _lib.ptr(cropped),
+                                        _lib.ptr(crop_lab), st), "tgn_crop_gather_center")
+    return ToothCrops(cropped, list(idx.split(per_scan)), crop_lab, list(cent.split(per_scan)))

@@ -112,7 +112,8 @@ TGN_API const char *tgn_last_error(void) { return tgn::g_error; }
 TGN_API void tgn_set_default_stream(tgn_stream_t stream) { tgn::g_default_stream = (hipStream_t)stream; }
 
 // Returns the OR of the error bits latched by launches on `stream` of the current device since the last call (and clears them):
-// bit 0 = a gather / grouping saw an index outside [-N, N).  Synchronises `stream`.
+// bit 0 = a gather / grouping saw an index outside [-N, N); bit 1 = a crop kernel (crop.hip) saw a label, scan or index out of
+// range.  Synchronises `stream`.
 TGN_API int tgn_take_index_error(tgn_stream_t stream) {
     int *w = tgn::index_error_word((hipStream_t)stream);
     if (!w) return 0;

@@ -15,6 +15,9 @@ of the fused eval paths.  Parameter names and shapes equal the reference classes
                        the reference ships (default.yaml: five stages, `multi` heads over the decoder stages, latent
                        features concatenated); BASELINE.json configs 3 / 4's network.  Inference outputs only: the
                        contrastive-boundary criterion of training (heads.py:62-253) is the reference's own Python.
+  GroupingNetworkModule  models/modules/grouping_network_module.py:7-101, tgnet_fps's network (train_configs/tgnet_fps.py): a
+                       PointTransformerSeg over the scan, on-device tooth crops (crops.tooth_crops), a second PointTransformerSeg over
+                       all crops as one batch.  Labelled-centroid path only; the cbl terms stay the reference's Python.
 """
 import torch
 import torch.nn as nn
@@ -22,7 +25,7 @@ import torch.nn.functional as F
 
 import functools
 
-from . import _derived, _lib, point_transformer as PT, pointops
+from . import _derived, _lib, crops as _crops, point_transformer as PT, pointops
 from .pointnet2_utils import PointNetFeaturePropagation, PointNetSetAbstraction, PointNetSetAbstractionMsg, linear_relu
 
 
@@ -251,3 +254,48 @@ class PointTransformerSeg(nn.Module):
         cls = self.cls_head(up).view(B, N, self.k).permute(0, 2, 1)
         offset = self.offset_head(up).view(B, N, 3).permute(0, 2, 1) if B == 1 else None
         return [cls, offset, None, up[0][1]]
+
+
+class GroupingNetworkModule(nn.Module):
+    """models/modules/grouping_network_module.py:7-101 (tgnet_fps): `first_ins_cent_model` (PointTransformerSeg, 10 classes) over the
+    whole scan; around every tooth the `crop_sample_size` nearest points, centred (crops.tooth_crops: three HIP kernels where the
+    reference runs numpy, an sklearn KDTree and python gathers on the host); `second_ins_cent_model` (PointTransformerSeg, 2 classes)
+    over all crops as one batch.  Same constructor argument and state_dict as the reference's class, so its checkpoints load with
+    strict=True.
+
+    Centroids: the labels' (inputs[1], the reference's path whenever len(inputs) >= 2), or `centroids` given by the caller; the
+    unlabelled path's DBSCAN clustering (ops_utils.get_clustering_labels) is not mirrored.  The contrastive-boundary terms
+    cbl_loss_1 / cbl_loss_2 of training (the reference's criterion, heads.py:62-253) are left out, as for PointTransformerSeg, so
+    `test` changes nothing here: both stages always run without the criterion.  One host synchronisation per forward (the tooth
+    count, see crops.tooth_crops)."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.config = config
+        mp = config["model_parameter"]
+        if mp.get("block_num", 5) != 5:
+            raise ValueError(f"block_num = {mp['block_num']}: only the five-stage network (train_configs/tgnet_fps.py) is mirrored")
+        arch = dict(planes=tuple(mp["planes"]), blocks=tuple(mp["blocks"]), stride=tuple(mp["stride"]), nsample=tuple(mp["nsample"]))
+        class_num = 9
+        self.first_ins_cent_model = PointTransformerSeg(c=mp["input_feat"], k=class_num + 1, **arch)
+        self.second_ins_cent_model = PointTransformerSeg(c=mp["input_feat"], k=2, **arch)
+        self.crop_sample_size = int(mp["crop_sample_size"])
+
+    def forward(self, inputs, test=False, centroids=None):
+        """inputs: [features (B, C, N)] or [features, labels (B, 1, N)] -> the reference's output dict (sem_1, offset_1, mask_1,
+        first_features, sem_2, offset_2, mask_2, cropped_feature_ls, nn_crop_indexes and, with labels, cluster_gt_seg_label);
+        offset_2 is None unless there is exactly one crop (the reference's head runs for B == 1 only)."""
+        feats = inputs[0]
+        labels = inputs[1] if len(inputs) >= 2 else None
+        if labels is None and centroids is None:
+            raise ValueError("GroupingNetworkModule: without labels the reference clusters the moved points with DBSCAN "
+                             "(ops_utils.get_clustering_labels), which is not mirrored; pass the centroids")
+        sem_1, offset_1, mask_1, first_features = self.first_ins_cent_model([feats])
+        out = {"sem_1": sem_1, "offset_1": offset_1, "mask_1": mask_1, "first_features": first_features}
+        cr = _crops.tooth_crops(feats, labels, centroids, self.crop_sample_size)
+        if labels is not None:
+            out["cluster_gt_seg_label"] = cr.cluster_gt_seg_label
+        sem_2, offset_2, mask_2, _ = self.second_ins_cent_model([cr.cropped])
+        out.update({"sem_2": sem_2, "offset_2": offset_2, "mask_2": mask_2, "cropped_feature_ls": cr.cropped,
+                    "nn_crop_indexes": cr.nn_crop_indexes})
+        return out

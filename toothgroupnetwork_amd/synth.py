@@ -118,3 +118,25 @@ def fdi_labels(n, jaw, seed=0):
     base = (10, 20) if jaw == "upper" else (30, 40)
     teeth = np.array([0] + [b + t for b in base for t in range(1, 9)])
     return teeth[rng.integers(0, teeth.size, n)].tolist()
+
+
+def labelled_arch(n, teeth, seed=0, dup=0):
+    """An arch scan with spatially coherent tooth labels, as the reference's generator yields them (generator.py:46-47: -1 =
+    gingiva, teeth 0..15): (n, 6) fp32 rows (xyz + normals) and (n,) int64 labels.  The teeth are `teeth` equal angular sectors
+    along the arch, labelled 0..teeth-1; the low band of the crown profile is gingiva.  `dup` of the n rows are copies of other
+    rows (with their labels), so that exact distance ties occur -- also across the k-th nearest point of a crop."""
+    if not 1 <= teeth <= 16:
+        raise ValueError("teeth must be in 1..16")
+    base = arch_cloud(n - dup, seed=seed)
+    rng = np.random.default_rng(seed + 7)
+    ang = np.arctan2(base[:, 1] + 0.45, base[:, 0])
+    ang = np.where(ang < -0.5 * np.pi, ang + 2.0 * np.pi, ang)      # the arch's angle about its centre, 0 .. pi
+    lo, hi = ang.min(), ang.max()
+    lab = np.clip(((ang - lo) / (hi - lo + 1e-9) * teeth).astype(np.int64), 0, teeth - 1)
+    lab[base[:, 2] < np.quantile(base[:, 2], 0.35)] = -1
+    if dup:
+        pick = rng.integers(0, n - dup, size=dup)
+        base, lab = np.concatenate([base, base[pick]]), np.concatenate([lab, lab[pick]])
+        order = rng.permutation(n)
+        base, lab = base[order], lab[order]
+    return np.ascontiguousarray(base, dtype=np.float32), lab
