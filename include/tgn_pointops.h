@@ -461,6 +461,32 @@ int tgn_crop_knn(int b, int n, int c_stride, const float *feats, int t_total, co
 int tgn_crop_gather_center(int b, int n, int c, int t_total, int k, const float *feats, const int *crop_scan, const long long *idx,
                            const long long *labels, float *out, long long *out_labels, tgn_stream_t stream);
 
+/*
+ * DGCNN's neighbourhood work (models/modules/dgcnn.py).  x (B, D, N) float32 channel-first, as the network holds it.
+ *   tgn_feature_knn: knn(x, k) (dgcnn.py:4-10) without the N x N matrix.  idx (B, N, k) int64 point indices local to their scan;
+ *     row i holds the k smallest distances to point i, i itself included, in ascending (distance, index) order.  The distance is
+ *     the direct form in float32 with every operation rounded: acc = 0; for c = 0..D-1: t = x[c][i] - x[c][j]; acc = acc + t*t.
+ *     dist2 (B, N, k) float32 receives those distances (NULL: not written).  The result depends on the input alone (splitting
+ *     and merging are exact).  Equal distances come in ascending index order, so a duplicate vertex of lower index precedes i
+ *     (torch.topk leaves the order of equal values unspecified).  1 <= D <= 64, 1 <= k <= min(N, 32).  workspace: at least
+ *     tgn_feature_knn_workspace_bytes(B, N, k) bytes of device memory (0: none needed), O(B N k).
+ *   tgn_edgeconv2_max: out[b, coff + c, i] = max_{r < K} lrelu((W2 lrelu(P[b, idx[b,i,r]] + Q[b, i]) + b2)[c]), c = 0..63 -- an
+ *     EdgeConv level of two 1x1 convolutions in eval mode with BatchNorm folded: P = Wa' x, Q = (Wb' - Wa') x + b1' per point
+ *     (W' = the first layer's weight scaled by its BatchNorm, [Wa | Wb] its halves for [x_j - x_i, x_i]).  P, Q (B, N, 64) float32
+ *     point-major, idx (B, N, K) int64, W2 (64, 64) float32 (out, in) row-major, b2 (64), lrelu = LeakyReLU(0.2).  The second layer
+ *     runs on fp32 MFMA (exact fp32 products, fp32 accumulation).
+ *   tgn_edgeconv1_max: out[b, coff + c, i] = max_{r < K} lrelu(P[b, idx[b,i,r], c] + Q[b, i, c]), the one-layer level.
+ *   Both: out (B, *, N) float32 channel-first with batch stride ostride >= (coff + 64) * N floats; 1 <= K <= 32.  An index outside
+ *   [0, N) reads point 0 and latches bit 1 of the stream's error word (tgn_take_index_error).
+ */
+size_t tgn_feature_knn_workspace_bytes(int B, int N, int k);
+int tgn_feature_knn(int B, int N, int D, int k, const float *x, long long *idx, float *dist2, void *workspace, size_t ws_bytes,
+                    tgn_stream_t stream);
+int tgn_edgeconv2_max(int B, int N, int K, const float *P, const float *Q, const long long *idx, const float *W2, const float *b2,
+                      float *out, long long ostride, int coff, tgn_stream_t stream);
+int tgn_edgeconv1_max(int B, int N, int K, const float *P, const float *Q, const long long *idx, float *out, long long ostride, int coff,
+                      tgn_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * 4. Mesh input of the preprocess path (HOST pointers, CPU code): gen_utils.read_txt_obj_ls (gen_utils.py:207-233).
  * ---------------------------------------------------------------------------------------- */

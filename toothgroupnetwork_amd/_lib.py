@@ -115,6 +115,10 @@ SIGNATURES = {
     "tgn_label_centroids": (c_int, [c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P]),
     "tgn_crop_knn": (c_int, [c_int, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P]),
     "tgn_crop_gather_center": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "tgn_feature_knn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "tgn_feature_knn": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "tgn_edgeconv2_max": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, ctypes.c_longlong, c_int, _P]),
+    "tgn_edgeconv1_max": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, ctypes.c_longlong, c_int, _P]),
     # section 4 (host pointers)
     "tgn_obj_count": (c_int, [ctypes.c_char_p, _P, _P]),
     "tgn_obj_read": (c_int, [ctypes.c_char_p, _P, _P, ctypes.c_longlong, ctypes.c_longlong, _P, _P]),

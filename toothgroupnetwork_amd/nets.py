@@ -15,6 +15,8 @@ of the fused eval paths.  Parameter names and shapes equal the reference classes
                        the reference ships (default.yaml: five stages, `multi` heads over the decoder stages, latent
                        features concatenated); BASELINE.json configs 3 / 4's network.  Inference outputs only: the
                        contrastive-boundary criterion of training (heads.py:62-253) is the reference's own Python.
+  DGCnnModule          models/modules/dgcnn.py:43-143 (the "dgcnn" model): three EdgeConv levels over feature-space kNN graphs,
+                       fused in eval mode (dgcnn.py of this package, re-exported here).
   GroupingNetworkModule  models/modules/grouping_network_module.py:7-101, tgnet_fps's network (train_configs/tgnet_fps.py): a
                        PointTransformerSeg over the scan, on-device tooth crops (crops.tooth_crops), a second PointTransformerSeg over
                        all crops as one batch.  Labelled-centroid path only; the cbl terms stay the reference's Python.
@@ -26,6 +28,7 @@ import torch.nn.functional as F
 import functools
 
 from . import _derived, _lib, crops as _crops, point_transformer as PT, pointops
+from .dgcnn import DGCnnModule  # noqa: F401
 from .pointnet2_utils import PointNetFeaturePropagation, PointNetSetAbstraction, PointNetSetAbstractionMsg, linear_relu
 
 
