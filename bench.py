@@ -14,11 +14,16 @@ timing, one RCCL all_gather of the per-rank timing vector at the end.
         --master-port P bench.py --gpus N --steps K --warmup W
 
 `python bench.py --gpus N` without torchrun starts its N ranks itself (toothgroupnetwork_amd.launch); a rank
-count other than --gpus is an error.  Rank 0 prints ONE JSON line.  `roofline` describes the dominant kernel
-(FPS level 1), timed with HIP events on the launch stream inside the timed region, against the measured
-latency floor of one FPS iteration (tools/fps_floor.hip); `cpu_baseline` is the reference's CPU path restated
+count other than --gpus is an error.  Rank 0 prints ONE JSON line; `ranks` / `backend` / `rccl_version` say who
+took part.
+
+A plain run does what the headline needs and nothing more: set-up, warm-up, the timed steps, --dump-outputs, the
+line.  `--full` adds everything else, after the timed region: `roofline` describes the dominant kernel (FPS
+level 1), timed with HIP events on the launch stream inside the timed region, against the measured latency floor
+of one FPS iteration (tools/fps_floor.hip), with a per-kernel table from a few more steps; `with_fps_prefix_identity`
+re-times the steps with the FPS-of-an-FPS-result shortcut; `cpu_baseline` is the reference's CPU path restated
 torch call for torch call (oracle/torch_cpu.py) on a bounded sample of the same workload, with the oracle's
-C/OpenMP port beside it; `ranks` / `backend` / `rccl_version` say who took part.
+C/OpenMP port beside it; `secondary` holds the non-headline configurations (tools/secondary_bench.py).
 """
 import argparse
 import json
@@ -257,7 +262,17 @@ def single_gpu_legs_only(args, world):
         args.secondary, args.cpu_meshes, args.no_alt = 0, 0, True
 
 
-def main(argv=None):
+def headline_legs_only(args):
+    """A plain run (no --full) measures the headline and nothing else: no CPU baseline, no secondary configurations, no
+    prefix-identity re-run, and no per-kernel / roofline steps after the timed region.  The HIP events around FPS level 1
+    inside the timed region stay (--no-kernel-timing drops them): they are part of the timed steps every run compares."""
+    if not args.full:
+        args.secondary, args.cpu_meshes, args.no_alt, args.roofline = 0, 0, True, False
+    else:
+        args.roofline = not args.no_kernel_timing
+
+
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -265,7 +280,9 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=256, help="scans per step per GPU (one FPS workgroup per scan)")
     ap.add_argument("--unique", type=int, default=0, help="distinct synthetic scans per batch (0 = all of them distinct, the default; "
                     "16 = what rounds 1-5 tiled to 256)")
-    ap.add_argument("--cpu-meshes", type=int, default=-1, help="CPU-baseline sample size (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure what it does not need: the per-kernel table and "
+                    "roofline, the prefix-identity re-run, the CPU baseline and the secondary configurations (single-GPU legs at N = 1 only)")
+    ap.add_argument("--cpu-meshes", type=int, default=-1, help="CPU-baseline sample size (0 = skip; --full only)")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--timing-stride", type=int, default=4, help="per-kernel HIP events on every n-th timed step (each event is a barrier "
                     "packet in its queue: on every step they cost the pipelined schedule ~5 %%)")
@@ -280,8 +297,8 @@ def main(argv=None):
                     "size S*K is written -- a second, non-headline line bound by the fp32 matrix cores")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default: nccl = RCCL; gloo lets several ranks share "
                     "one GPU, e.g. to exercise the N > 1 branch on a one-GPU box)")
-    ap.add_argument("--no-alt", action="store_true", help="skip the extra with_fps_prefix_identity measurement (profiling runs)")
-    ap.add_argument("--secondary", type=int, default=1, help="1 (default, N = 1 only): after the headline, also measure the non-headline "
+    ap.add_argument("--no-alt", action="store_true", help="skip the extra with_fps_prefix_identity measurement of --full (profiling runs)")
+    ap.add_argument("--secondary", type=int, default=1, help="1 (default; --full, N = 1 only): after the headline, also measure the non-headline "
                     "configurations of BASELINE.json (Shape B, the fused levels, kNN, large-cloud FPS, Point-Transformer forward, training "
                     "step), in a child process, and attach them as `secondary` (tools/secondary_bench.py; ~1-2 minutes); 0: skip")
     ap.add_argument("--group-max-blocks", type=int, default=None, help="bound the grouping kernels' grid (default: 256 in the phased schedule -- their "
@@ -294,6 +311,11 @@ def main(argv=None):
     ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step "
                     "computed as DIR/<name>.npy (float32, indices as float64; a fixed, seeded sample of the rows of the large "
                     "arrays, under 64 MB in all) and DIR/manifest.json; rank 0 only")
+    return ap
+
+
+def main(argv=None):
+    ap = parser()
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -314,6 +336,7 @@ def main(argv=None):
     B = args.batch
     shape = hotpath.SHAPE_A if args.shape == "A" else hotpath.SHAPE_B
     single_gpu_legs_only(args, world)
+    headline_legs_only(args)
     xyz, feats, scans = make_inputs(B, device, seed=100 + 1000 * rank, shape=shape, unique=args.unique)
     gopts = dict(fused=bool(args.fused), group_max_blocks=args.group_max_blocks, grid_stream=args.grid_stream, fps_low_valu=args.fps23 == "bucket")
     hp = hotpath.HotPath(B, device, shape=shape, pipeline=bool(args.pipeline), fps_prefix=bool(args.fps_prefix), **gopts)
@@ -389,6 +412,9 @@ def main(argv=None):
     }
     if rank == 0 and not args.no_kernel_timing:
         live = {k: float(np.mean(v)) for k, v in hp.kernel_times_ms().items() if v}      # FPS level 1, inside the timed region
+        out["kernel_timing"] = {"fps_l1_in_timed_region_ms": live.get("fps_l1"),
+                                "note": "FPS level 1 (the dominant kernel) is timed with HIP events on its stream inside the timed region"}
+    if rank == 0 and args.roofline:
         hp.enable_kernel_timing(8, stride=2)                                            # every kernel class, after it
         for _ in range(8):
             hp.run(xyz, feats, inputs_on_current_stream=False)
@@ -469,7 +495,7 @@ def main(argv=None):
                                  "unit": "GB/s", "frac": galgo / (avg[gk] * 1e-3) / 1e9 / HBM_PEAK_GBS,
                                  "traffic": (pmc[gk]["fetch"] + pmc[gk]["write"]) if gk in pmc and pmc_ok else None,
                                  "algorithmic_bytes_per_launch": galgo, "avg_launch_ms": avg[gk]}
-    if args.fused and rank == 0 and not args.no_kernel_timing:
+    if args.fused and rank == 0 and args.roofline:
         # the fused levels are bound by the fp32 matrix cores: flops of the first layers (per POINT where the transform commutes
         # with the gather, per gathered row in the direct form) and of the second layers (per gathered row), against 157.3 TFLOP/s
         fl = _secondary().fused_flops(shape)

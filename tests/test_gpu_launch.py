@@ -34,6 +34,26 @@ def test_bench_gpus_2_spawns_two_ranks_itself(dev):
     assert res["config"]["meshes_per_step_per_gpu"] == 16
 
 
+def test_bench_plain_run_and_full(dev):
+    """a plain run prints the headline and the FPS level-1 time of its timed steps and measures nothing else; --full adds the
+    per-kernel table and roofline, the prefix-identity re-run and the CPU baseline (the secondary configurations, minutes of
+    work, are left out here)"""
+    base = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "16"]
+    out = subprocess.run(base, capture_output=True, text=True, timeout=600, env=ENV)
+    assert out.returncode == 0, out.stderr[-3000:]
+    plain = _json_line(out.stdout)
+    assert plain["n_gpus"] == 1 and plain["steps"] == 2 and plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert plain["kernel_timing"]["fps_l1_in_timed_region_ms"] > 0
+    for k in ("roofline", "roofline_group", "kernel_ms_per_step", "with_fps_prefix_identity", "cpu_baseline", "secondary"):
+        assert k not in plain, k
+    out = subprocess.run(base + ["--full", "--cpu-meshes", "2", "--secondary", "0"], capture_output=True, text=True, timeout=600, env=ENV)
+    assert out.returncode == 0, out.stderr[-3000:]
+    full = _json_line(out.stdout)
+    assert full["roofline"]["kernel"] in full["kernel_ms_per_step"] and full["roofline"]["achieved"] > 0 and "group_l1" in full["kernel_ms_per_step"]
+    assert full["kernel_timing"]["fps_l1_after_it_ms"] > 0 and full["with_fps_prefix_identity"]["value"] > 0
+    assert full["cpu_baseline"]["value"] > 0 and full["cpu_baseline"]["c_openmp_port"]["value"] > 0 and "secondary" not in full
+
+
 def test_bench_under_torchrun_the_drivers_form(dev):
     """the command line the driver uses for N > 1 (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
     127.0.0.1 --master-port P bench.py --gpus N ...), with gloo so that both ranks may share this box's one GPU"""

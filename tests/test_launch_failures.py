@@ -147,3 +147,20 @@ def test_bench_single_gpu_legs_are_impossible_at_n_gt_1():
     a = argparse.Namespace(secondary=1, cpu_meshes=-1, no_alt=False)
     bench.single_gpu_legs_only(a, world=1)
     assert (a.secondary, a.cpu_meshes, a.no_alt) == (1, -1, False)
+
+
+def test_bench_plain_run_measures_the_headline_alone():
+    """without --full a run does only what the headline needs: no CPU baseline, secondary configurations, prefix-identity re-run
+    or per-kernel steps after the timed region; --full keeps every leg as its own option sets it"""
+    sys.path.insert(0, REPO)
+    import bench
+    a = bench.parser().parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert a.full is False
+    bench.headline_legs_only(a)
+    assert (a.secondary, a.cpu_meshes, a.no_alt, a.roofline, a.no_kernel_timing) == (0, 0, True, False, False)
+    a = bench.parser().parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    bench.headline_legs_only(a)
+    assert (a.secondary, a.cpu_meshes, a.no_alt, a.roofline) == (1, -1, False, True)
+    a = bench.parser().parse_args(["--full", "--no-kernel-timing", "--secondary", "0", "--no-alt"])
+    bench.headline_legs_only(a)
+    assert (a.secondary, a.cpu_meshes, a.no_alt, a.roofline) == (0, -1, True, False)

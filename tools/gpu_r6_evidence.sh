@@ -5,7 +5,7 @@ set -u
 export TMPDIR=/tmp
 O=gpurun_out/evidence6
 mkdir -p $O
-timeout 1500 python bench.py --steps 20 --warmup 5 > $O/bench_20.json 2> $O/bench_20.err; echo "bench rc=$?"
+timeout 1500 python bench.py --steps 20 --warmup 5 --full > $O/bench_20.json 2> $O/bench_20.err; echo "bench rc=$?"
 (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/prof -o r6 -- python $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --cpu-meshes 0 --no-alt --secondary 0 > $GRAFT_REPO_ROOT/$O/rocprof.log 2>&1)
 f=$(find $O/prof -name "*kernel_stats.csv" | head -1); cp $f $O/kernel_stats.csv; cut -c1-140 $O/kernel_stats.csv | head -14
 tail -1 $O/rocprof.log | cut -c1-400 > $O/bench_under_rocprof.json

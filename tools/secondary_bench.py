@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The non-headline configurations of BASELINE.json, measured in the SAME process as bench.py's headline (after it) so that
-the driver's bench run witnesses them: bench.py attaches `secondary` = measure_all(...) to its JSON line at N = 1.
+"""The non-headline configurations of BASELINE.json, measured after bench.py's headline in a child process of its own so that
+a full bench run witnesses them: `bench.py --full` attaches `secondary` = measure_all(...) to its JSON line at N = 1.
 
 Every entry: {"value", "unit", "ms", "config", "roofline": {"bound", "achieved", "peak", "unit", "frac"}} -- the roofline of
 the kernel family that bounds the entry, priced like the headline's (algorithmic bytes or flops per launch / HIP-event time).
