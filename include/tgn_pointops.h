@@ -462,6 +462,41 @@ int tgn_crop_gather_center(int b, int n, int c, int t_total, int k, const float 
                            const long long *labels, float *out, long long *out_labels, tgn_stream_t stream);
 
 /*
+ * The clustering of tgnet_fps's unlabelled path (ops_utils.get_clustering_labels, called from grouping_network_module.py:57-69): sklearn's
+ * DBSCAN and flat-kernel MeanShift on the moved foreground points, the moments of its PCA split test, the noise points' vote.  The
+ * reference runs it on the host.  q is a neighbour of p within radius r when ((0 + dx*dx) + dy*dy) + dz*dz <= r*r in float64, unfused
+ * (dx = double(p.x) - double(q.x): KDTree's euclidean rdist, as tgn_crop_knn); the point itself and exact duplicates count.
+ *   tgn_dbscan: DBSCAN(eps, min_samples).fit(X) on each of b clouds of xyz (n, 3) float32 row-major, cloud i = points
+ *     [offset[i-1], offset[i]) (pointops-style cumulative int32 offset (b), device memory, offset[b-1] = n; not checked here).  core (n)
+ *     uint8: 1 when the neighbour count (self included) is >= min_samples.  labels (n) int64, numbered per cloud: the connected
+ *     components of core points under the neighbour relation are clusters 0, 1, ... in ascending order of their smallest core index
+ *     (sklearn's dbscan_inner); a non-core point with a core neighbour takes the smallest of its core neighbours' cluster numbers
+ *     (the first depth-first search of dbscan_inner that reaches it), every other point is noise (-1).  nclusters (b) int32.  eps > 0,
+ *     min_samples >= 1.  workspace: at least tgn_dbscan_workspace_bytes(b, n) bytes of device memory, O(n).
+ *   tgn_mean_shift: MeanShift(bandwidth)'s climb (_mean_shift_single_seed, max_iter iterations at most; sklearn's default is 300) from
+ *     every point of xyz (n, 3) float64: the new mean is the sum of the points within the bandwidth, sequential in ascending point order,
+ *     divided by their count; a seed stops when the shift's norm is <= 1e-3 * bandwidth.  means (n, 3) float64 the final mean, counts (n)
+ *     int32 the number of points it is the mean of (0: no point within the bandwidth, the seed stayed where it was).  sklearn sums in
+ *     its KDTree's order instead, so the means agree with sklearn's to rounding, not bit for bit.
+ *   tgn_nearest_center: labels (n) int64 = the index of the centre (m, 3) float64 nearest to each point of xyz (n, 3) float64, by rdist,
+ *     ties to the lower index.  m >= 1.
+ *   tgn_cluster_moments: for every label l in [0, nlab): counts (nlab) int32 of the points i with labels[i] == l and mask[i] != 0 (mask
+ *     NULL: all), their float64 mean (nlab, 3) and covariance (nlab, 3, 3) with ddof = 1 (NaN entries for fewer than 2 points).
+ *     xyz (n, 3) float32.
+ *   tgn_cluster_vote: out[i] = the most frequent of cand_labels[nn_idx[i][0..k-1]], equal counts to the smallest label (np.unique +
+ *     argmax).  1 <= k <= 32.  An index outside [0, n_cand) reads candidate 0 and latches bit 1 of the stream's error word.
+ * Deterministic: no atomic whose order reaches an output.  n = 0 (m = 0 for the vote) launches nothing where it is allowed.
+ */
+size_t tgn_dbscan_workspace_bytes(int b, int n);
+int tgn_dbscan(int b, int n, const float *xyz, const int *offset, double eps, int min_samples, long long *labels, unsigned char *core,
+               int *nclusters, void *workspace, size_t workspace_bytes, tgn_stream_t stream);
+int tgn_mean_shift(int n, const double *xyz, double bandwidth, int max_iter, double *means, int *counts, tgn_stream_t stream);
+int tgn_nearest_center(int n, const double *xyz, int m, const double *centers, long long *labels, tgn_stream_t stream);
+int tgn_cluster_moments(int n, const float *xyz, const long long *labels, const unsigned char *mask, int nlab, int *counts, double *mean,
+                        double *cov, tgn_stream_t stream);
+int tgn_cluster_vote(int m, int k, const long long *nn_idx, int n_cand, const long long *cand_labels, long long *out, tgn_stream_t stream);
+
+/*
  * DGCNN's neighbourhood work (models/modules/dgcnn.py).  x (B, D, N) float32 channel-first, as the network holds it.
  *   tgn_feature_knn: knn(x, k) (dgcnn.py:4-10) without the N x N matrix.  idx (B, N, k) int64 point indices local to their scan;
  *     row i holds the k smallest distances to point i, i itself included, in ascending (distance, index) order.  The distance is

@@ -115,6 +115,12 @@ SIGNATURES = {
     "tgn_label_centroids": (c_int, [c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P]),
     "tgn_crop_knn": (c_int, [c_int, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P]),
     "tgn_crop_gather_center": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "tgn_dbscan_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "tgn_dbscan": (c_int, [c_int, c_int, _P, _P, ctypes.c_double, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "tgn_mean_shift": (c_int, [c_int, _P, ctypes.c_double, c_int, _P, _P, _P]),
+    "tgn_nearest_center": (c_int, [c_int, _P, c_int, _P, _P, _P]),
+    "tgn_cluster_moments": (c_int, [c_int, _P, _P, _P, c_int, _P, _P, _P, _P]),
+    "tgn_cluster_vote": (c_int, [c_int, c_int, _P, c_int, _P, _P, _P]),
     "tgn_feature_knn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "tgn_feature_knn": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "tgn_edgeconv2_max": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, ctypes.c_longlong, c_int, _P]),

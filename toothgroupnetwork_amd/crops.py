@@ -8,8 +8,9 @@ loop (centering_object); here it is three HIP kernels (csrc/crop.hip, include/tg
               (KDTree leaves that order unspecified; the index set and the distance sequence are the same)
   centring    channels 0..2 minus their mean over the crop: a float64 sum rounded once to float32, subtracted in float32
 
-Centroids from clustering (the unlabelled path: ops_utils.get_clustering_labels, sklearn DBSCAN) are not computed here; a caller that
-has them passes them as `centroids`.
+Centroids from clustering (the unlabelled path: ops_utils.get_clustering_labels) come from cluster.py -- nets.GroupingNetworkModule
+computes them there and passes them as `centroids`, as any caller that has centroids may; tooth_crops itself needs labels or
+centroids.
 """
 from collections import namedtuple
 
@@ -49,8 +50,9 @@ def tooth_crops(feats, labels=None, centroids=None, k=3072, num_labels=NUM_LABEL
     word, which by then waits on nothing.  Raises ValueError for labels outside [-1, num_labels) and when no tooth is present."""
     _lib.require_cuda(feats, labels if isinstance(labels, torch.Tensor) else None)
     if labels is None and centroids is None:
-        raise ValueError("tooth_crops needs labels or centroids: centroids from clustering (ops_utils.get_clustering_labels, sklearn "
-                         "DBSCAN on the moved foreground points) are the caller's to compute -- out of scope here (SURVEY.md section 2)")
+        raise ValueError("tooth_crops needs labels or centroids: centroids from clustering (DBSCAN on the moved foreground points, "
+                         "cluster.get_clustering_labels and cluster.cluster_centroids) are the caller's to compute, as "
+                         "nets.GroupingNetworkModule does")
     if feats.dim() != 3 or feats.shape[1] < 3:
         raise ValueError(f"feats must be (B, C >= 3, N), got {tuple(feats.shape)}")
     if feats.dtype != torch.float32:

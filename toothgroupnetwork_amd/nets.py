@@ -19,7 +19,8 @@ of the fused eval paths.  Parameter names and shapes equal the reference classes
                        fused in eval mode (dgcnn.py of this package, re-exported here).
   GroupingNetworkModule  models/modules/grouping_network_module.py:7-101, tgnet_fps's network (train_configs/tgnet_fps.py): a
                        PointTransformerSeg over the scan, on-device tooth crops (crops.tooth_crops), a second PointTransformerSeg over
-                       all crops as one batch.  Labelled-centroid path only; the cbl terms stay the reference's Python.
+                       all crops as one batch.  Without labels the centroids come from on-device clustering (cluster.py); the cbl
+                       terms stay the reference's Python.
 """
 import torch
 import torch.nn as nn
@@ -27,7 +28,7 @@ import torch.nn.functional as F
 
 import functools
 
-from . import _derived, _lib, crops as _crops, point_transformer as PT, pointops
+from . import _derived, _lib, cluster as _cluster, crops as _crops, point_transformer as PT, pointops
 from .dgcnn import DGCnnModule  # noqa: F401
 from .pointnet2_utils import PointNetFeaturePropagation, PointNetSetAbstraction, PointNetSetAbstractionMsg, linear_relu
 
@@ -233,9 +234,10 @@ class PointTransformerSeg(nn.Module):
         self.offset_head = MultiHead(planes, 3, planes[0])
 
     @_one_index_check
-    def forward(self, inputs):
+    def forward(self, inputs, all_offsets=False):
         """inputs: [features (B, C, N)] -> [cls (B, k, N), offset (1, 3, N) or None, None, x1 (B*N, planes[0])]
-        (cbl_point_transformer_module.py:196-216 without the training criterion)."""
+        (cbl_point_transformer_module.py:196-216 without the training criterion).  The offset head runs for B == 1 only, as in the
+        reference; all_offsets=True runs it for any B (GroupingNetworkModule's unlabelled path, one scan at a time)."""
         feats = inputs[0]
         B, C, N = feats.shape
         pxo = feats.permute(0, 2, 1)
@@ -255,7 +257,7 @@ class PointTransformerSeg(nn.Module):
             xi = dec[1:]([pi, head, oi])[1]
             above = up[i] = [pi, xi, oi]
         cls = self.cls_head(up).view(B, N, self.k).permute(0, 2, 1)
-        offset = self.offset_head(up).view(B, N, 3).permute(0, 2, 1) if B == 1 else None
+        offset = self.offset_head(up).view(B, N, 3).permute(0, 2, 1) if B == 1 or all_offsets else None
         return [cls, offset, None, up[0][1]]
 
 
@@ -266,11 +268,16 @@ class GroupingNetworkModule(nn.Module):
     over all crops as one batch.  Same constructor argument and state_dict as the reference's class, so its checkpoints load with
     strict=True.
 
-    Centroids: the labels' (inputs[1], the reference's path whenever len(inputs) >= 2), or `centroids` given by the caller; the
-    unlabelled path's DBSCAN clustering (ops_utils.get_clustering_labels) is not mirrored.  The contrastive-boundary terms
-    cbl_loss_1 / cbl_loss_2 of training (the reference's criterion, heads.py:62-253) are left out, as for PointTransformerSeg, so
-    `test` changes nothing here: both stages always run without the criterion.  One host synchronisation per forward (the tooth
-    count, see crops.tooth_crops)."""
+    Centroids: the labels' (inputs[1], the reference's path whenever len(inputs) >= 2), `centroids` given by the caller, or, with
+    neither, the unlabelled path of grouping_network_module.py:57-69: per scan, the first stage's class argmax, the moved points xyz +
+    offset_1, cluster.get_clustering_labels on them (DBSCAN, the PCA split test, MeanShift, the noise vote -- HIP kernels where the
+    reference runs sklearn) and the float32 mean of the moved foreground points of every cluster, ascending.  The reference's
+    unlabelled path works for B == 1 only (it indexes inputs[b_idx] and its offset head runs for B == 1); here every scan of a batch
+    is clustered on its own, and offset_1 is then returned for every B.  The contrastive-boundary terms cbl_loss_1 / cbl_loss_2 of
+    training (the reference's criterion, heads.py:62-253) are left out, as for PointTransformerSeg, so `test` changes nothing here:
+    both stages always run without the criterion.  One host synchronisation per forward with labels (the tooth count, see
+    crops.tooth_crops); the unlabelled path adds the clustering's (cluster.get_clustering_labels) and one per scan for its cluster
+    count."""
 
     def __init__(self, config):
         super().__init__()
@@ -290,11 +297,15 @@ class GroupingNetworkModule(nn.Module):
         offset_2 is None unless there is exactly one crop (the reference's head runs for B == 1 only)."""
         feats = inputs[0]
         labels = inputs[1] if len(inputs) >= 2 else None
-        if labels is None and centroids is None:
-            raise ValueError("GroupingNetworkModule: without labels the reference clusters the moved points with DBSCAN "
-                             "(ops_utils.get_clustering_labels), which is not mirrored; pass the centroids")
-        sem_1, offset_1, mask_1, first_features = self.first_ins_cent_model([feats])
+        B = feats.shape[0]
+        unlabelled = labels is None and centroids is None
+        if unlabelled and B > 1:
+            sem_1, offset_1, mask_1, first_features = self.first_ins_cent_model([feats], all_offsets=True)
+        else:
+            sem_1, offset_1, mask_1, first_features = self.first_ins_cent_model([feats])
         out = {"sem_1": sem_1, "offset_1": offset_1, "mask_1": mask_1, "first_features": first_features}
+        if unlabelled:
+            centroids = [self._cluster_centroids(feats[b], sem_1[b], offset_1[b]) for b in range(B)]
         cr = _crops.tooth_crops(feats, labels, centroids, self.crop_sample_size)
         if labels is not None:
             out["cluster_gt_seg_label"] = cr.cluster_gt_seg_label
@@ -302,3 +313,12 @@ class GroupingNetworkModule(nn.Module):
         out.update({"sem_2": sem_2, "offset_2": offset_2, "mask_2": mask_2, "cropped_feature_ls": cr.cropped,
                     "nn_crop_indexes": cr.nn_crop_indexes})
         return out
+
+    @staticmethod
+    def _cluster_centroids(feats, sem, offset):
+        """grouping_network_module.py:59-68 for one scan: feats (C, N), sem (k, N), offset (3, N) -> (T, 3) float32 centroids."""
+        with torch.no_grad():
+            cls = torch.argmax(sem, dim=0)                                  # np.argmax: the first index on ties
+            moved = (feats[:3].t() + offset.t()).contiguous()               # float32, as the reference adds its numpy copies
+            fg_labels = _cluster.get_clustering_labels(moved, cls)
+            return _cluster.cluster_centroids(moved[cls != 0], fg_labels)
