@@ -425,8 +425,9 @@ int tgn_three_interpolate_ex(int B, int N, int S, int C, const float *points2, c
  * index still outside [0,N) -- where the reference raises, e.g. an empty ball yields index N -- makes
  * tgn_gather_points write a zero row and tgn_group_points / tgn_sa_* read point 0, and latches a flag in the
  * current device's memory -- one flag per (device, stream), so host threads that drive different streams do not see or
- * clear each other's.  This returns 1 and clears the flag if that happened in a launch on `stream` since the last call;
- * it synchronises `stream`.  (The Python operators call it and raise IndexError.)
+ * clear each other's.  This returns the word and clears it -- 1 (bit 0) if that happened in a launch on `stream` since the last
+ * call, 2 (bit 1) for what the crop and clustering entry points below latch, 0 for neither; it synchronises `stream`.  (The Python
+ * operators call it and raise IndexError.)
  */
 int tgn_take_index_error(tgn_stream_t stream);
 /* The same over every stream of the current device (synchronises the DEVICE, ORs and clears all of its flags): for planners
@@ -474,15 +475,18 @@ int tgn_crop_gather_center(int b, int n, int c, int t_total, int k, const float 
  *     (the first depth-first search of dbscan_inner that reaches it), every other point is noise (-1).  nclusters (b) int32.  eps > 0,
  *     min_samples >= 1.  workspace: at least tgn_dbscan_workspace_bytes(b, n) bytes of device memory, O(n).
  *   tgn_mean_shift: MeanShift(bandwidth)'s climb (_mean_shift_single_seed, max_iter iterations at most; sklearn's default is 300) from
- *     every point of xyz (n, 3) float64: the new mean is the sum of the points within the bandwidth, sequential in ascending point order,
- *     divided by their count; a seed stops when the shift's norm is <= 1e-3 * bandwidth.  means (n, 3) float64 the final mean, counts (n)
+ *     every point of xyz (n, 3) float64: the new mean is the sum of the points within the bandwidth, sequential in ascending point order
+ *     from -0.0 (the identity of IEEE addition: the sum is p0 + p1 + ... and nothing else; numpy's axis-0 sum is the same sum started from
+ *     +0.0, bit-equal except that a column of nothing but -0.0 gives +0.0 there), divided by their count; a seed stops when the shift's
+ *     norm is <= 1e-3 * bandwidth or max_iter steps were completed before this one (max_iter = 0: one step).  means (n, 3) float64 the
+ *     final mean, counts (n)
  *     int32 the number of points it is the mean of (0: no point within the bandwidth, the seed stayed where it was).  sklearn sums in
  *     its KDTree's order instead, so the means agree with sklearn's to rounding, not bit for bit.
  *   tgn_nearest_center: labels (n) int64 = the index of the centre (m, 3) float64 nearest to each point of xyz (n, 3) float64, by rdist,
  *     ties to the lower index.  m >= 1.
  *   tgn_cluster_moments: for every label l in [0, nlab): counts (nlab) int32 of the points i with labels[i] == l and mask[i] != 0 (mask
- *     NULL: all), their float64 mean (nlab, 3) and covariance (nlab, 3, 3) with ddof = 1 (NaN entries for fewer than 2 points).
- *     xyz (n, 3) float32.
+ *     NULL: all), their float64 mean (nlab, 3) and covariance (nlab, 3, 3) with ddof = 1.  Fewer than 2 points: every covariance entry is
+ *     NaN (as np.cov); no point: count 0 and the mean is NaN too.  xyz (n, 3) float32.
  *   tgn_cluster_vote: out[i] = the most frequent of cand_labels[nn_idx[i][0..k-1]], equal counts to the smallest label (np.unique +
  *     argmax).  1 <= k <= 32.  An index outside [0, n_cand) reads candidate 0 and latches bit 1 of the stream's error word.
  * Deterministic: no atomic whose order reaches an output.  n = 0 (m = 0 for the vote) launches nothing where it is allowed.

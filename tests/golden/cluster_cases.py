@@ -111,3 +111,138 @@ def pack_core(core):
 
 def unpack_core(packed, n):
     return np.unpackbits(packed)[:n].astype(bool)
+
+
+MS_BANDWIDTH = 0.07
+
+
+def _bar(rng, n=900):
+    """A tapered bar 0.5 long whose density falls along it (beta(2, 5)): seeds at the thin end climb for tens of iterations."""
+    t = rng.beta(2, 5, n)[:, None]
+    x = t * [0.5, 0.05, 0.0] + rng.normal(0.0, 0.006, size=(n, 3))
+    return x.astype(np.float32).astype(np.float64)
+
+
+def mean_shift_cases():
+    """-> {tag: (X (n, 3) float64, bandwidth, max_iters tuple, compare_with_sklearn)} for make_golden_r10_cluster_kernels.py and the
+    tests of tgn_mean_shift / tgn_nearest_center.  Not compared with sklearn: `lattice` (its symmetric centres tie) and `nan`
+    (sklearn rejects the input)."""
+    cases = {}
+    rng = np.random.default_rng(1001)
+    two = np.concatenate([rng.normal(0, 0.012, (400, 3)), rng.normal(0, 0.012, (300, 3)) + [0.17, 0, 0]])
+    for n in (1, 2, 13, 255, 256, 257):                   # around the 256-point LDS tile; half the points in a second blob 0.2 away
+        x = rng.normal(0, 0.01, (n, 3))
+        x[n // 2 + 1:] += [0.2, 0.0, 0.0]
+        cases[f"n{n}"] = (x, MS_BANDWIDTH, (300,), True)
+    cases["two"] = (two, MS_BANDWIDTH, (300,), True)
+    dups = np.concatenate([two, two[rng.integers(0, len(two), 100)]])
+    cases["dups"] = (dups[rng.permutation(len(dups))], MS_BANDWIDTH, (300,), True)
+    three = np.concatenate([rng.normal(0, 0.012, (257, 3)) + [0.12 * k, 0.01 * k, 0] for k in range(3)])
+    cases["three"] = (three, MS_BANDWIDTH, (300,), True)
+    cases["f32"] = (three.astype(np.float32).astype(np.float64), MS_BANDWIDTH, (300,), True)
+    bar = _bar(rng)
+    cases["bar"] = (bar, MS_BANDWIDTH, (0, 1, 5, 300), True)
+    # a tight blob and the bar interleaved by index: the seeds of one workgroup retire at different iterations
+    blob = rng.normal(0, 0.004, (900, 3)) + [0.25, 0.4, 0.1]
+    mixed = np.empty((1800, 3))
+    mixed[0::2], mixed[1::2] = blob, bar
+    cases["mixed"] = (mixed, MS_BANDWIDTH, (300,), True)
+    # z = -0.0 everywhere: a sum that starts from -0.0 keeps the sign, one that starts from +0.0 loses it
+    nz = np.concatenate([rng.normal(0, 0.012, (150, 3)), rng.normal(0, 0.012, (150, 3)) + [0.2, 0, 0]])
+    nz[:, 2] = -0.0
+    cases["negzero"] = (nz, MS_BANDWIDTH, (300,), True)
+    # a 9^3 lattice with spacing and bandwidth 2^-4: the six axis neighbours lie AT the bandwidth
+    g = np.arange(9) * 0.0625 + 0.5
+    lat = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
+    cases["lattice"] = (lat[rng.permutation(len(lat))], 0.0625, (300,), False)
+    # one all-NaN row among two blobs
+    nan = two[rng.permutation(len(two))[:300]].copy()
+    nan[137] = np.nan
+    cases["nan"] = (nan, MS_BANDWIDTH, (300,), False)
+    return cases
+
+
+def _pulled_scan(seed, merges, keep_teeth=None):
+    """labelling_cases' scan (synth.labelled_arch(24000, 14, seed), tooth points pulled toward their centroid, 2 % thrown off) with
+    every (a, b) of merges collapsed as `split` collapses teeth 6 and 7, and only keep_teeth in the foreground (None: all)."""
+    rows, lab = synth.labelled_arch(24000, 14, seed=seed)
+    rng = np.random.default_rng(seed)
+    xyz = rows[:, :3].astype(np.float64)
+    cls = np.where(lab >= 0, lab % 9 + 1, 0).astype(np.int64)
+    if keep_teeth is not None:
+        cls[~np.isin(lab, keep_teeth)] = 0
+    moved = xyz.copy()
+    cent = {t: xyz[lab == t].mean(0) for t in range(14)}
+    target = dict(cent)
+    for a, b in merges:
+        d = cent[b] - cent[a]
+        target[b] = cent[a] + 0.17 * d / np.linalg.norm(d)
+    for t in range(14):
+        sel = np.flatnonzero(lab == t)
+        moved[sel] = target[t] + (xyz[sel] - cent[t]) * 0.04 + rng.normal(0.0, 0.004, size=(len(sel), 3))
+        for a, b in merges:
+            if t == b:
+                bridge = sel[rng.permutation(len(sel))[: int(0.4 * len(sel))]]
+                s = rng.uniform(0.0, 1.0, size=len(bridge))[:, None]
+                moved[bridge] = cent[a] + s * (target[b] - cent[a]) + rng.normal(0.0, 0.002, size=(len(bridge), 3))
+    fg = np.flatnonzero(lab >= 0)
+    far = fg[rng.permutation(len(fg))[: len(fg) // 50]]
+    moved[far] += rng.uniform(-0.25, 0.25, size=(len(far), 3))
+    return rows, lab, cls, moved, far, rng
+
+
+def _float32_moved(rows, moved):
+    xyz32 = rows[:, :3]
+    return xyz32 + (moved.astype(np.float32) - xyz32)      # exactly xyz + offset_1 in float32, as labelling_cases
+
+
+def _rd(a, b):
+    d = a - b
+    return ((0.0 + d[..., 0] * d[..., 0]) + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+
+
+def kernel_labelling_cases():
+    """-> {tag: (moved (N, 3) float32, cls (N,) int64)}, the branches of get_clustering_labels that labelling_cases leaves out:
+    split2   teeth 6+7 and teeth 2+3 collapse into two elongated clusters that both pass the ratio test (labels >= 100 and >= 200);
+    three    only teeth 4, 7 and 10 are foreground: exactly three clusters, the reference divides by the mean of nothing;
+    votetie  between each pair of neighbouring teeth one gingiva point becomes a foreground point placed on the line between the two
+             centroids where its 10 nearest tooth points are 5 of one tooth and 5 of the other (found by bisection on the float32
+             values; the generator checks the tie against DBSCAN's labels)."""
+    cases = {}
+    rows, lab, cls, moved, far, rng = _pulled_scan(913, [(6, 7), (2, 3)])
+    cases["split2"] = (_float32_moved(rows, moved), cls)
+    rows, lab, cls, moved, far, rng = _pulled_scan(914, [], keep_teeth=[4, 7, 10])
+    cases["three"] = (_float32_moved(rows, moved), cls)
+    rows, lab, cls, moved, far, rng = _pulled_scan(915, [])
+    m32 = _float32_moved(rows, moved)
+    placed = np.zeros(len(lab), bool)
+    placed[far] = True
+    gingiva = np.flatnonzero(lab < 0)
+    for a in range(13):
+        ia, ib = np.flatnonzero((lab == a) & ~placed), np.flatnonzero((lab == a + 1) & ~placed)
+        pa, pb = m32[ia].astype(np.float64), m32[ib].astype(np.float64)
+        ca, cb = pa.mean(0), pb.mean(0)
+        both, from_a = np.concatenate([pa, pb]), np.arange(len(ia) + len(ib)) < len(ia)
+        lo, hi = 0.0, 1.0                                  # at lo the 10 nearest are mostly of a, at hi mostly of a + 1
+        for _ in range(60):
+            mid = 0.5 * (lo + hi)
+            q = (ca + mid * (cb - ca)).astype(np.float32)
+            na = int(from_a[np.argsort(_rd(both, q.astype(np.float64)), kind="stable")[:10]].sum())
+            if na == 5:
+                g = gingiva[a]
+                m32[g], cls[g] = q, a % 9 + 1
+                break
+            lo, hi = (mid, hi) if na > 5 else (lo, mid)
+    cases["votetie"] = (m32, cls)
+    return cases
+
+
+def moments_far_cloud():
+    """-> (xyz (n, 3) float32, labels (n,) int64, mask (n,) uint8): 15 600 points in 14 labels around (40, -25, 3), so that the mean
+    cancels eight digits; the mask keeps the points within 1.5 sigma in x of their centre, so that ignoring it changes every moment."""
+    rng = np.random.default_rng(7)
+    n = 15600
+    cent, lab = rng.uniform(-0.5, 0.5, (14, 3)), rng.integers(0, 14, n)
+    noise = rng.normal(0, 1, (n, 3))
+    x = (cent[lab] + noise * [0.02, 0.006, 0.004] + [40.0, -25.0, 3.0]).astype(np.float32)
+    return x, lab.astype(np.int64), (np.abs(noise[:, 0]) < 1.5).astype(np.uint8)

@@ -271,7 +271,8 @@ __global__ void __launch_bounds__(kDbThreads) db_border_kernel(int b, int n, con
 // ---- tgn_mean_shift ------------------------------------------------------------------------------------------------------
 // One thread per seed; a workgroup's seeds walk the points together in ascending order, kMsThreads points at a time staged in LDS,
 // and iterate until every seed of the workgroup has stopped.  A seed's sum is sequential in point order and starts from -0.0 (the
-// identity of IEEE addition), so it equals numpy's row-by-row axis-0 sum over the same points in the same order.
+// identity of IEEE addition), so it is p0 + p1 + ... alone: numpy's row-by-row axis-0 sum over the same points in the same order, which
+// starts from +0.0 and so differs in one case only (a column of nothing but -0.0 gives +0.0 there, -0.0 here).
 constexpr int kMsThreads = 256;
 
 __global__ void __launch_bounds__(kMsThreads) mean_shift_kernel(int n, const double *__restrict__ xyz, double bw2, double stop_thresh,
@@ -398,7 +399,10 @@ __global__ void __launch_bounds__(kMomThreads) cluster_moments_kernel(int n, con
             a[5] += dz * dz;
         }
     double r[6];
-    for (int k = 0; k < 6; ++k) r[k] = block_sum(a[k], s_red) / (tot - 1.0);
+    for (int k = 0; k < 6; ++k) {
+        const double s = block_sum(a[k], s_red);
+        r[k] = tot >= 2.0 ? s / (tot - 1.0) : __builtin_nan("");      // np.cov: NaN below 2 points (0 / -1 would be -0.0 for none)
+    }
     if (tid == 0) {
         counts[l] = (int)tot;
         mean[3 * l] = mx;
