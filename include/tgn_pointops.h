@@ -501,6 +501,40 @@ int tgn_cluster_moments(int n, const float *xyz, const long long *labels, const 
 int tgn_cluster_vote(int m, int k, const long long *nn_idx, int n_cand, const long long *cand_labels, long long *out, tgn_stream_t stream);
 
 /*
+ * The join between the two stages of tsegnet (models/modules/tsegnet.py:57-81) and the painting loop of its inference pipeline
+ * (inference_pipelines/inference_pipeline_tsegnet.py:60-66); the reference runs both on the host.  Between tgn_tsg_proposals and
+ * tgn_tsg_crop_features lie tgn_dbscan, tgn_label_centroids and tgn_crop_knn.
+ *   tgn_tsg_proposals: for each scan s of b, l3_xyz, offset (b, 3, m) and dist (b, 1, m) float32 channel-first: point j is kept when
+ *     dist[s, 0, j] < threshold in float32 (NaN is dropped); moved[row] = l3_xyz[s, :, j] + offset[s, :, j], one float32 addition per
+ *     coordinate.  The kept points are written to moved (b * m, 3) row-major PACKED: scan after scan, ascending j inside a scan, the
+ *     first sum(counts) rows; counts (b) int32 the kept points per scan.  1 <= m <= 1024.  One workgroup per scan, no atomics.
+ *     Meant for the b of a forward (b small): every workgroup recounts the scans in front of it, b * (b - 1) / 2 * m comparisons in all.
+ *   tgn_tsg_crop_features: for crop t (scan crop_scan[t], centre cent[t], indices idx (t_total, k) int64): out (t_total, 3 + cf + 1, k)
+ *     float32 with channels 0..2 = feats[scan][0..2, idx] (feats (b, c_stride, n), xyz first; bit copies, NOT centred), channels
+ *     3..3+cf-1 = l0_points[scan][:, idx] (l0_points (b, cf, n); bit copies; cf = 0: none, l0_points may be NULL), the last channel =
+ *     expf(-4 * sqrtf(d)) with d = ((-2 * dot(p, c)) + |p|^2) + |c|^2 in float32, the expanded form of square_distance
+ *     (pointnet2_utils.py:20-41; dot = fma(pz, cz, fma(py, cy, px * cx)), |v|^2 = ((x*x) + (y*y)) + (z*z), as tgn_square_distance).  d is
+ *     NOT clamped: where it rounds below zero the feature is NaN, exactly where the reference's torch.sqrt gives NaN.  out_labels
+ *     (t_total, 1, k) int64 = labels[scan][idx] unchanged (labels (b, n) int64; NULL out_labels: not written).  A crop_scan value
+ *     outside [0, b) reads scan 0, an index outside [0, n) reads point 0; both latch bit 1 of the stream's error word.
+ *   tgn_tsg_paint: out (b, n) int64: out[s, p] = ids[t*], t* the LARGEST crop number t with crop_scan[t] = s that holds p = idx[t, pos]
+ *     at a position with mask[t, pos] != 0 (mask (t_total, k) uint8, ids (t_total) int64), and 0 where no crop does: the result of
+ *     writing the crops one after the other in ascending t.  Entries with a scan outside [0, b) or an index outside [0, n) are skipped
+ *     and latch bit 1.  t_total = 0: out is zeroed.
+ * Deterministic: no atomic whose order reaches an output (tgn_tsg_paint takes an integer maximum).  t_total = 0 launches nothing.
+ * The cluster means in between come from tgn_label_centroids, whose limit is 64 labels: a scan whose proposals form more than 64
+ * clusters (256 proposals with min_samples = 3 allow up to 85) is refused by the host layer, where the reference would go on.
+ * t_total <= 65535.
+ */
+int tgn_tsg_proposals(int b, int m, const float *l3_xyz, const float *offset, const float *dist, float threshold, float *moved,
+                      int *counts, tgn_stream_t stream);
+int tgn_tsg_crop_features(int b, int n, int c_stride, int cf, int t_total, int k, const float *feats, const float *l0_points,
+                          const int *crop_scan, const float *cent, const long long *idx, const long long *labels, float *out,
+                          long long *out_labels, tgn_stream_t stream);
+int tgn_tsg_paint(int b, int n, int t_total, int k, const int *crop_scan, const long long *idx, const unsigned char *mask,
+                  const long long *ids, long long *out, tgn_stream_t stream);
+
+/*
  * DGCNN's neighbourhood work (models/modules/dgcnn.py).  x (B, D, N) float32 channel-first, as the network holds it.
  *   tgn_feature_knn: knn(x, k) (dgcnn.py:4-10) without the N x N matrix.  idx (B, N, k) int64 point indices local to their scan;
  *     row i holds the k smallest distances to point i, i itself included, in ascending (distance, index) order.  The distance is

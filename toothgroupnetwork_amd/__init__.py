@@ -8,6 +8,7 @@ Point-Transformer subtraction / aggregation operators).
     toothgroupnetwork_amd.preprocess        preprocess_data.py / gen_utils.read_txt_obj_ls (OBJ -> 24 000-point .npy)
     toothgroupnetwork_amd.point_transformer mirrors of the cbl_point_transformer blocks (fused eval paths)
     toothgroupnetwork_amd.dgcnn             DGCNN: feature-space kNN, edge features, the DGCnnModule mirror (fused EdgeConv)
+    toothgroupnetwork_amd.tsegnet           tsegnet's join between its two networks and its label painting (proposals, clusters, crops)
     toothgroupnetwork_amd.nets              whole-network mirrors (state_dict-compatible with the reference's modules)
     toothgroupnetwork_amd.sharding          one-process-per-GPU mesh sharding + the RCCL metric gather
     toothgroupnetwork_amd.launch            starting the ranks of a multi-GPU run; rank / device / backend records

@@ -121,6 +121,9 @@ SIGNATURES = {
     "tgn_nearest_center": (c_int, [c_int, _P, c_int, _P, _P, _P]),
     "tgn_cluster_moments": (c_int, [c_int, _P, _P, _P, c_int, _P, _P, _P, _P]),
     "tgn_cluster_vote": (c_int, [c_int, c_int, _P, c_int, _P, _P, _P]),
+    "tgn_tsg_proposals": (c_int, [c_int, c_int, _P, _P, _P, c_float, _P, _P, _P]),
+    "tgn_tsg_crop_features": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "tgn_tsg_paint": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "tgn_feature_knn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "tgn_feature_knn": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "tgn_edgeconv2_max": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, ctypes.c_longlong, c_int, _P]),

@@ -11,13 +11,16 @@ single scan is bound by the host enqueuing its ~350 launches; the saving is the 
 
 Pinned against the reference's own class executed on CPU (tests/golden/make_golden_r3_pipeline.py: loader, FPS and .cuda() served,
 everything else the reference's code): the same label on every vertex.
-Not covered: meshes with fewer than 24 000 vertices, which the reference subdivides with open3d (:25-26)."""
+Not covered: meshes with fewer than 24 000 vertices, which the reference subdivides with open3d (:25-26).
+
+TSegNetInferencePipeLine is the same for tsegnet (inference_pipelines/inference_pipeline_tsegnet.py): the centroid module, the join and
+the painting on the GPU (tsegnet.py), pinned against the reference's class in the same way (tests/golden/make_golden_r11_tsegnet.py)."""
 import time
 
 import numpy as np
 import torch
 
-from . import preprocess, resample
+from . import preprocess, resample, tsegnet
 
 N_POINTS = 24000
 
@@ -71,6 +74,54 @@ class InferencePipeLine:
         result = preprocess.transfer_labels(sampled_feats[:, :3], labels, org_feats[:, :3])
         t.append(time.perf_counter())
         self.times = dict(zip(("load", "sample", "model", "transfer"), np.diff(t).tolist()))
+        return {"sem": result.reshape(-1), "ins": result.reshape(-1)}
+
+
+class TSegNetInferencePipeLine:
+    """inference_pipelines/inference_pipeline_tsegnet.py:9-80 on this package's operators: same constructor and call as the
+    reference class, pipeline(path) -> {"sem": labels per vertex, "ins": the same}.  `model` is anything with `cent_module`,
+    `seg_module` and `get_ddf` (nets.TSegNetModule, the reference's own class, or a stand-in): the centroid module on the 24 000
+    sampled points, then tsegnet.py's join WITHOUT crop subsampling (every cluster centre is cropped, :37-56; the fused crop kernel
+    writes the distance feature, so `get_ddf` is not called), the segmentation module on all crops, the painting loop (:60-66) as
+    tsegnet.paint_labels, the FDI relabelling (:69-70) and the nearest-sample transfer onto every vertex (:72-74).
+    `times` holds the stage times of the last call.  Meshes below 24 000 vertices: NotImplementedError, as InferencePipeLine."""
+
+    def __init__(self, model):
+        self.model = model
+        self.scaler = 1.8
+        self.shifter = 0.8
+        self.times = {}
+
+    def __call__(self, stl_path):
+        t = [time.perf_counter()]
+        feats, mesh = preprocess.read_txt_obj_ls(stl_path, ret_mesh=True)
+        t.append(time.perf_counter())
+        vertices = normalise_for_inference(mesh["vertices"], self.scaler, self.shifter)
+        org_feats = np.concatenate([vertices, mesh["vertex_normals"]], axis=1)
+        if org_feats.shape[0] < N_POINTS:
+            raise NotImplementedError("meshes below 24 000 vertices are subdivided with open3d in the reference (inference_pipeline_tsegnet.py:26-27)")
+        idx = resample.fps(org_feats[:, :3], N_POINTS)                             # gen_utils.resample_pcd(..., "fps")
+        sampled_feats = org_feats[idx[:N_POINTS]]
+        t.append(time.perf_counter())
+        with torch.no_grad():
+            inp = torch.from_numpy(np.ascontiguousarray(sampled_feats.astype("float32"))[None]).cuda().permute(0, 2, 1).contiguous()
+            l0_points, _, _, l3_xyz, offset_result, dist_result = self.model.cent_module(inp)
+            torch.cuda.current_stream().synchronize()
+            t.append(time.perf_counter())
+            moved, counts = tsegnet.centroid_proposals(l3_xyz, offset_result, dist_result)
+            centres = tsegnet.cluster_centers(moved, counts)
+            cropped, nn_crop_indexes, _ = tsegnet.crop_features(inp, l0_points, centres, tsegnet.CROP_K)
+            torch.cuda.current_stream().synchronize()
+            t.append(time.perf_counter())
+            _, _, pd_2, id_pred = self.model.seg_module(cropped)
+            torch.cuda.current_stream().synchronize()
+            t.append(time.perf_counter())
+            cls_pred = tsegnet.paint_labels(nn_crop_indexes, pd_2, id_pred, N_POINTS).reshape(-1).cpu().numpy()
+        t.append(time.perf_counter())
+        labels = fdi_from_classes(cls_pred)
+        result = preprocess.transfer_labels(sampled_feats[:, :3], labels, org_feats[:, :3])
+        t.append(time.perf_counter())
+        self.times = dict(zip(("load", "sample", "centroids", "join", "segmentation", "paint", "transfer"), np.diff(t).tolist()))
         return {"sem": result.reshape(-1), "ins": result.reshape(-1)}
 
 

@@ -21,6 +21,8 @@ of the fused eval paths.  Parameter names and shapes equal the reference classes
                        PointTransformerSeg over the scan, on-device tooth crops (crops.tooth_crops), a second PointTransformerSeg over
                        all crops as one batch.  Without labels the centroids come from on-device clustering (cluster.py); the cbl
                        terms stay the reference's Python.
+  TSegNetModule        models/modules/tsegnet.py:10-88 (the "tsegnet" model): TsgCentroidNet, the join on the GPU (tsegnet.py of this
+                       package: proposal filter, DBSCAN, cluster means, crops with the distance feature), TsgSegNet over the crops.
 """
 import torch
 import torch.nn as nn
@@ -28,9 +30,11 @@ import torch.nn.functional as F
 
 import functools
 
-from . import _derived, _lib, cluster as _cluster, crops as _crops, point_transformer as PT, pointops
+import numpy as np
+
+from . import _derived, _lib, cluster as _cluster, crops as _crops, point_transformer as PT, pointops, tsegnet as _tsg
 from .dgcnn import DGCnnModule  # noqa: F401
-from .pointnet2_utils import PointNetFeaturePropagation, PointNetSetAbstraction, PointNetSetAbstractionMsg, linear_relu
+from .pointnet2_utils import PointNetFeaturePropagation, PointNetSetAbstraction, PointNetSetAbstractionMsg, linear_relu, square_distance
 
 
 def _one_index_check(forward):
@@ -322,3 +326,79 @@ class GroupingNetworkModule(nn.Module):
             moved = (feats[:3].t() + offset.t()).contiguous()               # float32, as the reference adds its numpy copies
             fg_labels = _cluster.get_clustering_labels(moved, cls)
             return _cluster.cluster_centroids(moved[cls != 0], fg_labels)
+
+
+class TSegNetModule(nn.Module):
+    """models/modules/tsegnet.py:10-88 (the "tsegnet" model): `cent_module` (TsgCentroidNet) proposes tooth centroids from 256 coarse
+    points, `seg_module` (TsgSegNet) segments a 3072-point crop around each centre.  Same constructor argument, attribute names and
+    state_dict as the reference's class, so its checkpoints load with strict=True.  The join between the stages -- the proposal
+    filter, DBSCAN(0.05, 3), the cluster means, the KDTree crops, the gathers and the distance feature -- is host work with a device
+    round trip at every step in the reference; here it is tsegnet.py's HIP kernels.
+
+    Like the reference, at most 8 centres are kept, chosen by `np.random.permutation(T)[:8]` on numpy's GLOBAL generator: the same
+    `np.random.seed` gives the same crops as the reference (one call per scan, in scan order).  The reference is only meaningful for
+    B = 1 (its `.T.reshape(-1, 3)` mixes scans); here every scan of a batch is clustered on its own in one ragged DBSCAN launch.
+    `center_points` is what the reference returns for B = 1, a (1, T, 3) float32 numpy array, and for B > 1 a list over scans of
+    (1, T_b, 3) arrays.  Host synchronisations per forward: tsegnet.py's two (kept counts, cluster counts) and the copy of
+    `center_points` to the host that the reference's return type asks for.  In eval mode the segmentation module runs scan by scan
+    (`segment`), so a scan's outputs do not depend on the rest of the batch.  The losses (models/tsg_loss.py) stay the reference's
+    Python."""
+
+    MAX_CROPS = 8            # tsegnet.py:70
+    CROP_K = 3072            # tsegnet.py:73
+
+    def __init__(self, config):
+        super().__init__()
+        self.config = config
+        self.cent_module = TsgCentroidNet()
+        self.seg_module = TsgSegNet()
+        self.run_seg_module = bool(self.config["run_tooth_segmentation_module"])
+
+    def get_ddf(self, cropped_coord, center_points):
+        """cropped_coord (T, k, 3) float32 on the GPU, center_points (1, T, 3) numpy array or tensor -> (T, 1, k):
+        exp(-4 sqrt(square_distance(crop point, its centre))) (tsegnet.py:24-33).  forward does not call it: the fused crop kernel
+        writes the same feature (tgn_tsg_crop_features)."""
+        if not isinstance(center_points, torch.Tensor):
+            center_points = torch.from_numpy(center_points)
+        center_points = center_points.to(cropped_coord.device, cropped_coord.dtype)
+        ddf = square_distance(cropped_coord.contiguous(), center_points.permute(1, 0, 2).contiguous())
+        ddf = torch.exp(torch.sqrt(ddf) * (-4))
+        return ddf.permute(0, 2, 1)
+
+    def segment(self, cropped, per_scan):
+        """The segmentation module on the crops (T, 36, k) of a batch, per_scan = the number of crops of every scan.  Train mode: all
+        crops as ONE batch, as the reference runs them (its BatchNorm statistics are taken over all of them).  Eval mode: one scan's
+        crops at a time, so that what a scan gets does not depend on what else is in the batch -- the same crop in a batch of 8 and in
+        a batch of 16 differs in the last bits (measured on an MI355X: up to 2.6e-6 relative in pd_2, on bit-equal input; the
+        presumed cause, not traced to a layer, is that the library GEMMs behind the network pick their kernels by the row count).
+        The price is B passes of the segmentation network's launches instead of one in eval mode.  Scan 0 of a B = 2 forward is then bit-equal to the B = 1 forward."""
+        if self.training or len(per_scan) == 1:
+            return self.seg_module(cropped)
+        outs = [self.seg_module(c) for c in cropped.split(per_scan)]
+        return tuple(torch.cat(parts) for parts in zip(*outs))
+
+    def forward(self, inputs):
+        """inputs: [features (B, 6, N), labels (B, 1, N)] (labels may be left out: cluster_gt_seg_label is then None) -> the
+        reference's output dict: l0_points, l3_points, l0_xyz, l3_xyz, offset_result, dist_result and, when the segmentation module
+        runs, pd_1, weight_1, pd_2, id_pred, center_points, cluster_gt_seg_label, cropped_feature_ls."""
+        feats = inputs[0]
+        labels = inputs[1] if len(inputs) >= 2 else None
+        l0_points, l3_points, l0_xyz, l3_xyz, offset_result, dist_result = self.cent_module(feats)
+        outputs = {"l0_points": l0_points, "l3_points": l3_points, "l0_xyz": l0_xyz, "l3_xyz": l3_xyz,
+                   "offset_result": offset_result, "dist_result": dist_result}
+        if not self.run_seg_module:
+            return outputs
+        with torch.no_grad():
+            moved, counts = _tsg.centroid_proposals(l3_xyz, offset_result, dist_result)
+            centres = _tsg.cluster_centers(moved, counts)
+            chosen = []
+            for c in centres:
+                rand_indexes = np.random.permutation(c.shape[0])[:self.MAX_CROPS]
+                chosen.append(c.index_select(0, torch.from_numpy(rand_indexes).to(c.device, non_blocking=True)))
+        cropped, _, crop_labels = _tsg.crop_features(feats, l0_points, chosen, self.CROP_K, labels)
+        pd_1, weight_1, pd_2, id_pred = self.segment(cropped, [int(c.shape[0]) for c in chosen])
+        center_points = [c.cpu().numpy()[None] for c in chosen]
+        outputs.update({"pd_1": pd_1, "weight_1": weight_1, "pd_2": pd_2, "id_pred": id_pred,
+                        "center_points": center_points[0] if len(center_points) == 1 else center_points,
+                        "cluster_gt_seg_label": crop_labels, "cropped_feature_ls": cropped})
+        return outputs
