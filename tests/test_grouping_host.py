@@ -20,6 +20,43 @@ def test_tooth_crops_without_labels_or_centroids_raises_before_any_launch(monkey
         crops.tooth_crops(torch.zeros(1, 6, 100))
 
 
+def test_tooth_crops_validates_its_arguments_before_any_launch(monkeypatch):
+    import numpy as np
+    from toothgroupnetwork_amd import _lib, crops
+    feats, lab = torch.zeros(1, 6, 100), torch.zeros(1, 100, dtype=torch.int64)
+    monkeypatch.setattr(_lib, "require_cuda", lambda *t: None)
+    monkeypatch.setattr(_lib, "lib", lambda: pytest.fail("the library was reached"))
+    for k in (0, 101):
+        with pytest.raises(ValueError, match=rf"k = {k} must satisfy 1 <= k <= min\(N, 4096\) = 100"):
+            crops.tooth_crops(feats, lab, k=k)
+    with pytest.raises(ValueError, match="1 <= k"):
+        crops.tooth_crops(feats, centroids=[np.zeros((2, 3))], k=101)
+    with pytest.raises(TypeError, match="int32 or int64"):
+        crops.tooth_crops(feats, lab.float(), k=8)
+    with pytest.raises(ValueError, match="labels must be"):                # int32 is accepted: the shape check is what fails
+        crops.tooth_crops(feats, lab.int()[:, :99], k=8)
+    with pytest.raises(ValueError, match=r"feats must be \(B, C >= 3, N\)"):
+        crops.tooth_crops(feats[:, :2], lab, k=8)
+    # past the label checks tooth_crops takes the library handle and the stream, then stacks the centroids: all still host work
+    monkeypatch.setattr(_lib, "lib", lambda: object())                     # any launch through it is an AttributeError
+    monkeypatch.setattr(_lib, "stream", lambda: None)
+    with pytest.raises(ValueError, match="centroids must be a list of 1 per-scan"):
+        crops.tooth_crops(feats, centroids=[np.zeros((2, 3))] * 2, k=8)
+    with pytest.raises(ValueError, match="no tooth"):
+        crops.tooth_crops(feats, centroids=[np.zeros((0, 3))], k=8)
+    seen = {}                                                              # a flat centroid entry is reshaped to (-1, 3) and accepted
+
+    def stop_at_the_launch(feats_, scan, cent, k):
+        seen.update(scan=scan, cent=cent, k=k)
+        raise KeyboardInterrupt
+
+    monkeypatch.setattr(crops, "crop_knn", stop_at_the_launch)
+    with pytest.raises(KeyboardInterrupt):
+        crops.tooth_crops(feats, centroids=[np.arange(6.0)], k=8)
+    assert seen["cent"].dtype == torch.float32 and seen["cent"].tolist() == [[0, 1, 2], [3, 4, 5]]
+    assert seen["scan"].dtype == torch.int32 and seen["scan"].tolist() == [0, 0] and seen["k"] == 8
+
+
 @pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "models")), reason="reference checkout not present")
 def test_grouping_network_state_dict_equals_the_reference(monkeypatch):
     from toothgroupnetwork_amd import nets

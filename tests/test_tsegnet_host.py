@@ -149,6 +149,40 @@ def test_host_layer_validates_its_arguments():
         T.crop_features(feats, l0, cents, k=4, labels=torch.zeros(1, 16, dtype=torch.int32))
     with pytest.raises(ValueError, match="labels must be"):
         T.crop_features(feats, l0, cents, k=4, labels=torch.zeros(1, 15, dtype=torch.int64))
+    with pytest.raises(ValueError, match="1 <= k"):
+        T.crop_features(feats, l0, cents, k=0)
+    with pytest.raises(ValueError, match="list of 1 per-scan"):
+        T.crop_features(feats, l0, cents[0], k=4)                          # a bare array is not a list over scans
+    with pytest.raises(ValueError, match=r"must be \(T_b, 3\)"):
+        T.crop_features(feats, l0, [np.zeros((2, 2), np.float32)], k=4)
+    with pytest.raises(ValueError, match=r"must be \(T_b, 3\)"):
+        T.crop_features(feats, l0, [torch.zeros(6)], k=4)
+    with pytest.raises(TypeError, match="int64"):
+        T.crop_features(feats, l0, cents, k=4, labels=np.zeros((1, 16), np.int64))
+    # the shared helpers of crops.py that crop_features, tooth_crops and the noise vote go through, on their own
+    from toothgroupnetwork_amd import crops as C
+    cpu = torch.device("cpu")
+    with pytest.raises(ValueError, match="centres must be a list of 2 per-scan"):
+        C.stack_centres(cents, 2, cpu, "centres")
+    with pytest.raises(ValueError, match=r"every scan's centroids must be \(T_b, 3\), got \(3, 2\)"):
+        C.stack_centres((np.zeros((1, 3)), np.zeros((3, 2))), 2, cpu, "centroids")
+    cent, scan, per_scan = C.stack_centres([np.ones((2, 3)), torch.zeros(0, 3), [[1, 2, 3]]], 3, cpu, "centres")
+    assert cent.dtype == torch.float32 and cent.is_contiguous() and cent.tolist() == [[1, 1, 1], [1, 1, 1], [1, 2, 3]]
+    assert scan.dtype == torch.int32 and scan.tolist() == [0, 0, 2] and per_scan == [2, 0, 1]
+    assert C.scan_ids([1, 0, 2], cpu).tolist() == [0, 2, 2] and C.scan_ids([0], cpu).shape == (0,)
+    for k, n in ((0, 16), (17, 16), (4097, 5000)):
+        with pytest.raises(ValueError, match=rf"k = {k} must satisfy 1 <= k <= min\(N, 4096\) = {min(n, 4096)}"):
+            C.crop_knn(torch.zeros(1, 3, n), scan, cent, k)
+    assert C.check_k(4096, 5000) == 4096 and C.check_k(np.int64(16), 16) == 16 and (C.MAX_K, C.MAX_CLUSTERS) == (4096, 64)
+    lab32 = torch.arange(16, dtype=torch.int32).reshape(1, 1, 16)
+    with pytest.raises(TypeError, match="int64, got torch.int32"):
+        C.labels_2d(lab32, 1, 16, (torch.int64,))
+    with pytest.raises(TypeError, match="int32 or int64, got torch.float32"):
+        C.labels_2d(lab32.float(), 1, 16, (torch.int32, torch.int64))
+    with pytest.raises(ValueError, match="labels must be"):
+        C.labels_2d(lab32, 1, 15, (torch.int32, torch.int64))
+    got = C.labels_2d(lab32, 1, 16, (torch.int32, torch.int64))
+    assert got.dtype == torch.int64 and got.is_contiguous() and got.tolist() == [list(range(16))]
     idx, pd_2, ids = [torch.zeros(2, 4, dtype=torch.int64)], torch.zeros(2, 1, 4), torch.zeros(2, 17)
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         T.paint_labels(idx, pd_2, ids, 16)

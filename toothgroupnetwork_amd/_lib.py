@@ -138,6 +138,9 @@ SIGNATURES = {
 }
 
 ERR_INVALID_ARGUMENT, ERR_LAUNCH, ERR_UNSUPPORTED = 1, 2, 3     # TGN_ERR_* of include/tgn_pointops.h
+# bits of a stream's error word (tgn_take_index_error; csrc/tgn_common.h: kIndexErrGather, kIndexErrCrop)
+INDEX_ERROR_GATHER = 1      # the gather family: an index outside the gathered dimension
+INDEX_ERROR_CROP = 2        # crop.hip, cluster.hip, tsegnet.hip: a label or a crop index out of range
 
 FPS_FMA = 1
 FPS_LOCAL_INDEX = 2

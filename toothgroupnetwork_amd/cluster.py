@@ -5,7 +5,8 @@ host; here the per-point work is HIP (csrc/cluster.hip, include/tgn_pointops.h):
   dbscan                 sklearn's DBSCAN(eps, min_samples).fit(X): equal labels and core flags
   mean_shift             sklearn's MeanShift(bandwidth) with its defaults: equal labels_; cluster_centers_ equal to rounding (sklearn
                          sums each seed's neighbours in its KDTree's order, the kernel in ascending point order)
-  get_clustering_labels  ops_utils.get_clustering_labels step by step
+  get_clustering_labels  ops_utils.get_clustering_labels step by step (the noise vote's kNN is crop.hip's, through crops.crop_knn)
+  cluster_centroids      the float32 mean of every cluster's points (crop.hip's label means, through crops.label_centroids)
 
 sklearn picks a brute-force neighbour search (the expanded distance formula) for fewer than 12 points; the kernels always use the
 KDTree's rdist, so results on such tiny inputs can differ where a pair lies within rounding of the radius.
@@ -13,7 +14,7 @@ KDTree's rdist, so results on such tiny inputs can differ where a pair lies with
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, crops as _crops
 
 DBSCAN_EPS, DBSCAN_MIN_SAMPLES = 0.03, 30     # ops_utils.py:96
 SPLIT_RATIO, SPLIT_BANDWIDTH = 8, 0.07        # ops_utils.py:127, :132
@@ -156,7 +157,7 @@ def get_clustering_labels(moved_points, labels):
       2. per cluster the largest eigenvalue of its core points' covariance (PCA(3).explained_variance_[0]; tgn_cluster_moments);
       3. among the three largest, a cluster above 8x the mean of the others is re-split with MeanShift(0.07) over all its points,
          labelled ms_label + 100 * (position in that list + 1);
-      4. every noise point takes the most frequent label among its 10 nearest labelled points (ascending (rdist, index); tgn_crop_knn),
+      4. every noise point takes the most frequent label among its 10 nearest labelled points (ascending (rdist, index), crops.crop_knn),
          equal counts to the smallest label (tgn_cluster_vote).
     Host synchronisations: 3, plus 2 per re-split cluster -- the foreground compaction, the cluster count, the moments, per split its
     point compaction and its seed means, and the noise compaction.
@@ -206,11 +207,8 @@ def get_clustering_labels(moved_points, labels):
                          "(the reference's KDTree.query raises here too)")
     q = pts[noise].contiguous()
     if q.shape[0]:
-        feats = cand_pts.t().contiguous()
-        scan = torch.zeros(q.shape[0], dtype=torch.int32, device=dev)
-        idx = torch.empty(q.shape[0], VOTE_K, dtype=torch.int64, device=dev)
-        _lib.check(L.tgn_crop_knn(1, m, 3, _lib.ptr(feats), q.shape[0], _lib.ptr(scan), _lib.ptr(q), VOTE_K, _lib.ptr(idx), st),
-                   "tgn_crop_knn")
+        scan = torch.zeros(q.shape[0], dtype=torch.int32, device=dev)                         # one cloud: the labelled points
+        idx = _crops.crop_knn(cand_pts.t().contiguous()[None], scan, q, VOTE_K)
         cand_labels = out[cand].contiguous()
         vote = torch.empty(q.shape[0], dtype=torch.int64, device=dev)
         _lib.check(L.tgn_cluster_vote(q.shape[0], VOTE_K, _lib.ptr(idx), m, _lib.ptr(cand_labels), _lib.ptr(vote), st), "tgn_cluster_vote")
@@ -218,23 +216,14 @@ def get_clustering_labels(moved_points, labels):
     return out.cpu().numpy() if as_numpy else out
 
 
-MAX_CLUSTERS = 64                             # tgn_label_centroids' label limit
-
-
 def cluster_centroids(moved_fg, cluster_labels):
     """grouping_network_module.py:66-68: the mean of the moved foreground points (M, 3) float32 of every final label, in ascending
-    label order -> (T, 3) float32, bit-equal to numpy's float32 mean(axis=0) (tgn_label_centroids on the dense-ranked labels).
+    label order -> (T, 3) float32, bit-equal to numpy's float32 mean(axis=0) (crops.label_centroids on the dense-ranked labels).
     ONE host synchronisation (the number of labels).  More than 64 clusters: ValueError."""
     uniq, rank = torch.unique(cluster_labels, sorted=True, return_inverse=True)
     T = int(uniq.shape[0])
-    if T > MAX_CLUSTERS:
-        raise ValueError(f"{T} clusters: at most {MAX_CLUSTERS} tooth centroids are supported (tgn_label_centroids)")
-    M = moved_fg.shape[0]
-    feats = moved_fg.to(torch.float32).t().contiguous()
-    rank = rank.to(torch.int64).contiguous()
-    counts = torch.empty(1, T, dtype=torch.int32, device=feats.device)
-    cent = torch.empty(1, T, 3, dtype=torch.float32, device=feats.device)
-    L = _lib.lib()
-    _lib.check(L.tgn_label_centroids(1, M, 3, _lib.ptr(feats), _lib.ptr(rank), T, _lib.ptr(counts), _lib.ptr(cent), _lib.stream()),
-               "tgn_label_centroids")
+    if T > _crops.MAX_CLUSTERS:
+        raise ValueError(f"{T} clusters: at most {_crops.MAX_CLUSTERS} tooth centroids are supported (tgn_label_centroids)")
+    feats = moved_fg.to(torch.float32).t().contiguous()[None]
+    _, cent = _crops.label_centroids(feats, rank.to(torch.int64).contiguous()[None], T)
     return cent[0]

@@ -11,6 +11,9 @@ loop (centering_object); here it is three HIP kernels (csrc/crop.hip, include/tg
 Centroids from clustering (the unlabelled path: ops_utils.get_clustering_labels) come from cluster.py -- nets.GroupingNetworkModule
 computes them there and passes them as `centroids`, as any caller that has centroids may; tooth_crops itself needs labels or
 centroids.
+
+This is also the one host layer over crop.hip for cluster.py (noise vote, cluster centroids) and tsegnet.py (cluster means, the join's
+crops): the launches crop_knn and label_centroids, their operands (stack_centres, scan_ids, labels_2d), the limits MAX_K, MAX_CLUSTERS.
 """
 from collections import namedtuple
 
@@ -20,20 +23,74 @@ import torch
 from . import _lib
 
 NUM_LABELS = 16          # tooth labels 0..15, -1 = gingiva (generator.py:46-47)
-MAX_K = 4096             # ops_utils.get_nearest_neighbor_idx's default crop_num; the kernel's limit
-_CROP_ERROR = 2          # bit 1 of the stream's error word (include/tgn_pointops.h: tgn_label_centroids)
+MAX_K = 4096             # ops_utils.get_nearest_neighbor_idx's default crop_num; tgn_crop_knn's limit
+MAX_CLUSTERS = 64        # tgn_label_centroids' label limit
 
 ToothCrops = namedtuple("ToothCrops", "cropped nn_crop_indexes cluster_gt_seg_label centroids")
 
 
-def _labels_2d(labels, B, N):
-    if labels.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"labels must be int32 or int64, got {labels.dtype}")
+def labels_2d(labels, B, N, dtypes):
+    """(B, N) or (B, 1, N) labels of one of `dtypes` -> (B, N) int64 contiguous."""
+    if not isinstance(labels, torch.Tensor) or labels.dtype not in dtypes:
+        names = " or ".join(str(d).replace("torch.", "") for d in dtypes)
+        raise TypeError(f"labels must be a torch tensor of {names}, got {getattr(labels, 'dtype', type(labels).__name__)}")
     if labels.dim() == 3 and labels.shape[1] == 1:
         labels = labels[:, 0]
     if tuple(labels.shape) != (B, N):
         raise ValueError(f"labels must be (B, N) or (B, 1, N) = ({B}, {N}), got {tuple(labels.shape)}")
     return labels.to(torch.int64).contiguous()
+
+
+def scan_ids(per_scan, dev):
+    """per_scan: the number of centres of every scan -> (T,) int32 on dev, the scan of every centre (scan-major)."""
+    return torch.from_numpy(np.repeat(np.arange(len(per_scan), dtype=np.int32), per_scan)).to(dev, non_blocking=True)
+
+
+def stack_centres(centres, B, dev, what):
+    """centres: list or tuple over the B scans of (T_b, 3) arrays or tensors -> tgn_crop_knn's operands (cent (T, 3) float32
+    contiguous on dev, scan (T,) int32 on dev, per_scan: list of the T_b).  `what` names the argument in the errors."""
+    if not isinstance(centres, (list, tuple)) or len(centres) != B:
+        raise ValueError(f"{what} must be a list of {B} per-scan (T_b, 3) arrays or tensors")
+    parts = []
+    for c in centres:
+        c = c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(c), dtype=np.float32))
+        if c.dim() != 2 or c.shape[1] != 3:
+            raise ValueError(f"every scan's {what} must be (T_b, 3), got {tuple(c.shape)}")
+        parts.append(c.to(dev, torch.float32))
+    per_scan = [int(p.shape[0]) for p in parts]
+    return torch.cat(parts).contiguous(), scan_ids(per_scan, dev), per_scan
+
+
+def check_k(k, N):
+    """k as an int within tgn_crop_knn's range for scans of N points; callers with GPU work ahead of crop_knn ask before that work."""
+    k = int(k)
+    if not 1 <= k <= min(N, MAX_K):
+        raise ValueError(f"k = {k} must satisfy 1 <= k <= min(N, {MAX_K}) = {min(N, MAX_K)} (KDTree.query raises for k > N too)")
+    return k
+
+
+def crop_knn(feats, scan, cent, k):
+    """feats (B, C >= 3, N) float32 contiguous with xyz in channels 0..2, scan (T,) int32 and cent (T, 3) float32 (stack_centres) ->
+    idx (T, k) int64: per centre the k nearest points of its scan, ascending (float64 squared distance, index).  No synchronisation."""
+    B, C, N = feats.shape
+    k = check_k(k, N)
+    T = cent.shape[0]
+    idx = torch.empty(T, k, dtype=torch.int64, device=feats.device)
+    _lib.check(_lib.lib().tgn_crop_knn(B, N, C, _lib.ptr(feats), T, _lib.ptr(scan), _lib.ptr(cent), k, _lib.ptr(idx), _lib.stream()),
+               "tgn_crop_knn")
+    return idx
+
+
+def label_centroids(feats, labels, nlab):
+    """feats (B, C >= 3, N) float32 and labels (B, N) int64, contiguous -> (counts (B, nlab) int32, cent (B, nlab, 3) float32): per scan
+    and label 0..nlab-1 its point count and float32 mean, bit-equal to numpy's xyz[label == t].mean(axis=0).  -1 is skipped; another label
+    outside [0, nlab) latches _lib.INDEX_ERROR_CROP, which is neither cleared nor read here.  No synchronisation."""
+    B, C, N = feats.shape
+    counts = torch.empty(B, nlab, dtype=torch.int32, device=feats.device)
+    cent = torch.empty(B, nlab, 3, dtype=torch.float32, device=feats.device)
+    _lib.check(_lib.lib().tgn_label_centroids(B, N, C, _lib.ptr(feats), _lib.ptr(labels), nlab, _lib.ptr(counts), _lib.ptr(cent),
+                                              _lib.stream()), "tgn_label_centroids")
+    return counts, cent
 
 
 def tooth_crops(feats, labels=None, centroids=None, k=3072, num_labels=NUM_LABELS):
@@ -59,38 +116,28 @@ def tooth_crops(feats, labels=None, centroids=None, k=3072, num_labels=NUM_LABEL
         raise TypeError(f"feats must be float32, got {feats.dtype}")
     feats = feats.detach().contiguous()
     B, C, N = feats.shape
-    k = int(k)
-    if not 1 <= k <= min(N, MAX_K):
-        raise ValueError(f"k = {k} must satisfy 1 <= k <= min(N, {MAX_K}) = {min(N, MAX_K)} (KDTree.query raises for k > N too)")
+    k = check_k(k, N)
+    lab = labels_2d(labels, B, N, (torch.int32, torch.int64)) if labels is not None else None
     L, dev, st = _lib.lib(), feats.device, _lib.stream()
-    lab = _labels_2d(labels, B, N) if labels is not None else None
     if centroids is None:
-        counts = torch.empty(B, num_labels, dtype=torch.int32, device=dev)
-        cent_all = torch.empty(B, num_labels, 3, dtype=torch.float32, device=dev)
         _lib.check(L.tgn_clear_index_error(st), "tgn_clear_index_error")
-        _lib.check(L.tgn_label_centroids(B, N, C, _lib.ptr(feats), _lib.ptr(lab), num_labels, _lib.ptr(counts), _lib.ptr(cent_all), st),
-                   "tgn_label_centroids")
+        counts, cent_all = label_centroids(feats, lab, num_labels)
         present = counts.cpu().numpy() > 0                                        # the one synchronisation
-        if L.tgn_take_index_error(st) & _CROP_ERROR:
+        if L.tgn_take_index_error(st) & _lib.INDEX_ERROR_CROP:
             raise ValueError(f"tooth_crops: a label outside [-1, {num_labels}) (gingiva -1, teeth 0..{num_labels - 1})")
         per_scan = present.sum(1).tolist()
         rows = torch.from_numpy(np.flatnonzero(present.reshape(-1))).to(dev, non_blocking=True)
         cent = cent_all.view(-1, 3).index_select(0, rows).contiguous()
+        scan = scan_ids(per_scan, dev)
     else:
-        if len(centroids) != B:
-            raise ValueError(f"centroids must be a list of {B} per-scan (T_b, 3) arrays")
-        parts = [torch.as_tensor(np.asarray(c, np.float32) if not isinstance(c, torch.Tensor) else c).to(dev, torch.float32).reshape(-1, 3)
-                 for c in centroids]
-        per_scan = [int(p.shape[0]) for p in parts]
-        cent = torch.cat(parts).contiguous()
+        flat = [(c if isinstance(c, torch.Tensor) else np.asarray(c, np.float32)).reshape(-1, 3) for c in centroids]
+        cent, scan, per_scan = stack_centres(flat, B, dev, "centroids")
     T = int(sum(per_scan))
     if T == 0:
         raise ValueError("tooth_crops: no tooth in the batch (every point is gingiva, label -1)")
-    scan = torch.from_numpy(np.repeat(np.arange(B, dtype=np.int32), per_scan)).to(dev, non_blocking=True)
-    idx = torch.empty(T, k, dtype=torch.int64, device=dev)
+    idx = crop_knn(feats, scan, cent, k)
     cropped = torch.empty(T, C, k, dtype=torch.float32, device=dev)
     crop_lab = torch.empty(T, 1, k, dtype=torch.int64, device=dev) if lab is not None else None
-    _lib.check(L.tgn_crop_knn(B, N, C, _lib.ptr(feats), T, _lib.ptr(scan), _lib.ptr(cent), k, _lib.ptr(idx), st), "tgn_crop_knn")
     _lib.check(L.tgn_crop_gather_center(B, N, C, T, k, _lib.ptr(feats), _lib.ptr(scan), _lib.ptr(idx), _lib.ptr(lab), _lib.ptr(cropped),
                                         _lib.ptr(crop_lab), st), "tgn_crop_gather_center")
     return ToothCrops(cropped, list(idx.split(per_scan)), crop_lab, list(cent.split(per_scan)))

@@ -441,7 +441,7 @@ __global__ void cluster_vote_kernel(int m, int k, const long long *__restrict__ 
         }
     }
     out[i] = best;
-    if (bad && err) atomicOr(err, 2);
+    if (bad && err) atomicOr(err, kIndexErrCrop);
 }
 
 }  // namespace tgn

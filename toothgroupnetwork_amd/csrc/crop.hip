@@ -10,8 +10,6 @@
 
 namespace tgn {
 
-constexpr int kCropErrBit = 2;
-
 // ---- tgn_label_centroids -------------------------------------------------------------------------------------------------
 // One workgroup per scan walks the scan in chunks of kCentThreads points.  Per chunk: a stable counting sort of the chunk's points by
 // label into LDS (ballot per label and wave; the rank inside a wave is mbcnt, so point order is kept within a label), then lane
@@ -84,7 +82,7 @@ __global__ void __launch_bounds__(kCentThreads) label_centroids_kernel(int n, in
         }
         __syncthreads();
     }
-    if (__any(bad_seen) && lane == 0 && err) atomicOr(err, kCropErrBit);
+    if (__any(bad_seen) && lane == 0 && err) atomicOr(err, kIndexErrCrop);
     if (summer) {
         cent[((long long)b * nlab + my_l) * 3 + my_ax] = acc / (float)total;   // 0 / 0 = NaN for an absent label, as numpy's mean
         if (my_ax == 0) counts[(long long)b * nlab + my_l] = total;
@@ -120,7 +118,7 @@ __global__ void __launch_bounds__(kKnnThreads) crop_knn_kernel(int nscan, int n,
     const int b = crop_scan[t];
     if (b < 0 || b >= nscan) {                          // uniform over the block
         for (int j = tid; j < k; j += kKnnThreads) out[j] = 0;
-        if (tid == 0 && err) atomicOr(err, kCropErrBit);
+        if (tid == 0 && err) atomicOr(err, kIndexErrCrop);
         return;
     }
     const float *X = feats + (long long)b * c_stride * n;
@@ -279,7 +277,7 @@ __global__ void __launch_bounds__(kGatherThreads) crop_gather_center_kernel(
             out_labels[(long long)t * k + j] = v >= 0 ? 0 : v;
         }
     }
-    if (__syncthreads_or(bad) && tid == 0 && err) atomicOr(err, kCropErrBit);
+    if (__syncthreads_or(bad) && tid == 0 && err) atomicOr(err, kIndexErrCrop);
 }
 
 }  // namespace tgn

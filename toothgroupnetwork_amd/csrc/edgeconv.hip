@@ -213,7 +213,7 @@ __global__ __launch_bounds__(kEcThreads) void edgeconv2_max_kernel(int B, int N,
         const float y = lrelu02((h ? m1 : m0) + bias);
         out[(size_t)b * ostride + (size_t)(coff + 32 * h + r) * N + i] = y;
     }
-    if (__any(bad) && lane == 0 && err) atomicOr(err, 1);
+    if (__any(bad) && lane == 0 && err) atomicOr(err, kIndexErrGather);
 }
 
 // ---- tgn_edgeconv1_max --------------------------------------------------------------------------------------------------------
@@ -237,7 +237,7 @@ __global__ __launch_bounds__(kEcThreads) void edgeconv1_max_kernel(int B, int N,
         }
         out[(size_t)b * ostride + (size_t)(coff + lane) * N + i] = lrelu02(m + Q[(size_t)g * kEcC + lane]);
     }
-    if (__any(bad) && lane == 0 && err) atomicOr(err, 1);
+    if (__any(bad) && lane == 0 && err) atomicOr(err, kIndexErrGather);
 }
 
 static int ec_grid(long long nq) {

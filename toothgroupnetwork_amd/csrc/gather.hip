@@ -371,7 +371,7 @@ __global__ __launch_bounds__(256) void sa_first_layer_kernel(long long queries, 
             }
             sfb[wv][k] = ((unsigned)pbase + (unsigned)v64) * (unsigned)C;
         }
-        if (err && __any(bad) && lane == 0) atomicOr(err, 1);
+        if (err && __any(bad) && lane == 0) atomicOr(err, kIndexErrGather);
         const float *__restrict__ cst = Cst + (size_t)q * C;
         if constexpr (MAXK) {
             float *__restrict__ dst = out + (size_t)q * C;
@@ -406,7 +406,7 @@ __global__ __launch_bounds__(256) void gather_points_kernel(long long rows, int 
         if (k < 0) k += N;  // torch's advanced indexing wraps negative indices (pointnet2_utils.py:56-60)
         float *dst = out + (size_t)r * C;
         if (k < 0 || k >= N) {  // the reference raises here: the row is zero-filled and the error word latched
-            if (err && tx == 0) atomicOr(err, 1);
+            if (err && tx == 0) atomicOr(err, kIndexErrGather);
             for (int ci = tx; ci < C; ci += cx) dst[ci] = 0.0f;
             continue;
         }

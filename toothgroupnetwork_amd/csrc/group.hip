@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(24))) void grou
             srel[wv][k * 3 + 1] = xyz[pv * 3u + 1u] - cq1;
             srel[wv][k * 3 + 2] = xyz[pv * 3u + 2u] - cq2;
         }
-        if (err && __any(bad) && lane == 0) atomicOr(err, 1);
+        if (err && __any(bad) && lane == 0) atomicOr(err, kIndexErrGather);
         float *__restrict__ dst = out + (size_t)q * total;
 #pragma unroll 1
         for (int e = lane; e < total; e += kWave) {
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(24))) void grou
             srel[wv][k * 3 + 1] = py - cq1;
             srel[wv][k * 3 + 2] = pz - cq2;
         }
-        if (err && __any(bad) && lane == 0) atomicOr(err, 1);
+        if (err && __any(bad) && lane == 0) atomicOr(err, kIndexErrGather);
         // (the same wave wrote the tables: LDS operations of one wave complete in order, no barrier needed)
         const __amdgpu_buffer_rsrc_t rs_pts = make_rsrc(points + (size_t)b * N * D, (unsigned)N * (unsigned)D * 4u);
         const __amdgpu_buffer_rsrc_t rs_out = make_rsrc(out + (size_t)q * total, total * 4u);
@@ -394,7 +394,7 @@ __global__ __launch_bounds__(64) void group_points_rows_kernel(
             srel[lane * 3 + 1] = plane_xyz[64 + lane] - cq1;
             srel[lane * 3 + 2] = plane_xyz[128 + lane] - cq2;
         }
-        if (err && __any(bad) && lane == 0) atomicOr(err, 1);
+        if (err && __any(bad) && lane == 0) atomicOr(err, kIndexErrGather);
         bad = false;
         const __amdgpu_buffer_rsrc_t rs_pts = make_rsrc_uniform(points + (size_t)b * N * D, (unsigned)N * (unsigned)D * 4u);
         const __amdgpu_buffer_rsrc_t rs_out = make_rsrc_uniform(out + (size_t)q * total, total * 4u);
@@ -629,7 +629,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(48))) void grou
             ++b1;
         }
     }
-    if (err && __any(bad) && lane == 0) atomicOr(err, 1);
+    if (err && __any(bad) && lane == 0) atomicOr(err, kIndexErrGather);
 }
 
 

@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256) void sa_gather_max_kernel(int B, int N, int S,
             }
             roff = (unsigned)v * (unsigned)C1 * 4u;
         }
-        if (err && cb == 0 && __any(bad) && lane == 0) atomicOr(err, 1);
+        if (err && cb == 0 && __any(bad) && lane == 0) atomicOr(err, kIndexErrGather);
         const __amdgpu_buffer_rsrc_t rs = sa_rsrc(A + (size_t)b * N * C1, (unsigned)N * (unsigned)C1 * 4u);
         f32x4 m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
         const bool live = c < (unsigned)C1;
@@ -278,7 +278,7 @@ __global__ __launch_bounds__(256) void sa_direct_max_kernel(long long queries, i
                 best[t] = fmaxf(best[t], mx);
             }
         }
-        if (err && __any(bad) && lane == 0) atomicOr(err, 1);
+        if (err && __any(bad) && lane == 0) atomicOr(err, kIndexErrGather);
         if (hi == 0) {
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
@@ -423,7 +423,7 @@ __global__ __launch_bounds__(256) void sa_gather_act_kernel(long long queries, i
             }
             roff = (unsigned)v * (unsigned)C1 * 4u;
         }
-        if (err && __any(bad) && lane == 0) atomicOr(err, 1);
+        if (err && __any(bad) && lane == 0) atomicOr(err, kIndexErrGather);
         const __amdgpu_buffer_rsrc_t rs = sa_rsrc(A + (size_t)b * N * C1, (unsigned)N * (unsigned)C1 * 4u);
         for (unsigned c = lane * 4u; c < (unsigned)C1; c += 256u) {
             const f32x4 w0 = *(const f32x4 *)(Wxs + c), w1 = *(const f32x4 *)(Wxs + C1 + c), w2 = *(const f32x4 *)(Wxs + 2 * C1 + c);

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256, 2) void sa_mlp2_max_kernel(long long Q, int N,
             bad = true;
             v = 0;
         }
-        if (err && col0 == 0 && bad) atomicOr(err, 1);
+        if (err && col0 == 0 && bad) atomicOr(err, kIndexErrGather);
     } else {
         // group_all (pointnet2_utils.py:178-195): "query" s of a cloud owns the points s*Kp .. s*Kp + Kp-1, no centre; a short
         // last chunk repeats its first point, which a max does not see
@@ -360,7 +360,7 @@ __global__ __launch_bounds__(WM * 128, WM == 2 ? TGN_SA_SPLIT_BLOCKS : 1) void s
             bad = true;
             v = 0;
         }
-        if (err && col0 == 0 && bad) atomicOr(err, 1);
+        if (err && col0 == 0 && bad) atomicOr(err, kIndexErrGather);
     } else {
         const long long first = (q - (long long)b * S) * Kp;
         v = first + kk < N ? first + kk : first;

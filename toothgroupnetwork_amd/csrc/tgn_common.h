@@ -20,6 +20,9 @@ hipStream_t default_stream();
 // error word of the gather family for launches on `stream` of the current device (capi.hip): one word per (device, stream), so
 // that host threads driving different streams never clear or take each other's bits; nullptr if it cannot be allocated
 int *index_error_word(hipStream_t stream);
+// bits of that word: kernels latch them with atomicOr, tgn_take_index_error returns the word
+constexpr int kIndexErrGather = 1;  // the gather family (gather, group, sa, sa_mlp, edgeconv): an index outside the gathered dimension
+constexpr int kIndexErrCrop = 2;    // crop.hip, cluster.hip, tsegnet.hip: a label or a crop index out of range
 
 // Kernel-variant switches (capi.hip; include/tgn_pointops.h: tgn_set_tuning).  One table of atomics, read with a relaxed load on
 // the launch paths -- no getenv() there.  The legacy TGN_* environment names seed the table ONCE, when the library is loaded.

@@ -11,8 +11,6 @@
 
 namespace tgn {
 
-constexpr int kTsgErrBit = 2;
-
 // ---- tgn_tsg_proposals ---------------------------------------------------------------------------------------------------
 // One workgroup per scan, one lane per coarse point (m <= 1024).  The scan's first output row is the number of points kept in the
 // scans in front of it: every workgroup counts those itself from `dist` (b * m comparisons, b small), so no workgroup waits for
@@ -69,7 +67,7 @@ __global__ void __launch_bounds__(kFeatThreads) tsg_crop_features_kernel(
         bad = true;
         p = 0;
     }
-    if (bad && err) atomicOr(err, kTsgErrBit);
+    if (bad && err) atomicOr(err, kIndexErrCrop);
     const float *X = feats + (long long)b * c_stride * n + p;
     float *O = out + (long long)t * (3 + cf + 1) * k + j;
     const float x = X[0], y = X[n], z = X[2 * (long long)n];
@@ -104,7 +102,7 @@ __global__ void __launch_bounds__(kPaintThreads) tsg_paint_mark_kernel(int nscan
     const int b = crop_scan[t];
     const long long p = idx[e];
     if (b < 0 || b >= nscan || p < 0 || p >= n) {
-        if (err) atomicOr(err, kTsgErrBit);
+        if (err) atomicOr(err, kIndexErrCrop);
         return;
     }
     atomicMax(out + (long long)b * n + p, (unsigned long long)t + 1ull);

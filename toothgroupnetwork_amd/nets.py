@@ -19,10 +19,11 @@ of the fused eval paths.  Parameter names and shapes equal the reference classes
                        fused in eval mode (dgcnn.py of this package, re-exported here).
   GroupingNetworkModule  models/modules/grouping_network_module.py:7-101, tgnet_fps's network (train_configs/tgnet_fps.py): a
                        PointTransformerSeg over the scan, on-device tooth crops (crops.tooth_crops), a second PointTransformerSeg over
-                       all crops as one batch.  Without labels the centroids come from on-device clustering (cluster.py); the cbl
-                       terms stay the reference's Python.
+                       all crops as one batch.  Without labels the centroids come from on-device clustering (cluster.py, which
+                       reaches crop.hip's kNN and label means through crops.py); the cbl terms stay the reference's Python.
   TSegNetModule        models/modules/tsegnet.py:10-88 (the "tsegnet" model): TsgCentroidNet, the join on the GPU (tsegnet.py of this
-                       package: proposal filter, DBSCAN, cluster means, crops with the distance feature), TsgSegNet over the crops.
+                       package: proposal filter, DBSCAN, cluster means, crops with the distance feature; the means and the crops'
+                       kNN through crops.py's wrappers of crop.hip), TsgSegNet over the crops.
 """
 import torch
 import torch.nn as nn
@@ -275,7 +276,8 @@ class GroupingNetworkModule(nn.Module):
     Centroids: the labels' (inputs[1], the reference's path whenever len(inputs) >= 2), `centroids` given by the caller, or, with
     neither, the unlabelled path of grouping_network_module.py:57-69: per scan, the first stage's class argmax, the moved points xyz +
     offset_1, cluster.get_clustering_labels on them (DBSCAN, the PCA split test, MeanShift, the noise vote -- HIP kernels where the
-    reference runs sklearn) and the float32 mean of the moved foreground points of every cluster, ascending.  The reference's
+    reference runs sklearn) and the float32 mean of the moved foreground points of every cluster, ascending
+    (cluster.cluster_centroids, over crops.label_centroids).  The reference's
     unlabelled path works for B == 1 only (it indexes inputs[b_idx] and its offset head runs for B == 1); here every scan of a batch
     is clustered on its own, and offset_1 is then returned for every B.  The contrastive-boundary terms cbl_loss_1 / cbl_loss_2 of
     training (the reference's criterion, heads.py:62-253) are left out, as for PointTransformerSeg, so `test` changes nothing here:
@@ -333,7 +335,8 @@ class TSegNetModule(nn.Module):
     points, `seg_module` (TsgSegNet) segments a 3072-point crop around each centre.  Same constructor argument, attribute names and
     state_dict as the reference's class, so its checkpoints load with strict=True.  The join between the stages -- the proposal
     filter, DBSCAN(0.05, 3), the cluster means, the KDTree crops, the gathers and the distance feature -- is host work with a device
-    round trip at every step in the reference; here it is tsegnet.py's HIP kernels.
+    round trip at every step in the reference; here it is tsegnet.py's HIP kernels (tsegnet.hip, and cluster.py's DBSCAN and crops.py's
+    label means and kNN for the steps it shares with tgnet_fps).
 
     Like the reference, at most 8 centres are kept, chosen by `np.random.permutation(T)[:8]` on numpy's GLOBAL generator: the same
     `np.random.seed` gives the same crops as the reference (one call per scan, in scan order).  The reference is only meaningful for

@@ -1,11 +1,11 @@
 """The join between the two stages of tsegnet (models/modules/tsegnet.py:57-81) and the painting loop of its inference pipeline
 (inference_pipelines/inference_pipeline_tsegnet.py:60-66) on the GPU.  The reference does every step on the host -- numpy filters,
 sklearn's DBSCAN, a KDTree over the whole scan, python gathers, a python loop over the crops -- with a device round trip at each;
-here (csrc/tsegnet.hip, cluster.hip, crop.hip; include/tgn_pointops.h):
+here (csrc/tsegnet.hip; cluster.hip through cluster.py; crop.hip through crops.py's wrappers, operand builders and limits):
 
   centroid_proposals  (l3_xyz + offset)[dist < 0.3] in point order                      tgn_tsg_proposals
-  cluster_centers     DBSCAN(0.05, 3) on them, the float32 mean of every cluster        tgn_dbscan, tgn_label_centroids
-  crop_features       the k nearest scan points of every centre and the segmentation    tgn_crop_knn, tgn_tsg_crop_features
+  cluster_centers     DBSCAN(0.05, 3) on them, the float32 mean of every cluster        cluster.dbscan_counts, crops.label_centroids
+  crop_features       the k nearest scan points of every centre and the segmentation    crops.crop_knn, tgn_tsg_crop_features
                       module's 3 + Cf + 1 input channels (xyz, features, distance feature)
   paint_labels        every scan point takes the tooth id of the last crop that masks it   tgn_tsg_paint
 
@@ -16,15 +16,12 @@ centres and indices back on the same stretch.
 import numpy as np
 import torch
 
-from . import _lib, cluster as _cluster
+from . import _lib, cluster as _cluster, crops as _crops
 
 THRESHOLD = 0.3                    # tsegnet.py:58
 EPS, MIN_SAMPLES = 0.05, 3         # tsegnet.py:59
 CROP_K = 3072                      # tsegnet.py:73
 MAX_M = 1024                       # tgn_tsg_proposals: one workgroup per scan
-MAX_K = 4096                       # tgn_crop_knn
-MAX_CLUSTERS = 64                  # tgn_label_centroids
-_INDEX_ERROR = 2                   # bit 1 of the stream's error word
 
 
 def _f32(t, what, shape_text, ok):
@@ -85,29 +82,15 @@ def cluster_centers(moved, counts, eps=EPS, min_samples=MIN_SAMPLES):
     for b, t in enumerate(ncl):
         if t == 0:
             raise ValueError(f"tsegnet: DBSCAN found no cluster among the {counts[b]} proposals of scan {b}")
-        if t > MAX_CLUSTERS:
-            raise ValueError(f"tsegnet: {t} clusters in scan {b}: at most {MAX_CLUSTERS} are supported (tgn_label_centroids)")
-    L, st, out, lo = _lib.lib(), _lib.stream(), [], 0
-    for hi, t in zip(ends, ncl):
-        pts = moved[lo:hi].t().contiguous()                       # (3, n_b) channel-first; noise (-1) is skipped by the kernel
-        lab = labels[lo:hi].contiguous()
-        cnt = torch.empty(1, t, dtype=torch.int32, device=moved.device)
-        cent = torch.empty(1, t, 3, dtype=torch.float32, device=moved.device)
-        _lib.check(L.tgn_label_centroids(1, hi - lo, 3, _lib.ptr(pts), _lib.ptr(lab), t, _lib.ptr(cnt), _lib.ptr(cent), st),
-                   "tgn_label_centroids")
+        if t > _crops.MAX_CLUSTERS:
+            raise ValueError(f"tsegnet: {t} clusters in scan {b}: at most {_crops.MAX_CLUSTERS} are supported (tgn_label_centroids)")
+    out, lo = [], 0
+    for hi, t in zip(ends, ncl):                                  # one launch per scan
+        pts = moved[lo:hi].t().contiguous()[None]                 # (1, 3, n_b) channel-first; noise (-1) is skipped by the kernel
+        _, cent = _crops.label_centroids(pts, labels[None, lo:hi].contiguous(), t)
         out.append(cent[0])
         lo = hi
     return out
-
-
-def _centres(centres, B, dev):
-    parts = []
-    for c in centres:
-        c = c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(c), dtype=np.float32))
-        if c.dim() != 2 or c.shape[1] != 3:
-            raise ValueError(f"every scan's centres must be (T_b, 3), got {tuple(c.shape)}")
-        parts.append(c.detach().to(dev, torch.float32))
-    return parts
 
 
 def crop_features(feats, l0_points, centres, k=CROP_K, labels=None):
@@ -132,40 +115,25 @@ def crop_features(feats, l0_points, centres, k=CROP_K, labels=None):
         raise ValueError(f"l0_points must be ({B}, Cf, {N}), got {tuple(l0_points.shape)}")
     if feats.dtype != torch.float32 or l0_points.dtype != torch.float32:
         raise TypeError(f"feats and l0_points must be float32, got {feats.dtype} and {l0_points.dtype}")
-    k = int(k)
-    if not 1 <= k <= min(N, MAX_K):
-        raise ValueError(f"k = {k} must satisfy 1 <= k <= min(N, {MAX_K}) = {min(N, MAX_K)} (KDTree.query raises for k > N too)")
+    k = _crops.check_k(k, N)
     dev = feats.device
-    lab = None
-    if labels is not None:
-        if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64:
-            raise TypeError("labels must be an int64 torch tensor")
-        if labels.dim() == 3 and labels.shape[1] == 1:
-            labels = labels[:, 0]
-        if tuple(labels.shape) != (B, N):
-            raise ValueError(f"labels must be (B, N) or (B, 1, N) = ({B}, {N}), got {tuple(labels.shape)}")
-        lab = labels.contiguous()
-    if not isinstance(centres, (list, tuple)) or len(centres) != B:
-        raise ValueError(f"centres must be a list of {B} per-scan (T_b, 3) arrays or tensors")
+    lab = _crops.labels_2d(labels, B, N, (torch.int64,)) if labels is not None else None
+    cent, scan, per_scan = _crops.stack_centres(centres, B, dev, "centres")
     _lib.require_cuda(feats, l0_points, lab)
-    parts = _centres(centres, B, dev)
-    per_scan = [int(p.shape[0]) for p in parts]
     T = sum(per_scan)
     if T == 0:
         raise ValueError("crop_features: no centre in the batch")
-    cent = torch.cat(parts).contiguous()
-    scan = torch.from_numpy(np.repeat(np.arange(B, dtype=np.int32), per_scan)).to(dev, non_blocking=True)
+    cent = cent.detach()                                          # the kernels read the centres; no gradient flows to them
     x = feats.detach().contiguous()
     differentiable = torch.is_grad_enabled() and l0_points.requires_grad
     f = l0_points.detach().contiguous()
     Cf = 0 if differentiable else int(f.shape[1])
-    L, st = _lib.lib(), _lib.stream()
-    idx = torch.empty(T, k, dtype=torch.int64, device=dev)
+    idx = _crops.crop_knn(x, scan, cent, k)
     out = torch.empty(T, 3 + Cf + 1, k, dtype=torch.float32, device=dev)
     crop_lab = torch.empty(T, 1, k, dtype=torch.int64, device=dev) if lab is not None else None
-    _lib.check(L.tgn_crop_knn(B, N, C, _lib.ptr(x), T, _lib.ptr(scan), _lib.ptr(cent), k, _lib.ptr(idx), st), "tgn_crop_knn")
-    _lib.check(L.tgn_tsg_crop_features(B, N, C, Cf, T, k, _lib.ptr(x), _lib.ptr(f) if Cf else None, _lib.ptr(scan), _lib.ptr(cent),
-                                       _lib.ptr(idx), _lib.ptr(lab), _lib.ptr(out), _lib.ptr(crop_lab), st), "tgn_tsg_crop_features")
+    _lib.check(_lib.lib().tgn_tsg_crop_features(B, N, C, Cf, T, k, _lib.ptr(x), _lib.ptr(f) if Cf else None, _lib.ptr(scan),
+                                                _lib.ptr(cent), _lib.ptr(idx), _lib.ptr(lab), _lib.ptr(out), _lib.ptr(crop_lab),
+                                                _lib.stream()), "tgn_tsg_crop_features")
     if differentiable:
         flat = (scan.to(torch.int64)[:, None] * N + idx).reshape(-1)                           # rows of the (B * N, Cf) features
         rows = l0_points.permute(0, 2, 1).reshape(B * N, -1).index_select(0, flat)
@@ -205,12 +173,12 @@ def paint_labels(nn_crop_indexes, pd_2, id_pred, n_points):
     idx = torch.cat(list(nn_crop_indexes)).contiguous()
     mask = (torch.sigmoid(pd_2.detach()) > 0.5).to(torch.uint8).contiguous()
     ids = id_pred.detach().argmax(dim=1).to(torch.int64).contiguous()
-    scan = torch.from_numpy(np.repeat(np.arange(B, dtype=np.int32), per_scan)).to(dev, non_blocking=True)
+    scan = _crops.scan_ids(per_scan, dev)
     out = torch.empty(B, n_points, dtype=torch.int64, device=dev)
     L, st = _lib.lib(), _lib.stream()
     _lib.check(L.tgn_clear_index_error(st), "tgn_clear_index_error")
     _lib.check(L.tgn_tsg_paint(B, n_points, T, k, _lib.ptr(scan), _lib.ptr(idx), _lib.ptr(mask), _lib.ptr(ids), _lib.ptr(out), st),
                "tgn_tsg_paint")
-    if L.tgn_take_index_error(st) & _INDEX_ERROR:
+    if L.tgn_take_index_error(st) & _lib.INDEX_ERROR_CROP:
         raise IndexError(f"paint_labels: a crop index outside [0, {n_points})")
     return out
