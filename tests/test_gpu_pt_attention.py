@@ -46,12 +46,20 @@ def test_fused_layer_reproduces_the_reference_layer(dev, golden_r2):
     close(y.cpu().numpy(), g["pt_y"], "fused layer vs reference layer", tol=2e-5)
 
 
-@pytest.mark.parametrize("n,c,ns", [(24000, 32, 36), (6000, 64, 24), (1500, 128, 24), (375, 256, 24), (93, 512, 24), (500, 32, 5),
-                                     (333, 64, 64)])
-def test_fused_attention_vs_oracle(dev, oracle, n, c, ns):
+@pytest.mark.parametrize("n,c,ns,fused", [pytest.param(24000, 32, 36, True, id="24000-32-36"),
+                                          pytest.param(6000, 64, 24, True, id="6000-64-24"),
+                                          pytest.param(1500, 128, 24, True, id="1500-128-24"),
+                                          pytest.param(375, 256, 24, False, id="375-256-24-deep-composition"),
+                                          pytest.param(93, 512, 24, False, id="93-512-24-deep-composition"),
+                                          pytest.param(500, 32, 5, True, id="500-32-5"),
+                                          pytest.param(333, 64, 64, True, id="333-64-64")])
+def test_fused_attention_vs_oracle(dev, oracle, monkeypatch, n, c, ns, fused):
     """every stage width of the tgnet_fps U-Net (enc1 ... enc5: c = 32 ... 512, share_planes 8), enc1 at full size
-    (24 000 points, 36 neighbours): the fused kernel against the float64 restatement, eval mode; and the training-path
-    composition (fused softmax + aggregation tail) against the same."""
+    (24 000 points, 36 neighbours): the eval-mode layer against the float64 restatement; and the training-path
+    composition (fused softmax + aggregation tail) against the same.  The eval-mode layer runs the fused kernel for c <= 128
+    only: the two deep stages (c * c / 8 >= 8192 below 4096 points) take the torch composition there too
+    (PointTransformerLayer.forward), and a spy asserts which path each case took.  The kernel itself at c = 256 and c = 512
+    is tested in tests/test_gpu_pt_attention_bounds.py."""
     from toothgroupnetwork_amd import point_transformer as PT, pointops as P, synth
     xyz = synth.arch_cloud(n, seed=n % 89, with_normals=False)
     off = np.array([n], np.int32)
@@ -60,8 +68,13 @@ def test_fused_attention_vs_oracle(dev, oracle, n, c, ns):
     layer = PT.PointTransformerLayer(c, c, 8, ns).to(dev).eval()
     _randomise_bn(layer, c)
     tx, tp, to = T(x, dev), T(xyz, dev), T(off, dev)
+    calls = {"fused": 0, "tail": 0}
+    real_fused, real_tail = PT.pt_attention, PT.pt_softmax_aggregate
+    monkeypatch.setattr(PT, "pt_attention", lambda *a, **k: calls.__setitem__("fused", calls["fused"] + 1) or real_fused(*a, **k))
+    monkeypatch.setattr(PT, "pt_softmax_aggregate", lambda *a, **k: calls.__setitem__("tail", calls["tail"] + 1) or real_tail(*a, **k))
     with torch.no_grad():
         y = layer([tp, tx, to])
+        assert calls == ({"fused": 1, "tail": 0} if fused else {"fused": 0, "tail": 1}), calls
         xq, xk, xv = layer.linear_q(tx), layer.linear_k(tx), layer.linear_v(tx)
         idx, _ = P.knnquery(ns, tp, tp, to, to)
     sd = {k: v.cpu().numpy() for k, v in layer.state_dict().items()}
@@ -69,7 +82,7 @@ def test_fused_attention_vs_oracle(dev, oracle, n, c, ns):
     close(y.cpu().numpy(), want, "fused")
     if n <= 6000:
         y2 = layer([tp, tx.clone().requires_grad_(True), to])          # autograd on: the composition with the fused tail
-        assert y2.requires_grad
+        assert y2.requires_grad and calls["fused"] == (1 if fused else 0)
         close(y2.detach().cpu().numpy(), want, "training-path composition")
 
 

@@ -97,9 +97,12 @@ __global__ __launch_bounds__(256) void pt_attention_fwd_kernel(int n, int nsampl
         for (int g = 0; g < G; ++g) hid[g] = fmaxf(lg[g] + P.bw1[g], 0.0f);
 #pragma unroll
         for (int g = 0; g < G; ++g) {
-            float a = P.bw2[g];
+            // the bias goes on LAST (as in pass 1): a sum started from it rounds every partial at the bias's magnitude, and a
+            // weight channel with a large bias then loses G roundings of it where one is due
+            float a = 0.0f;
 #pragma unroll
             for (int g2 = 0; g2 < G; ++g2) a += P.Ww2[g * G + g2] * hid[g2];
+            a += P.bw2[g];
             // softmax over the neighbours (= over the lanes), blocks.py:41
             const float lgt = act ? a : -INFINITY;
             const float mx = wave_max_f32x(lgt);
