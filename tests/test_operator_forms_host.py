@@ -1,0 +1,140 @@
+"""CPU: the operator table of tests/operator_forms.py is complete and its form builders do what they say.
+
+Every public callable of toothgroupnetwork_amd.pointops that the reference's pointops.py defines has a row, and so has every
+function or class of pointops, pointnet2_utils, dgcnn, crops, cluster, tsegnet and point_transformer whose source reaches
+``ptr(`` (the raw device pointer of a tensor) -- or it is listed in INTERNAL with the row that covers it.  A wrapper added later
+without a row fails here.
+"""
+import importlib
+import inspect
+import re
+
+import pytest
+import torch
+
+import operator_forms as T
+
+
+def _reaches_ptr(module):
+    mod = importlib.import_module("toothgroupnetwork_amd." + module)
+    found = []
+    for name, obj in vars(mod).items():
+        if (inspect.isfunction(obj) or inspect.isclass(obj)) and getattr(obj, "__module__", None) == mod.__name__:
+            try:
+                source = inspect.getsource(obj)
+            except (OSError, TypeError):         # a class made by a call (a namedtuple): no source, no pointer
+                continue
+            if re.search(r"\bptr\(", source):
+                found.append(name)
+    return mod, found
+
+
+@pytest.mark.parametrize("module", T.SWEPT_MODULES)
+def test_every_wrapper_that_takes_a_raw_pointer_has_a_row(module):
+    mod, found = _reaches_ptr(module)
+    assert found, f"{module}: no function reaches ptr( -- has the binding been renamed?"
+    covered = T.covered_names(module)
+    missing = [n for n in found if n not in covered]
+    assert not missing, f"{module}: {missing} reach _lib.ptr( but have neither a row in tests/operator_forms.py nor an INTERNAL entry"
+    stale = [n for n in covered if not hasattr(mod, n)]
+    assert not stale, f"{module}: the table names {stale}, which the module does not define"
+
+
+def test_every_reference_pointops_name_has_a_row():
+    from toothgroupnetwork_amd import pointops
+    covered = T.covered_names("pointops")
+    for name in T.REFERENCE_POINTOPS_NAMES:
+        assert callable(getattr(pointops, name)), name
+        assert name in covered, f"pointops.{name} has no row"
+
+
+def test_internal_entries_point_at_rows():
+    rows = {r["name"] for r in T.ROWS}
+    for name, (module, covering, why) in T.INTERNAL.items():
+        assert module in T.SWEPT_MODULES and covering in rows and why, name
+
+
+def test_rows_are_well_formed():
+    names = [r["name"] for r in T.ROWS]
+    assert len(names) == len(set(names))
+    forms = set(T.FLOAT_LAYOUTS) | set(T.FLOAT_DTYPES) | set(T.INDEX_DTYPES) | {"expanded", "strided"}
+    for r in T.ROWS:
+        assert r["module"] in T.SWEPT_MODULES and r["outputs"] and (r["floats"] or r["ints"]), r["name"]
+        assert set(r.get("diff", ())) <= set(r["floats"]), r["name"]
+        assert (r.get("grad") in ("exact", "bound")) == bool(r.get("diff")), r["name"]
+        for key, outcome in r.get("expect", {}).items():
+            arg, _, form = key.rpartition(":")
+            assert outcome in ("equal", "raises") and form in forms and (not arg or arg in r["floats"] + r["ints"]), (r["name"], key)
+
+
+def test_form_builders():
+    """the probes hold the baseline's values, are what their name says, and a probe narrower than the baseline sits in a buffer of
+    twice the bytes a read in the baseline's dtype takes"""
+    t = T.q16(T.gen_for("forms"), 7, 5)
+    assert bool((t * 16 == (t * 16).round()).all()) and float(t.abs().max()) <= 4.0
+    for form in T.FLOAT_LAYOUTS + tuple(T.FLOAT_DTYPES) + ("expanded",):
+        v = T.float_form(t, form)
+        if form == "f32":
+            assert v is None
+            continue
+        assert v.shape == t.shape
+        if form != "expanded":
+            assert torch.equal(v.double(), t.double()), form
+        if form == "offset":
+            assert v.is_contiguous() and v.storage_offset() == 1
+        elif form in ("strided_t", "strided_col"):
+            assert not v.is_contiguous()
+        elif form == "expanded":
+            assert v.stride(0) == 0 and torch.equal(v[3], t[0])
+        elif form in ("f16", "bf16"):
+            assert v.is_contiguous() and v.untyped_storage().nbytes() >= 2 * 4 * t.numel()
+    assert T.float_form(torch.zeros(5), "strided_t") is None
+    i = torch.arange(12).view(3, 4)
+    for form in ("i32", "strided"):
+        v = T.index_form(i, form)
+        assert torch.equal(v.long(), i) and (form != "strided" or not v.is_contiguous())
+    assert T.index_form(i, "i64") is None and T.index_form(i, "i32").untyped_storage().nbytes() >= 2 * 8 * i.numel()
+    d = t.double()                                                # a float64 baseline (mean_shift): float32 is a narrow probe too
+    for form, size in (("f32", 4), ("f16", 2), ("bf16", 2)):
+        v = T.float_form(d, form)
+        assert v.element_size() == size and torch.equal(v.double(), d) and v.untyped_storage().nbytes() >= 2 * 8 * d.numel(), form
+    assert T.float_form(d, "f64") is None and T.float_form(d, "offset").data_ptr() % 16 == 8
+    o = torch.tensor([3, 7], dtype=torch.int32)
+    assert T.index_form(o, "i64").dtype == torch.int64 and not T.index_form(o, "strided").is_contiguous()
+
+
+def test_normalisers_of_the_packed_operators():
+    """pointops._f32c / _idx32c on the CPU: what they return, and that a non-floating feature tensor is a TypeError"""
+    from toothgroupnetwork_amd import pointops as P
+    t = T.q16(T.gen_for("norm"), 6, 4)
+    assert P._f32c(t, "x") is t
+    for form in ("offset", "strided_t", "strided_col", "f64", "f16", "bf16"):
+        v = P._f32c(T.float_form(t, form), "x")
+        assert v.dtype == torch.float32 and v.is_contiguous() and torch.equal(v, t)
+    with pytest.raises(TypeError, match="feat"):
+        P._f32c(torch.zeros(3, 2, dtype=torch.int64), "feat")
+    with pytest.raises(TypeError, match="idx"):
+        P._idx32c(torch.zeros(3, 2), "idx")
+    i = torch.arange(6).view(3, 2)
+    assert P._idx32c(i, "idx").dtype == torch.int32 and P._idx32c(T.index_form(i, "strided"), "idx").is_contiguous()
+    with pytest.raises(ValueError, match="input"):
+        P._packed(t.double(), "input")
+    with pytest.raises(ValueError, match="input"):
+        P._packed(t.t(), "input")
+
+
+def test_crop_host_layer_refuses_operands_it_would_misread():
+    """crops.crop_knn and crops.label_centroids pass raw pointers: another dtype or a strided view raises before the library is
+    touched (so this runs without a GPU)"""
+    from toothgroupnetwork_amd import crops
+    feats, scan, cent = torch.zeros(1, 3, 8), torch.zeros(2, dtype=torch.int32), torch.zeros(2, 3)
+    labels = torch.zeros(1, 8, dtype=torch.int64)
+    for bad, what, err in ((dict(feats=feats.double()), "feats", TypeError), (dict(feats=feats.transpose(1, 2).contiguous().transpose(1, 2)), "feats", ValueError),
+                           (dict(scan=scan.long()), "scan", TypeError), (dict(cent=cent.half()), "cent", TypeError),
+                           (dict(cent=torch.zeros(3, 2).t()), "cent", ValueError)):
+        with pytest.raises(err, match=what):
+            crops.crop_knn(**dict(dict(feats=feats, scan=scan, cent=cent, k=4), **bad))
+    for bad, what, err in ((dict(feats=feats.half()), "feats", TypeError), (dict(labels=labels.int()), "labels", TypeError),
+                           (dict(labels=torch.zeros(1, 16, dtype=torch.int64)[:, ::2]), "labels", ValueError)):
+        with pytest.raises(err, match=what):
+            crops.label_centroids(**dict(dict(feats=feats, labels=labels, nlab=4), **bad))

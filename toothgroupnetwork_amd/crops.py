@@ -61,6 +61,14 @@ def stack_centres(centres, B, dev, what):
     return torch.cat(parts).contiguous(), scan_ids(per_scan, dev), per_scan
 
 
+def _operand(t, what, dtype):
+    """crop_knn and label_centroids hand raw pointers to the kernels: their operands are `dtype` and contiguous, or it is an error."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+        raise TypeError(f"{what} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what} must be contiguous, got strides {tuple(t.stride())}")
+
+
 def check_k(k, N):
     """k as an int within tgn_crop_knn's range for scans of N points; callers with GPU work ahead of crop_knn ask before that work."""
     k = int(k)
@@ -72,6 +80,7 @@ def check_k(k, N):
 def crop_knn(feats, scan, cent, k):
     """feats (B, C >= 3, N) float32 contiguous with xyz in channels 0..2, scan (T,) int32 and cent (T, 3) float32 (stack_centres) ->
     idx (T, k) int64: per centre the k nearest points of its scan, ascending (float64 squared distance, index).  No synchronisation."""
+    _operand(feats, "feats", torch.float32), _operand(scan, "scan", torch.int32), _operand(cent, "cent", torch.float32)
     B, C, N = feats.shape
     k = check_k(k, N)
     T = cent.shape[0]
@@ -85,6 +94,7 @@ def label_centroids(feats, labels, nlab):
     """feats (B, C >= 3, N) float32 and labels (B, N) int64, contiguous -> (counts (B, nlab) int32, cent (B, nlab, 3) float32): per scan
     and label 0..nlab-1 its point count and float32 mean, bit-equal to numpy's xyz[label == t].mean(axis=0).  -1 is skipped; another label
     outside [0, nlab) latches _lib.INDEX_ERROR_CROP, which is neither cleared nor read here.  No synchronisation."""
+    _operand(feats, "feats", torch.float32), _operand(labels, "labels", torch.int64)
     B, C, N = feats.shape
     counts = torch.empty(B, nlab, dtype=torch.int32, device=feats.device)
     cent = torch.empty(B, nlab, 3, dtype=torch.float32, device=feats.device)

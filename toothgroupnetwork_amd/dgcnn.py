@@ -78,11 +78,21 @@ def edgeconv_max(x, idx, first, second=None, out=None, coff=0):
     second = _second_layer(...) or None (one-layer level).  Writes max_j lrelu(...) into out[:, coff:coff + 64] of a (B, Ctot, N)
     tensor (allocated (B, 64, N) when None) and returns out.  The per-point transforms P = Wa' x, Q = (Wb' - Wa') x + t are GEMMs."""
     require_cuda(x, idx)
+    if not x.is_floating_point():
+        raise TypeError(f"edgeconv_max: x must be a floating-point tensor, got {x.dtype}")
     B, C, N = x.shape
     K = idx.shape[-1]
     WaT, WdT, t1 = first
     if WaT.shape != (C, 64):
         raise ValueError(f"edgeconv_max: the fused kernels take 64 output channels from C = {C} inputs, got {tuple(WaT.shape)}")
+    if out is not None:
+        if out.dtype != torch.float32 or out.device != x.device:
+            raise TypeError(f"edgeconv_max: out must be float32 on {x.device}, got {out.dtype} on {out.device}")
+        if out.dim() != 3 or out.shape[0] != B or out.shape[2] != N or not 0 <= coff <= out.shape[1] - 64:
+            raise ValueError(f"edgeconv_max: out must be ({B}, Ctot, {N}) with 0 <= coff <= Ctot - 64, got {tuple(out.shape)}, coff {coff}")
+        if out.stride(2) != 1 or out.stride(1) != N:
+            raise ValueError("edgeconv_max: out must be (B, Ctot, N) with rows of N contiguous floats")
+    x = (x if x.dtype == torch.float32 else x.float()).contiguous()   # one layout: the GEMMs below round by the layout they read
     xt = x.transpose(1, 2)                              # (B, N, C) view; the GEMMs read it in place
     P = torch.matmul(xt, WaT)                           # (B, N, 64), contiguous
     Q = torch.matmul(xt, WdT).add_(t1)
@@ -91,13 +101,11 @@ def edgeconv_max(x, idx, first, second=None, out=None, coff=0):
         idx = idx.long()
     if out is None:
         out, coff = torch.empty(B, 64, N, dtype=torch.float32, device=x.device), 0
-    if out.stride(2) != 1 or out.stride(1) != N:
-        raise ValueError("edgeconv_max: out must be (B, Ctot, N) with rows of N contiguous floats")
     _lib.begin_index_check()
     if second is None:
         check(lib().tgn_edgeconv1_max(B, N, K, ptr(P), ptr(Q), ptr(idx), ptr(out), out.stride(0), coff, stream()), "edgeconv1_max")
     else:
-        W2, b2 = second
+        W2, b2 = (t.float().contiguous() for t in second)
         check(lib().tgn_edgeconv2_max(B, N, K, ptr(P), ptr(Q), ptr(idx), ptr(W2), ptr(b2), ptr(out), out.stride(0), coff, stream()),
               "edgeconv2_max")
     _lib.raise_on_index_error("DGCNN EdgeConv")

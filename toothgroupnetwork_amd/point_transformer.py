@@ -38,9 +38,11 @@ class _SoftmaxAggregate(Function):
     @staticmethod
     @_fwd
     def forward(ctx, x_v, p_r, logit, idx):
+        for t, what in ((x_v, "x_v"), (p_r, "p_r"), (logit, "logit")):
+            pointops._packed(t, what)
+        pointops._packed_idx(idx, "idx")
         n, nsample, c = p_r.shape
         g = logit.shape[2]
-        x_v, p_r, logit = x_v.contiguous(), p_r.contiguous(), logit.contiguous()
         sm = torch.empty(n, nsample, g, dtype=torch.float32, device=x_v.device)
         out = torch.empty(n, c, dtype=torch.float32, device=x_v.device)
         check(lib().tgn_pt_softmax_aggregate_forward(n, nsample, c, g, ptr(x_v), ptr(p_r), ptr(logit), ptr(idx), ptr(sm), ptr(out),
@@ -67,7 +69,19 @@ def pt_softmax_aggregate(x_v, p_r, logit, idx):
     """x_v (n_v, c) value rows, p_r (n, nsample, c) position encodings, logit (n, nsample, c // share_planes) attention
     logits, idx (n, nsample) int32 neighbour rows -> (n, c).  Differentiable w.r.t. x_v, p_r and logit."""
     _lib.require_cuda(x_v, p_r, logit, idx)
-    return _SoftmaxAggregate.apply(x_v, p_r, logit, idx.to(torch.int32).contiguous())
+    x_v, p_r, logit = pointops._f32c(x_v, "x_v"), pointops._f32c(p_r, "p_r"), pointops._f32c(logit, "logit")
+    idx = pointops._idx32c(idx, "idx")
+    if idx.dim() != 2:
+        raise ValueError(f"idx must be (n, nsample), got {tuple(idx.shape)}")
+    n, nsample = idx.shape
+    if p_r.dim() != 3 or tuple(p_r.shape[:2]) != (n, nsample):
+        raise ValueError(f"p_r must be ({n}, {nsample}, c) like idx ({n}, {nsample}), got {tuple(p_r.shape)}")
+    c = p_r.shape[2]
+    if x_v.dim() != 2 or x_v.shape[1] != c:
+        raise ValueError(f"x_v must be (n_v, {c}) like p_r's channels, got {tuple(x_v.shape)}")
+    if logit.dim() != 3 or tuple(logit.shape[:2]) != (n, nsample) or logit.shape[2] < 1 or c % logit.shape[2]:
+        raise ValueError(f"logit must be ({n}, {nsample}, g) with g dividing c = {c}, got {tuple(logit.shape)}")
+    return _SoftmaxAggregate.apply(x_v, p_r, logit, idx)
 
 
 class _LinearSplitK(Function):
@@ -181,10 +195,13 @@ def _plain_batchnorm(bn):
 
 
 def bn_rows(bn, x, relu=False):
-    """[relu](bn(x)) for x (rows, C): the fused kernels in training mode on fp32 CUDA rows, the module otherwise."""
-    if (BN_ROWS and bn.training and _plain_batchnorm(bn) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[0] >= 2 and x.shape[1] <= 1024
-            and bn.affine and bn.momentum is not None and x.is_contiguous() and not torch.is_autocast_enabled()):
-        return _BNRows.apply(x, bn.weight, bn.bias, bn, relu)
+    """[relu](bn(x)) for x (rows, C): the fused kernels for a plain fp32 BatchNorm1d in training mode on CUDA rows (x of any floating
+    dtype and layout is read as fp32, the result is fp32), the module otherwise (eval mode, autocast, a non-fp32 module)."""
+    if (BN_ROWS and bn.training and _plain_batchnorm(bn) and x.is_cuda and x.is_floating_point() and x.dim() == 2 and x.shape[0] >= 2
+            and x.shape[1] <= 1024 and bn.affine and bn.momentum is not None and bn.weight.dtype == torch.float32
+            and not torch.is_autocast_enabled()):
+        # any floating dtype and layout of x: cast and packed out here, so that autograd hands back x's own dtype (an fp32 module: fp32 out)
+        return _BNRows.apply(pointops._f32c(x, "x"), bn.weight, bn.bias, bn, relu)
     y = bn(x)
     return F.relu(y) if relu else y
 
@@ -283,7 +300,20 @@ def _fold_pt_layer(lp0, bnp, lp3, bnw0, lw2, bnw3, lw5):
 def pt_attention(p, x_q, x_k, x_v, idx, params, post=None):
     """The fused eval-mode layer: p (n,3), x_q/x_k/x_v (n,c), idx (n,nsample) int32 -> (n,c).
     post = (scale, shift): relu(out * scale + shift) on the way out (the block's bn2 + ReLU, folded)."""
+    _lib.require_cuda(p, x_q, x_k, x_v, idx)
+    p, x_q, x_k, x_v = (pointops._f32c(t.detach(), what) for t, what in ((p, "p"), (x_q, "x_q"), (x_k, "x_k"), (x_v, "x_v")))
+    # the kernel takes 16-byte vector loads of the key and value rows and its launcher refuses other pointers: a packed view that
+    # starts off that grid (buf[1:], a row slice of a wider batch) is copied to a fresh allocation
+    x_k, x_v = (t if t.data_ptr() % 16 == 0 else t.clone() for t in (x_k, x_v))
+    idx = pointops._idx32c(idx, "idx")
+    if x_q.dim() != 2 or idx.dim() != 2 or idx.shape[0] != x_q.shape[0]:
+        raise ValueError(f"x_q must be (n, c) and idx (n, nsample), got {tuple(x_q.shape)} and {tuple(idx.shape)}")
     n, c = x_q.shape
+    if tuple(p.shape) != (n, 3):
+        raise ValueError(f"p must be ({n}, 3) like idx's rows, got {tuple(p.shape)}")
+    for t, what in ((x_k, "x_k"), (x_v, "x_v")):
+        if tuple(t.shape) != (n, c):
+            raise ValueError(f"{what} must be ({n}, {c}) like x_q, got {tuple(t.shape)}")
     nsample = idx.shape[1]
     g = params["Ww2"].shape[0]
     out = torch.empty(n, c, dtype=torch.float32, device=x_q.device)
@@ -334,7 +364,7 @@ class PointTransformerLayer(nn.Module):
             if post_bn is not None:
                 post = _derived.cached(post_bn, "scale_shift", _derived.sources(post_bn), None,
                                        lambda: tuple(t.contiguous() for t in _bn_scale_shift(post_bn)))
-            return pt_attention(p.contiguous(), x_q.contiguous(), x_k.contiguous(), x_v.contiguous(), idx, fold_pt_layer(self), post)
+            return pt_attention(p, x_q, x_k, x_v, idx, fold_pt_layer(self), post)
         # training: the reference's composition with the softmax + weighted sum as one differentiable kernel pair.
         # Under autocast this section stays in fp32: it is bandwidth-bound over (n, nsample, c) tensors that the gather
         # kernels produce and consume as fp32, its learned layers are 3- to c/8-wide, and letting autocast flip every other
@@ -342,7 +372,8 @@ class PointTransformerLayer(nn.Module):
         with torch.autocast("cuda", enabled=False):
             x_q, x_k, x_v = x_q.float(), x_k.float(), x_v.float()
             # (idx comes from this package's kNN: no index check, i.e. no host round trip per layer)
-            x_kg = pointops._QueryGroup.apply(p, p, x_k.contiguous(), idx, True)                            # (n, nsample, 3+c)
+            pc = pointops._f32c(p, "p")
+            x_kg = pointops._QueryGroup.apply(pc, pc, x_k.contiguous(), idx, True)                            # (n, nsample, 3+c)
             p_r, x_kg = x_kg[:, :, 0:3], x_kg[:, :, 3:]
             p_r = _mlp_rows(self.linear_p, p_r)
             w = _mlp_rows(self.linear_w, x_kg - x_q.unsqueeze(1) + p_r)
@@ -403,7 +434,7 @@ class TransitionDown(nn.Module):
             Wt, Wxyz, t = _derived.cached(self, "down", _derived.sources(self.linear, self.bn), c, fold)
             A = torch.empty(n, C1, dtype=torch.float32, device=x.device)
             L = lib()
-            check(L.tgn_sa_point_transform(n, c, C1, ptr(p.contiguous()), ptr(x.contiguous()), ptr(Wt), ptr(A), stream()),
+            check(L.tgn_sa_point_transform(n, c, C1, ptr(pointops._f32c(p, "p")), ptr(x.contiguous()), ptr(Wt), ptr(A), stream()),
                   "sa_point_transform")
             out = torch.empty(m, C1, dtype=torch.float32, device=x.device)
             check(L.tgn_sa_gather_max(1, n, m, self.nsample, C1, ptr(A), ptr(n_p), ptr(Wxyz), ptr(t),

@@ -53,6 +53,21 @@ def _f32c(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _idxc(idx):
+    """Index tensors reach the kernels as packed int64 or int32 (a flag tells which); any other integer width is widened."""
+    if idx.dtype not in (torch.int64, torch.int32):
+        idx = idx.long()
+    return idx if idx.is_contiguous() else idx.contiguous()
+
+
+def _sa_operands(xyz, new_xyz, points, idx):
+    """The tensor arguments of the fused set-abstraction entries as the kernels read them: packed fp32 rows, packed indices.  The
+    modules pass them in that form already (then nothing is copied); a direct caller may pass any floating dtype or layout."""
+    require_cuda(xyz, new_xyz, points, idx)
+    return (_f32c(xyz.detach()), None if new_xyz is None else _f32c(new_xyz.detach()), None if points is None else _f32c(points.detach()),
+            None if idx is None else _idxc(idx))
+
+
 # ---------------------------------------------------------------------------------------------
 # square_distance
 # ---------------------------------------------------------------------------------------------
@@ -420,7 +435,8 @@ def three_interpolate_add_relu(points2, dist, idx, add=None, relu=False):
     N = dist.shape[1]
     if add is not None:
         add = _f32c(add)
-        assert tuple(add.shape) == (B, N, C)
+        if tuple(add.shape) != (B, N, C):
+            raise ValueError(f"three_interpolate_add_relu: add must be ({B}, {N}, {C}), got {tuple(add.shape)}")
     out = add if add is not None else torch.empty(B, N, C, dtype=torch.float32, device=points2.device)
     check(lib().tgn_three_interpolate_ex(B, N, S, C, ptr(points2), ptr(dist), ptr(idx), int(idx.dtype == torch.int64), ptr(add),
                                          int(bool(relu)), ptr(out), None, stream()), "three_interpolate_ex")
@@ -505,8 +521,12 @@ def sa_point_transform(xyz, points, Wt, Wts=None):
     """A[b,n,:] = [points[b,n,:], xyz[b,n,:]] @ Wt -- the per-POINT half of a fused first layer, on the matrix cores.
     xyz (B,N,3), points (B,N,D) or None, Wt (D+3, C1) -> (B,N,C1).  Wts = split_point_transform(Wt): the bf16 x 3 form
     (tgn_sa_point_transform_bf16x3, fp32-class rounding at up to 2.7x the rate); None: exact fp32 MFMA (tgn_sa_point_transform)."""
+    xyz, _, points, _ = _sa_operands(xyz, None, points, None)
+    Wt = _f32c(Wt)
     B, N, _ = xyz.shape
     D = 0 if points is None else points.shape[2]
+    if Wt.dim() != 2 or Wt.shape[0] != D + 3:
+        raise ValueError(f"sa_point_transform: Wt must be ({D + 3}, C1) for points with {D} channels, got {tuple(Wt.shape)}")
     C1 = Wt.shape[1]
     A = torch.empty(B, N, C1, dtype=torch.float32, device=xyz.device)
     if Wts is not None and B * N <= 65535 * 128:
@@ -522,12 +542,12 @@ def sa_level_max(xyz, new_xyz, points, idx, conv, bn, xyz_first):
         max_k relu(bn(conv([xyz[idx]-new_xyz, points[idx]])))  ->  (B,S,C1)
     (pointnet2_utils.py:162-169 + 229-236, or 281-294 for Msg) with nothing of size S*K ever written: narrow inputs go
     through the direct kernel (gather -> matrix cores -> max), wide ones through the per-point transform + gather-max."""
+    xyz, new_xyz, points, idx = _sa_operands(xyz, new_xyz, points, idx)
     B, N, _ = xyz.shape
     _, S, K = idx.shape
     D = 0 if points is None else points.shape[2]
     f = fold_first_layer(conv, bn, D, xyz_first)
     C1 = f["C1"]
-    idx = idx.contiguous()
     out = torch.empty(B, S, C1, dtype=torch.float32, device=xyz.device)
     L = lib()
     _lib.begin_index_check()
@@ -551,12 +571,12 @@ def sa_first_layer(xyz, new_xyz, points, idx, conv, bn, xyz_first, reduce_max=Fa
     reduce_max (= sa_level_max).  Eval-mode BatchNorm statistics are folded in."""
     if reduce_max:
         return sa_level_max(xyz, new_xyz, points, idx, conv, bn, xyz_first)
+    xyz, new_xyz, points, idx = _sa_operands(xyz, new_xyz, points, idx)
     B, N, _ = xyz.shape
     _, S, K = idx.shape
     D = 0 if points is None else points.shape[2]
     f = fold_first_layer(conv, bn, D, xyz_first)
     C1 = f["C1"]
-    idx = idx.contiguous()
     A = sa_point_transform(xyz, points, f["Wt"])
     out = torch.empty(B, S, K, C1, dtype=torch.float32, device=xyz.device)
     _lib.begin_index_check()
@@ -608,6 +628,7 @@ def sa_level_mlp2_max(xyz, new_xyz, points, idx, convs, bns, xyz_first, out=None
     layer (wide inputs) or with the first layer computed from the gathered rows (3+D <= 16): nothing of size S*K is
     written, no torch convolution runs (tgn_sa_mlp2_max; the second layer on the fp32 matrix cores).  out: optional (B,S,C2)
     view into a wider row-major tensor (last stride 1) -- a multi-scale level writes its branches side by side."""
+    xyz, new_xyz, points, idx = _sa_operands(xyz, new_xyz, points, idx)
     B, N, _ = xyz.shape
     _, S, K = idx.shape
     D = 0 if points is None else points.shape[2]
@@ -626,10 +647,13 @@ def sa_level_mlp2_max(xyz, new_xyz, points, idx, convs, bns, xyz_first, out=None
                           operands)
     C1p, W2f, b2, b1, W1 = ops["C1p"], ops["W2f"], ops["b2"], ops["b1"], ops["W1"]
     C2 = b2.shape[0]
-    idx = idx.contiguous()
     if out is None:
         out = torch.empty(B, S, C2, dtype=torch.float32, device=xyz.device)
-    assert out.shape == (B, S, C2) and out.stride(2) == 1 and out.stride(0) == S * out.stride(1) and out.dtype == torch.float32
+    if out.dtype != torch.float32 or out.device != xyz.device:
+        raise TypeError(f"sa_level_mlp2_max: out must be float32 on {xyz.device}, got {out.dtype} on {out.device}")
+    if tuple(out.shape) != (B, S, C2) or out.stride(2) != 1 or out.stride(0) != S * out.stride(1):
+        raise ValueError(f"sa_level_mlp2_max: out must be ({B}, {S}, {C2}) with unit last stride and evenly spaced rows, got "
+                         f"{tuple(out.shape)} with strides {tuple(out.stride())}")
     A1 = None if direct else sa_point_transform(xyz, points, ops["Wt"], ops["Wts"])      # (B, N, C1p)
     _lib.begin_index_check()
     if ops["W2s"] is not None:
@@ -649,6 +673,7 @@ def sa_all_mlp2_max(xyz, points, convs, bns):
         max_n relu(bn2(conv2(relu(bn1(conv1([xyz_n, points_n]))))))  ->  (B, C2)
     The first layer runs once per point on the fp32 matrix cores (tgn_sa_point_transform; 3+D <= 16: inside the kernel), the second
     layer and the maximum over the cloud in tgn_sa_all_mlp2_max: no (B,1,N,.) tensor, no torch convolution."""
+    xyz, _, points, _ = _sa_operands(xyz, None, points, None)
     B, N, _ = xyz.shape
     D = 0 if points is None else points.shape[2]
     L = lib()

@@ -28,6 +28,37 @@ def _i32(t):
     return t if t.dtype == torch.int32 else t.to(torch.int32)
 
 
+def _f32c(t, what):
+    """What every float tensor argument goes through on its way to a kernel (the kernels read packed fp32 rows): any floating dtype,
+    any strides, any storage offset in; float32 and contiguous out -- the same tensor when it already is.  Applied in the public
+    functions, outside the autograd Functions, so that gradients come back in the caller's dtype and layout."""
+    if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+        raise TypeError(f"{what} must be a floating-point tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    t = t if t.dtype == torch.float32 else t.float()
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _idx32c(t, what):
+    if not isinstance(t, torch.Tensor) or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+        raise TypeError(f"{what} must be an integer tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    return _i32(t).contiguous()
+
+
+def _packed(t, what):
+    """Guard inside the autograd Functions, which callers in this package reach directly (.apply): the kernels behind them read
+    `t` through its raw pointer as packed fp32."""
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{what} must be float32 and contiguous here, got {t.dtype} with strides {tuple(t.stride())}; "
+                         "the public functions of this module normalise their arguments")
+    return t
+
+
+def _packed_idx(t, what):
+    if t.dtype != torch.int32 or not t.is_contiguous():
+        raise ValueError(f"{what} must be int32 and contiguous here, got {t.dtype} with strides {tuple(t.stride())}")
+    return t
+
+
 def _offsets_host(offset):
     """Offsets are device tensors in the reference API; the output size depends on their values, so one
     device->host copy per call is inherent (the reference syncs b+1 times, pointops.py:18-21)."""
@@ -111,10 +142,9 @@ def fps_with_coords(xyz, offset, new_offset, cuda_compat=False, prefix=False):
     (what blocks.py:69-70 computes with a second gather).  Returns (idx int32 (m,), new_xyz (m,3)).
     prefix=True: this call site chains sampling levels -- take part in the FPS-of-an-FPS-result shortcut."""
     require_cuda(xyz, offset, new_offset)
-    assert xyz.is_contiguous()
-    xyz = xyz.float() if xyz.dtype != torch.float32 else xyz
+    xyz = _f32c(xyz.detach(), "xyz")
     off_h, noff_h = offsets_host(offset, new_offset)   # one device->host copy, or none (register_offsets)
-    offset, new_offset = _i32(offset).contiguous(), _i32(new_offset).contiguous()
+    offset, new_offset = _idx32c(offset, "offset"), _idx32c(new_offset, "new_offset")
     b = offset.shape[0]
     if b == 0 or noff_h[-1] == 0:      # nothing to sample (no segments, or only empty ones): an empty result, no launch
         return (torch.zeros(0, dtype=torch.int32, device=xyz.device),
@@ -167,10 +197,8 @@ def _knn_raw(nsample, xyz, new_xyz, offset, new_offset):
     if new_xyz is None:
         new_xyz = xyz
     require_cuda(xyz, new_xyz, offset, new_offset)
-    assert xyz.is_contiguous() and new_xyz.is_contiguous()
-    xyz = xyz.float() if xyz.dtype != torch.float32 else xyz
-    new_xyz = new_xyz.float() if new_xyz.dtype != torch.float32 else new_xyz
-    offset, new_offset = _i32(offset).contiguous(), _i32(new_offset).contiguous()
+    xyz, new_xyz = _f32c(xyz.detach(), "xyz"), _f32c(new_xyz.detach(), "new_xyz")
+    offset, new_offset = _idx32c(offset, "offset"), _idx32c(new_offset, "new_offset")
     m = new_xyz.shape[0]
     idx = torch.empty(m, nsample, dtype=torch.int32, device=xyz.device)
     dist2 = torch.empty(m, nsample, dtype=torch.float32, device=xyz.device)
@@ -196,7 +224,7 @@ config.legacy_attributes(__name__, {"KNN_GRID": "knn_grid", "KNN_GRID_MIN_POINTS
 
 # kNN memo.  The reference recomputes identical neighbour lists again and again: PointTransformerLayer calls
 # queryandgroup(idx=None) twice with the same arguments (blocks.py:34-35) and every block of a stage repeats it.
-# Results are keyed on the identity AND version counter of the argument tensors (kept alive by the cache, so an
+# Results are keyed on the identity (pointer, shape, strides, dtype) AND version counter of the argument tensors (kept alive by the cache, so an
 # address can not be recycled under a live key) and on the current stream (a result is only handed to launches that
 # are stream-ordered after the one that produced it); an in-place write bumps the version and misses.  Tensors
 # without a version counter (torch.inference_mode) bypass the memo.  Writes that torch cannot see -- through
@@ -211,7 +239,7 @@ def _knn_cached(nsample, xyz, new_xyz, offset, new_offset):
     try:
         # inference tensors (torch.inference_mode) carry no version counter: _version raises -> no memo for them
         key = (as_int(nsample), torch.cuda.current_stream().cuda_stream) + tuple(
-            (t.data_ptr(), t._version, tuple(t.shape), t.dtype) for t in tensors)
+            (t.data_ptr(), t._version, tuple(t.shape), tuple(t.stride()), t.dtype) for t in tensors)
     except RuntimeError:
         return _knn_raw(nsample, xyz, new_xyz, offset, new_offset)
     hit = _KNN_CACHE.get(key)
@@ -258,6 +286,8 @@ knnquery = KNNQuery.apply
 
 
 class Grouping(Function):
+    # .apply takes packed operands only -- float32 features, int32 indices, contiguous -- and raises ValueError otherwise (the
+    # reference's kernels read int32 too); the function of the same name in lower case casts and packs any dtype and layout
     @staticmethod
     @_fwd
     def forward(ctx, input, idx):
@@ -266,8 +296,7 @@ class Grouping(Function):
         output: (m, nsample, c)     [pointops.py:48-61]
         """
         require_cuda(input, idx)
-        assert input.is_contiguous() and idx.is_contiguous()
-        idx = _i32(idx)
+        _packed(input, "input"), _packed_idx(idx, "idx")
         m, nsample, n, c = idx.shape[0], idx.shape[1], input.shape[0], input.shape[1]
         output = torch.empty(m, nsample, c, dtype=torch.float32, device=input.device)
         check(lib().tgn_grouping_forward(m, nsample, c, ptr(input), ptr(idx), ptr(output), stream()), "grouping fwd")
@@ -292,7 +321,10 @@ class Grouping(Function):
         return grad_input, None
 
 
-grouping = Grouping.apply
+def grouping(input, idx):
+    """input (n, c) of any floating dtype and layout, idx (m, nsample) of any integer dtype -> (m, nsample, c) float32"""
+    require_cuda(input, idx)
+    return Grouping.apply(_f32c(input, "input"), _idx32c(idx, "idx"))
 
 
 class _QueryGroup(Function):
@@ -305,8 +337,13 @@ class _QueryGroup(Function):
     @staticmethod
     @_fwd
     def forward(ctx, xyz, new_xyz, feat, idx, use_xyz):
+        _packed(feat, "feat"), _packed_idx(idx, "idx")
+        if use_xyz:
+            _packed(xyz, "xyz"), _packed(new_xyz, "new_xyz")
         m, nsample = idx.shape
         n, c = feat.shape
+        if use_xyz and (tuple(xyz.shape) != (n, 3) or tuple(new_xyz.shape) != (m, 3)):
+            raise ValueError(f"xyz must be ({n}, 3) and new_xyz ({m}, 3), got {tuple(xyz.shape)} and {tuple(new_xyz.shape)}")
         ctx.n, ctx.use_xyz = n, use_xyz
         ctx.save_for_backward(idx)
         if not use_xyz:
@@ -353,11 +390,13 @@ def queryandgroup(nsample, xyz, new_xyz, feat, idx, offset, new_offset, use_xyz=
     if new_xyz is None:
         new_xyz = xyz
     require_cuda(xyz, new_xyz, feat)
-    assert xyz.is_contiguous() and new_xyz.is_contiguous() and feat.is_contiguous()
+    same = new_xyz is xyz
+    xyz, feat = _f32c(xyz, "xyz"), _f32c(feat, "feat")
+    new_xyz = xyz if same else _f32c(new_xyz, "new_xyz")
     own_idx = idx is None
     if own_idx:
         idx, _ = knnquery(nsample, xyz, new_xyz, offset, new_offset)  # (m, nsample)
-    idx = _i32(idx).contiguous()
+    idx = _idx32c(idx, "idx")
     if not own_idx and use_xyz:
         _lib.begin_index_check()
     out = _QueryGroup.apply(xyz, new_xyz, feat, idx, bool(use_xyz))
@@ -368,6 +407,8 @@ def queryandgroup(nsample, xyz, new_xyz, feat, idx, offset, new_offset, use_xyz=
 
 
 class Subtraction(Function):
+    # .apply takes packed operands only -- float32 features, int32 indices, contiguous -- and raises ValueError otherwise (the
+    # reference's kernels read int32 too); the function of the same name in lower case casts and packs any dtype and layout
     @staticmethod
     @_fwd
     def forward(ctx, input1, input2, idx):
@@ -376,8 +417,7 @@ class Subtraction(Function):
         output:  (n, nsample, c)    [pointops.py:103-116]
         """
         require_cuda(input1, input2, idx)
-        assert input1.is_contiguous() and input2.is_contiguous()
-        idx = _i32(idx).contiguous()
+        _packed(input1, "input1"), _packed(input2, "input2"), _packed_idx(idx, "idx")
         n, c = input1.shape
         nsample = idx.shape[-1]
         output = torch.empty(n, nsample, c, dtype=torch.float32, device=input1.device)
@@ -404,10 +444,15 @@ class Subtraction(Function):
         return grad_input1, grad_input2, None
 
 
-subtraction = Subtraction.apply
+def subtraction(input1, input2, idx):
+    """input1, input2 (n, c) of any floating dtype and layout, idx (n, nsample) of any integer dtype -> (n, nsample, c) float32"""
+    require_cuda(input1, input2, idx)
+    return Subtraction.apply(_f32c(input1, "input1"), _f32c(input2, "input2"), _idx32c(idx, "idx"))
 
 
 class Aggregation(Function):
+    # .apply takes packed operands only -- float32 features, int32 indices, contiguous -- and raises ValueError otherwise (the
+    # reference's kernels read int32 too); the function of the same name in lower case casts and packs any dtype and layout
     @staticmethod
     @_fwd
     def forward(ctx, input, position, weight, idx):
@@ -416,8 +461,7 @@ class Aggregation(Function):
         output: (n, c)              [pointops.py:133-146]
         """
         require_cuda(input, position, weight, idx)
-        assert input.is_contiguous() and position.is_contiguous() and weight.is_contiguous()
-        idx = _i32(idx).contiguous()
+        _packed(input, "input"), _packed(position, "position"), _packed(weight, "weight"), _packed_idx(idx, "idx")
         n, nsample, c = position.shape
         w_c = weight.shape[-1]
         output = torch.zeros(n, c, dtype=torch.float32, device=input.device)
@@ -446,7 +490,11 @@ class Aggregation(Function):
         return grad_input, grad_position, grad_weight, None
 
 
-aggregation = Aggregation.apply
+def aggregation(input, position, weight, idx):
+    """input (n, c), position (n, nsample, c), weight (n, nsample, c') of any floating dtype and layout, idx (n, nsample) of any
+    integer dtype -> (n, c) float32"""
+    require_cuda(input, position, weight, idx)
+    return Aggregation.apply(_f32c(input, "input"), _f32c(position, "position"), _f32c(weight, "weight"), _idx32c(idx, "idx"))
 
 
 def _inverse_distance_weights(dist):
@@ -462,6 +510,7 @@ class _WeightedGather(Function):
     @staticmethod
     @_fwd
     def forward(ctx, feat, idx, weight):
+        _packed(feat, "feat"), _packed_idx(idx, "idx"), _packed(weight, "weight")
         n, k = idx.shape
         m, c = feat.shape
         output = torch.zeros(n, c, dtype=torch.float32, device=feat.device)
@@ -490,7 +539,7 @@ def interpolation(xyz, new_xyz, feat, offset, new_offset, k=3):
     output: (n, c)                  [pointops.py:164-180; weights detached as there]
     """
     require_cuda(xyz, new_xyz, feat)
-    assert xyz.is_contiguous() and new_xyz.is_contiguous() and feat.is_contiguous()
+    xyz, new_xyz, feat = _f32c(xyz, "xyz"), _f32c(new_xyz, "new_xyz"), _f32c(feat, "feat")
     k = as_int(k)
     idx, dist = knnquery(k, xyz, new_xyz, offset, new_offset)  # (n, k), (n, k)
     weight = _inverse_distance_weights(dist).detach().contiguous()
@@ -505,11 +554,10 @@ class Interpolation(Function):
         output: (n, c)              [pointops.py:183-201]
         """
         require_cuda(xyz, new_xyz, input)
-        assert xyz.is_contiguous() and new_xyz.is_contiguous() and input.is_contiguous()
+        _packed(input, "input")
         k = as_int(k)
-        idx, dist2 = _knn_raw(k, xyz, new_xyz, offset, new_offset)
+        idx, dist2 = _knn_raw(k, xyz, new_xyz, offset, new_offset)      # (normalises xyz, new_xyz and the offsets itself)
         weight = _inverse_distance_weights(torch.sqrt(dist2)).contiguous()
-        input = input.float()
         n, c, m = new_xyz.shape[0], input.shape[1], input.shape[0]
         output = torch.zeros(n, c, dtype=torch.float32, device=input.device)
         check(lib().tgn_interpolation_forward(n, c, k, ptr(input), ptr(idx), ptr(weight), ptr(output), stream()),
@@ -533,4 +581,7 @@ class Interpolation(Function):
         return None, None, grad_input, None, None, None
 
 
-interpolation2 = Interpolation.apply
+def interpolation2(xyz, new_xyz, input, offset, new_offset, k=3):
+    """Interpolation.apply on arguments of any floating dtype and layout (the gradient reaches `input` only, as in the reference)"""
+    require_cuda(xyz, new_xyz, input)
+    return Interpolation.apply(_f32c(xyz, "xyz"), _f32c(new_xyz, "new_xyz"), _f32c(input, "input"), offset, new_offset, k)

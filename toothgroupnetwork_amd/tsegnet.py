@@ -159,7 +159,7 @@ def paint_labels(nn_crop_indexes, pd_2, id_pred, n_points):
     B = len(nn_crop_indexes)
     for i in nn_crop_indexes:
         if i.dim() != 2 or i.dtype != torch.int64 or i.shape[1] != nn_crop_indexes[0].shape[1]:
-            raise ValueError("every scan's crop indices must be (T_b, k) int64 with one k")
+            raise ValueError(f"nn_crop_indexes: every scan's crop indices must be (T_b, k) int64 with one k, got {tuple(i.shape)} {i.dtype}")
     per_scan = [int(i.shape[0]) for i in nn_crop_indexes]
     T, k = sum(per_scan), int(nn_crop_indexes[0].shape[1])
     if pd_2.dim() == 3 and pd_2.shape[1] == 1:
