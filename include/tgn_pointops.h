@@ -535,6 +535,54 @@ int tgn_tsg_paint(int b, int n, int t_total, int k, const int *crop_scan, const 
                   const long long *ids, long long *out, tgn_stream_t stream);
 
 /*
+ * The geometric training losses as fused kernels (csrc/loss.hip), forward and backward.  All tensors float32 and contiguous unless
+ * said otherwise; offset, xyz (b, 3, n) channel-first.  Squared distances are the direct form ((dx*dx) + (dy*dy)) + (dz*dz) in float32;
+ * every sum that crosses threads is float64 in a fixed order (wave, LDS, per-block partials in `workspace`, a finishing kernel) and
+ * is rounded to float32 once.  No atomics on floats: the same inputs give the same bits.  The calls launch on `stream` and neither
+ * allocate, copy nor synchronise; `workspace` (device memory, at least *_workspace_bytes) is free again when the forward has run.
+ *
+ *   tgn_offset_loss_forward: batch_center_offset_loss and batch_chamfer_distance_loss of tgnet_fps (models/tgn_loss.py:6-61, 263-302).
+ *     labels (b, n) int64 in -1..15 (-1 = gingiva; another value counts as gingiva and latches bit 1 of the stream's error word),
+ *     counts (b, 16) int32 and cent (b, 16, 3) the per-tooth point counts and centroids of tgn_label_centroids with nlab = 16.  A tooth
+ *     is valid when its count is >= 5.  With m = p + o, c_t the centroid of the point's tooth:
+ *       losses[0] = (sum over valid (s, t) of (sum_i |m_i - c_t|^2) / n_st) / #valid
+ *       losses[1] = (sum over valid (s, t) with k_st > 0 of (sum over kept i of (d_i . o_i/|o_i| - 1)^2) / k_st) / #those,
+ *                   d = (c_t - p)/|c_t - p|, a point kept when |o| > 0.0002, k_st the kept points
+ *       losses[2] = (1 / b) sum_s (sum over points with label != -1 of d1 / d2) / #those, d1 <= d2 the two smallest |m - c|^2 over the
+ *                   VALID teeth of the scan
+ *     An empty denominator gives NaN (0 / 0, as the reference); a scan with fewer than two valid teeth gives NaN for losses[2]
+ *     (the reference raises).  scales (b, 33) receives what the backward needs: per tooth 1 / (n_st #valid) and 1 / (k_st #those),
+ *     then 1 / (b #foreground); 0 where the term is undefined.
+ *   tgn_offset_loss_backward: grad_offset (b, 3, n) = grad_losses[0] d losses[0] + grad_losses[1] d losses[1] + grad_losses[2] d losses[2]
+ *     with respect to offset (grad_losses: 3 floats in DEVICE memory).  A point the direction term does not keep, an exactly zero
+ *     offset included, gets a zero direction gradient (the reference's autograd gives NaN for an exact zero); a term whose loss is
+ *     NaN for want of teeth contributes zero.
+ *
+ *   tgn_centroid_loss_forward: centroid_loss of tsegnet (models/tsg_loss.py:4-61).  offset, xyz (b, 3, m), distance (b, m), centroid
+ *     (b, 3, c) with 1 <= c <= 16, exists (b, c) bytes or NULL (every centroid exists); absent centroids are skipped in both
+ *     directions.  With m_j = x_j + o_j, d1 <= d2 the two smallest |m_j - c|^2, g_c = min_j |c - m_j|^2 over the scan's points:
+ *       losses[0] = mean over b m of smooth_l1(distance - sqrt(min_c |x - c|^2)), beta 1
+ *       losses[1] = sum(d1 | distance <= 0.2) / # + sum(g_c | g_c <= 0.2) / #        (counts over the whole batch)
+ *       losses[2] = sum(d1 / d2 | d1 <= 0.2) / #
+ *     An empty mask gives NaN; fewer than two existing centroids in a scan give NaN for losses[2].  scales (4) and rev_arg (b, 16)
+ *     int32 (the argmin of every g_c that is <= 0.2, lowest index on a tie, else -1) are for the backward.
+ *   tgn_centroid_loss_backward: grad_offset (b, 3, m) and grad_distance (b, m) for grad_losses (3 floats in device memory).  Every
+ *     point collects the reverse term by looking for its own index among its scan's 16 saved argmins: one launch, no atomics.
+ */
+size_t tgn_offset_loss_workspace_bytes(int b, int n);
+int tgn_offset_loss_forward(int b, int n, const float *offset, const float *xyz, const long long *labels, const int *counts,
+                            const float *cent, float *losses, float *scales, void *workspace, size_t ws_bytes, tgn_stream_t stream);
+int tgn_offset_loss_backward(int b, int n, const float *offset, const float *xyz, const long long *labels, const int *counts,
+                             const float *cent, const float *scales, const float *grad_losses, float *grad_offset, tgn_stream_t stream);
+size_t tgn_centroid_loss_workspace_bytes(int b);
+int tgn_centroid_loss_forward(int b, int m, int c, const float *offset, const float *xyz, const float *distance, const float *centroid,
+                              const unsigned char *exists, float *losses, float *scales, int *rev_arg, void *workspace, size_t ws_bytes,
+                              tgn_stream_t stream);
+int tgn_centroid_loss_backward(int b, int m, int c, const float *offset, const float *xyz, const float *distance, const float *centroid,
+                               const unsigned char *exists, const float *scales, const int *rev_arg, const float *grad_losses,
+                               float *grad_offset, float *grad_distance, tgn_stream_t stream);
+
+/*
  * DGCNN's neighbourhood work (models/modules/dgcnn.py).  x (B, D, N) float32 channel-first, as the network holds it.
  *   tgn_feature_knn: knn(x, k) (dgcnn.py:4-10) without the N x N matrix.  idx (B, N, k) int64 point indices local to their scan;
  *     row i holds the k smallest distances to point i, i itself included, in ascending (distance, index) order.  The distance is

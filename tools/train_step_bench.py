@@ -86,6 +86,20 @@ def losses(offset, sem, xyz, label, teeth=17):
     return ce + 0.03 * (cen_t * valid).sum() / cnt + 0.03 * (dir_t * valid).sum() / cnt, ce
 
 
+def fused_losses(offset, sem, xyz, label):
+    """The same two terms from the package's fused criterion (toothgroupnetwork_amd.losses.batch_center_offset_loss, csrc/loss.hip):
+    a point pass, a finishing kernel and one backward launch instead of the index_add_ composition.  The labels shift by one (here
+    0 = gingiva, there -1); the chamfer term is left out, as in `losses`.  The direction term is averaged over the teeth that keep a
+    point, as the reference does, where `losses` divides by the number of valid teeth: the same value when every valid tooth keeps one."""
+    from toothgroupnetwork_amd import losses as L
+    ce = F.cross_entropy(sem.float(), label)
+    cen, dirl = L.batch_center_offset_loss(offset.t()[None], xyz.t()[None], (label - 1)[None])
+    return ce + 0.03 * cen + 0.03 * dirl, ce
+
+
+criterion = losses     # what the step functions below call; --fused-loss selects fused_losses
+
+
 class TwoStage(nn.Module):
     """The two passes of GroupingNetworkModule.forward (grouping_network_module.py:16-101): the first-stage network on the whole
     scan; then, around the centroid of every tooth (the reference clusters the moved foreground points with DBSCAN on the CPU and
@@ -119,7 +133,7 @@ def run_two_stage(net, opt, feat, xyz, label, steps, amp, graph):
     def step():
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
             offset, sem, offset2, mask2, mask_gt = net(feat, xyz, label)
-            loss, _ = losses(offset, sem, xyz, label)
+            loss, _ = criterion(offset, sem, xyz, label)
             loss = loss + F.cross_entropy(mask2.float(), mask_gt) + 0.03 * offset2.float().square().sum(1).mean()
         opt.zero_grad(set_to_none=False)
         loss.backward()
@@ -166,7 +180,7 @@ def run_graph(net, opt, feat, xyz, label, steps, amp):
     def step():
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
             offset, sem = net(feat)
-            loss, ce = losses(offset, sem, xyz, label)
+            loss, ce = criterion(offset, sem, xyz, label)
         opt.zero_grad(set_to_none=False)
         loss.backward()
         opt.step()
@@ -202,7 +216,7 @@ def run(net, opt, feat, xyz, label, steps, amp):
         a.record()
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
             offset, sem = net(feat)
-            loss, ce = losses(offset, sem, xyz, label)
+            loss, ce = criterion(offset, sem, xyz, label)
         opt.zero_grad(set_to_none=True)
         loss.backward()
         # (checked on the first step only: 569 isfinite + all + item round trips are 15 ms of a step)
@@ -273,11 +287,15 @@ def main():
     ap.add_argument("--two-stage-module", action="store_true", help="also time a training step of nets.GroupingNetworkModule (fp32, eager, "
                     "a labelled arch scan with its real tooth count; on-device crops) and its crop step against square_distance + topk")
     ap.add_argument("--graph", action="store_true", help="also capture the whole step in a HIP graph and time its replays")
+    ap.add_argument("--fused-loss", action="store_true", help="take the offset and direction terms from toothgroupnetwork_amd.losses "
+                    "(fused HIP kernels) instead of the index_add_ composition `losses`")
     ap.add_argument("--profile", action="store_true", help="print the top GPU kernels of one bf16-autocast step (torch.profiler)")
     args = ap.parse_args()
+    global criterion
+    criterion = fused_losses if args.fused_loss else losses
     dev = torch.device("cuda")
     feat, xyz, label = make_scan(args.points, 3, dev)
-    res = {}
+    res = {"criterion": "fused" if args.fused_loss else "index_add"}
     for amp in (False, True):
         torch.manual_seed(0)
         net = (FirstStage((16, 32, 32, 64, 64), (1, 2, 2, 2, 1)) if args.small else FirstStage()).to(dev).train()

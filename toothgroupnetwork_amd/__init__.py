@@ -9,6 +9,7 @@ Point-Transformer subtraction / aggregation operators).
     toothgroupnetwork_amd.point_transformer mirrors of the cbl_point_transformer blocks (fused eval paths)
     toothgroupnetwork_amd.dgcnn             DGCNN: feature-space kNN, edge features, the DGCnnModule mirror (fused EdgeConv)
     toothgroupnetwork_amd.tsegnet           tsegnet's join between its two networks and its label painting (proposals, clusters, crops)
+    toothgroupnetwork_amd.losses            the geometric training losses of tgnet_fps and tsegnet (fused forward and backward kernels)
     toothgroupnetwork_amd.nets              whole-network mirrors (state_dict-compatible with the reference's modules)
     toothgroupnetwork_amd.sharding          one-process-per-GPU mesh sharding + the RCCL metric gather
     toothgroupnetwork_amd.launch            starting the ranks of a multi-GPU run; rank / device / backend records

@@ -124,6 +124,12 @@ SIGNATURES = {
     "tgn_tsg_proposals": (c_int, [c_int, c_int, _P, _P, _P, c_float, _P, _P, _P]),
     "tgn_tsg_crop_features": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "tgn_tsg_paint": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    "tgn_offset_loss_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "tgn_offset_loss_forward": (c_int, [c_int, c_int] + [_P] * 8 + [c_size_t, _P]),
+    "tgn_offset_loss_backward": (c_int, [c_int, c_int] + [_P] * 9),
+    "tgn_centroid_loss_workspace_bytes": (c_size_t, [c_int]),
+    "tgn_centroid_loss_forward": (c_int, [c_int, c_int, c_int] + [_P] * 9 + [c_size_t, _P]),
+    "tgn_centroid_loss_backward": (c_int, [c_int, c_int, c_int] + [_P] * 11),
     "tgn_feature_knn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "tgn_feature_knn": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "tgn_edgeconv2_max": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, ctypes.c_longlong, c_int, _P]),

@@ -20,7 +20,8 @@ of the fused eval paths.  Parameter names and shapes equal the reference classes
   GroupingNetworkModule  models/modules/grouping_network_module.py:7-101, tgnet_fps's network (train_configs/tgnet_fps.py): a
                        PointTransformerSeg over the scan, on-device tooth crops (crops.tooth_crops), a second PointTransformerSeg over
                        all crops as one batch.  Without labels the centroids come from on-device clustering (cluster.py, which
-                       reaches crop.hip's kNN and label means through crops.py); the cbl terms stay the reference's Python.
+                       reaches crop.hip's kNN and label means through crops.py).  The offset, direction and chamfer terms of its loss are
+                       losses.grouping_loss_terms (fused kernels, csrc/loss.hip); the cbl terms stay the reference's Python.
   TSegNetModule        models/modules/tsegnet.py:10-88 (the "tsegnet" model): TsgCentroidNet, the join on the GPU (tsegnet.py of this
                        package: proposal filter, DBSCAN, cluster means, crops with the distance feature; the means and the crops'
                        kNN through crops.py's wrappers of crop.hip), TsgSegNet over the crops.
@@ -344,8 +345,8 @@ class TSegNetModule(nn.Module):
     `center_points` is what the reference returns for B = 1, a (1, T, 3) float32 numpy array, and for B > 1 a list over scans of
     (1, T_b, 3) arrays.  Host synchronisations per forward: tsegnet.py's two (kept counts, cluster counts) and the copy of
     `center_points` to the host that the reference's return type asks for.  In eval mode the segmentation module runs scan by scan
-    (`segment`), so a scan's outputs do not depend on the rest of the batch.  The losses (models/tsg_loss.py) stay the reference's
-    Python."""
+    (`segment`), so a scan's outputs do not depend on the rest of the batch.  The centroid terms of its loss (tsg_loss.centroid_loss) are
+    losses.tsegnet_centroid_loss_terms (fused kernels, csrc/loss.hip); segmentation_loss and id_loss stay the reference's Python."""
 
     MAX_CROPS = 8            # tsegnet.py:70
     CROP_K = 3072            # tsegnet.py:73
