@@ -362,7 +362,7 @@ def _wt_build(dev, D):
 
 
 for _D in (5, 64):
-    row(f"sa_point_transform[D{_D}]", "pointnet2_utils", ["sa_point_transform"], lambda dev, D=_D: _wt_build(dev, D),
+    row(f"sa_point_transform[D{_D}]", "sa_fused", ["sa_point_transform"], lambda dev, D=_D: _wt_build(dev, D),
         lambda a: _U().sa_point_transform(a["xyz"], a["points"], a["Wt"]), floats=["xyz", "points", "Wt"], ints=[], outputs=["A"])
 
     def _call_level(a, D=_D, reduce_max=True):
@@ -372,9 +372,9 @@ for _D in (5, 64):
                 return _U().sa_level_max(a["xyz"], a["new_xyz"], a["points"], a["idx"], convs[0], bns[0], True)
             return _U().sa_first_layer(a["xyz"], a["new_xyz"], a["points"], a["idx"], convs[0], bns[0], True)
 
-    row(f"sa_level_max[D{_D}]", "pointnet2_utils", ["sa_level_max"], lambda dev, D=_D: _sa_build(dev, "sa_level_max", D)[0], _call_level,
+    row(f"sa_level_max[D{_D}]", "sa_fused", ["sa_level_max"], lambda dev, D=_D: _sa_build(dev, "sa_level_max", D)[0], _call_level,
         floats=["xyz", "new_xyz", "points"], ints=["idx"], outputs=["out"])
-    row(f"sa_first_layer[D{_D}]", "pointnet2_utils", ["sa_first_layer"], lambda dev, D=_D: _sa_build(dev, "sa_first_layer", D)[0],
+    row(f"sa_first_layer[D{_D}]", "sa_fused", ["sa_first_layer"], lambda dev, D=_D: _sa_build(dev, "sa_first_layer", D)[0],
         lambda a, f=_call_level: f(a, reduce_max=False), floats=["xyz", "new_xyz", "points"], ints=["idx"], outputs=["out"])
 
     def _call_mlp2(a, D=_D, all_points=False):
@@ -387,10 +387,10 @@ for _D in (5, 64):
             _U().sa_level_mlp2_max(a["xyz"], a["new_xyz"], a["points"], a["idx"], convs, bns, True, out=cat[:, :, 16:64])
             return cat
 
-    row(f"sa_level_mlp2_max[D{_D},out=view]", "pointnet2_utils", ["sa_level_mlp2_max", "split_second_layer"],
+    row(f"sa_level_mlp2_max[D{_D},out=view]", "sa_fused", ["sa_level_mlp2_max", "split_second_layer"],
         lambda dev, D=_D: _sa_build(dev, "sa_level_mlp2_max", D)[0], _call_mlp2,
         floats=["xyz", "new_xyz", "points"], ints=["idx"], outputs=["cat"])
-    row(f"sa_all_mlp2_max[D{_D}]", "pointnet2_utils", ["sa_all_mlp2_max"],
+    row(f"sa_all_mlp2_max[D{_D}]", "sa_fused", ["sa_all_mlp2_max"],
         lambda dev, D=_D: {k: v for k, v in _dense(dev, "sa_all_mlp2_max", D)[0].items() if k in ("xyz", "points")},
         lambda a, f=_call_mlp2: f(a, all_points=True), floats=["xyz", "points"], ints=[], outputs=["out"])
 
@@ -601,13 +601,16 @@ INTERNAL = {
     "dbscan_counts": ("cluster", "dbscan", "dbscan is dbscan_counts(...)[:2]: the same validation and launch, one more output"),
     "_LinearSplitK": ("point_transformer", "bn_rows", "reached through mlp_train next to bn_rows; takes the kernel only for fp32 rows "
                       "and packs them itself, every other dtype goes to torch.bmm"),
+    "_launch_point_transform": ("sa_fused", "sa_point_transform[D5]", "the launch under sa_point_transform, which normalises the operands first"),
+    "launch_branch": ("sa_fused", "sa_level_max[D5]", "the launch under sa_level_max / sa_level_mlp2_max, which normalise the operands "
+                      "first; HotPath calls it with buffers it allocated packed itself"),
     "TransitionDown": ("point_transformer", "sa_point_transform[D5]", "a module: its fused eval path launches the kernels of "
                        "sa_point_transform / sa_level_max on operands it normalises the same way"),
 }
 
 REFERENCE_POINTOPS_NAMES = ["FurthestSampling", "furthestsampling", "KNNQuery", "knnquery", "Grouping", "grouping", "queryandgroup",
                             "Subtraction", "subtraction", "Aggregation", "aggregation", "interpolation", "Interpolation", "interpolation2"]
-SWEPT_MODULES = ["pointops", "pointnet2_utils", "dgcnn", "crops", "cluster", "tsegnet", "point_transformer"]
+SWEPT_MODULES = ["pointops", "pointnet2_utils", "sa_fused", "dgcnn", "crops", "cluster", "tsegnet", "point_transformer"]
 
 
 def covered_names(module):

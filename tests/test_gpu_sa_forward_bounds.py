@@ -1,7 +1,7 @@
 """GPU: the fused set-abstraction forward kernels (csrc/sa.hip, csrc/sa_mlp.hip) held to a float64 error bound scaled by their terms.
 
-The kernels do not compute what the reference computes: they fold BatchNorm into the weights (pointnet2_utils._fold_first_layer /
-_fold_second_layer), commute the first layer for wide inputs (A1 = [f, x] . W1t per point, cst = b - Wxs . centre per query) and by
+The kernels do not compute what the reference computes: they fold BatchNorm into the weights (sa_fused.pack_first_layer /
+pack_second_layer), commute the first layer for wide inputs (A1 = [f, x] . W1t per point, cst = b - Wxs . centre per query) and by
 default run the commuted first layer and the second layer as six bf16 MFMAs per fp32 product (bf16x3).  Each test restates the
 algorithm the kernel documents in float64 and returns, for every output, the value `want` and the magnitude M, the sum of the absolute
 values of the terms that algorithm adds:
@@ -308,7 +308,7 @@ MLP2_EXTRA = [(1500, 512, 32, 128, 128, 392),     # C2 past 256, no multiple of 
 
 
 def _mlp2_case(dev, monkeypatch, N, S, K, D, C1, C2, xyz_first, regime):
-    from toothgroupnetwork_amd import pointnet2_utils as U, _lib
+    from toothgroupnetwork_amd import pointnet2_utils as U, _lib, sa_fused
     B = 2
     xyz, feat, radius = make_cloud(B, N, D, N + K + D + C2, regime)
     tx, tf = T(xyz, dev), T(feat, dev)
@@ -325,7 +325,7 @@ def _mlp2_case(dev, monkeypatch, N, S, K, D, C1, C2, xyz_first, regime):
     pre, mag = next_layer64(pre, mag, fold64(conv2, bn2))
     want, M, premax = reduce_max64(pre, mag)
     del pre, mag
-    C1p = (C1 + 15) // 16 * 16
+    C1p = sa_fused.pad16(C1)
     C = chain_const(max(3 + D + 4, C1p))
     tag = f"({N},{S},{K},{D},{C1},{C2}) {'direct' if direct else 'commuted'} xyz_first={xyz_first} {regime}"
     rel = {}
@@ -392,7 +392,7 @@ def test_commuted_bound_off_origin(dev):
 @pytest.mark.parametrize("N", [1, 31, 32, 33, 64, 65, 257, 24000])
 @pytest.mark.parametrize("D,C1,C2", [(6, 64, 128), (512, 256, 512)])
 def test_group_all_bound(dev, monkeypatch, N, D, C1, C2):
-    from toothgroupnetwork_amd import pointnet2_utils as U, _lib
+    from toothgroupnetwork_amd import pointnet2_utils as U, _lib, sa_fused
     monkeypatch.setattr(U, "FUSED_SA", True)
     calls = []
     real = U.sa_all_mlp2_max
@@ -415,7 +415,7 @@ def test_group_all_bound(dev, monkeypatch, N, D, C1, C2):
     pre, mag = next_layer64(pre, mag, fold64(mod.mlp_convs[1], mod.mlp_bns[1]))
     want, M, premax = reduce_max64(pre, mag)
     direct = bool(_lib.lib().tgn_sa_mlp2_direct_supported(min(N, 64), D))
-    check_bound(got, want[:, 0], M[:, 0], chain_const(max(3 + D + 4, (C1 + 15) // 16 * 16)),
+    check_bound(got, want[:, 0], M[:, 0], chain_const(max(3 + D + 4, sa_fused.pad16(C1))),
                 f"group-all N={N} D={D} {'direct' if direct else 'commuted'}", premax[:, 0])
 
 
@@ -423,7 +423,7 @@ def test_group_all_bound(dev, monkeypatch, N, D, C1, C2):
 # bench.py --fused: HotPath(fused=True) at its own shape, each level against its own fp32 input
 # ------------------------------------------------------------------------------------------------------------------------------
 def test_hotpath_fused_bench_shape_bound(dev, monkeypatch):
-    from toothgroupnetwork_amd import hotpath, synth, pointnet2_utils as U
+    from toothgroupnetwork_amd import hotpath, synth, pointnet2_utils as U, sa_fused
     B = 2
     scans = synth.scan_batch(B, hotpath.SHAPE_A["n"], "arch", 17)
     pts = T(scans, dev)
@@ -446,7 +446,7 @@ def test_hotpath_fused_bench_shape_bound(dev, monkeypatch):
                 pre, mag = next_layer64(pre, mag, layer)
             want, M, premax = reduce_max64(pre, mag)
             del pre, mag
-            C1p = (lv["layers"][0][0].shape[0] + 15) // 16 * 16
+            C1p = sa_fused.pad16(lv["layers"][0][0].shape[0])
             form = "bf16x3" if bf16x3 else "fp32-MFMA"
             rel[bf16x3, li] = check_bound(lv["out"], want, M, chain_const(max(3 + D + 4, C1p)),
                                           f"HotPath fused level {li + 1} {form} ({'direct' if direct else 'commuted'}, D={D})", premax)

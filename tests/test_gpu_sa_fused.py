@@ -273,6 +273,40 @@ def test_hotpath_fused_multi_scale_levels_vs_oracle(dev, oracle, pipeline):
         cur, feat = new_xyz, lv["out"].cpu().numpy()
 
 
+@pytest.mark.parametrize("bf16x3", [True, False])
+@pytest.mark.parametrize("mlp", [[[24, 32], [64, 48]], [[32], [64]]])
+def test_hotpath_and_the_modules_are_one_path(dev, mlp, bf16x3):
+    """What bench.py --fused measures is what the networks run: every fused HotPath level equals, bit for bit, sa_level_max /
+    sa_level_mlp2_max called on the level's own inputs with Conv2d / BatchNorm2d modules that hold the level's weights (identity
+    BatchNorm with eps = 0: scale exactly 1, shift exactly 0).  No float atomics on either side, so equality is the bar.  Level 1 is
+    the direct form, level 2 the commuted one; [24, 32] -> [64, 48]: two layers, C1 = 24 is padded to 32 in both."""
+    from toothgroupnetwork_amd import config, hotpath, pointnet2_utils as U, synth
+    d = [6, mlp[0][-1]]                                           # level 2 reads level 1's output
+    shape = dict(n=600, npoint=[128, 32], radius=[0.2, 0.4], nsample=[16, 32], d=d, mlp=mlp)
+    B = 2
+    pts = T(synth.scan_batch(B, 600, "arch", 47), dev)
+    xyz = pts[:, :, :3].contiguous()
+    with config.override(sa_bf16x3=bf16x3), torch.no_grad():
+        levels = hotpath.HotPath(B, dev, shape=shape, fused=True).run(xyz, [pts])
+        cur, feat = xyz, pts
+        for li, lv in enumerate(levels):
+            convs, bns = [], []
+            for W, b in lv["layers"]:
+                conv = torch.nn.Conv2d(W.shape[1], W.shape[0], 1).to(dev)
+                conv.weight.copy_(T(W, dev).view_as(conv.weight))
+                conv.bias.copy_(T(b, dev))
+                bn = torch.nn.BatchNorm2d(W.shape[0], eps=0.0).to(dev).eval()      # fresh: mean 0, var 1, weight 1, bias 0
+                convs.append(conv)
+                bns.append(bn)
+            args = (cur, lv["new_xyz"], feat, lv["group_idx"])
+            got = (U.sa_level_max(*args, convs[0], bns[0], True) if len(convs) == 1
+                   else U.sa_level_mlp2_max(*args, convs, bns, True))
+            assert lv["D"] == d[li] and got.shape == lv["out"].shape
+            assert lv["branches"][0]["plan"]["direct"] == (li == 0)            # level 1 direct, level 2 commuted, as the docstring says
+            assert torch.equal(got, lv["out"]), f"level {li + 1} mlp {mlp[li]} bf16x3={bf16x3}"
+            cur, feat = lv["new_xyz"], lv["out"]
+
+
 @pytest.mark.parametrize("M,D,C1", [(6000, 256, 256), (4099, 1024, 784), (1000, 61, 100), (300, 13, 208), (129, 0, 16)])
 def test_point_transform_bf16x3_vs_float64(dev, M, D, C1):
     """tgn_sa_point_transform_bf16x3 (per-point first layer as six bf16 MFMAs per fp32 product) and the fp32-MFMA form against

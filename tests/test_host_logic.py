@@ -258,6 +258,64 @@ def test_derived_operand_memo_follows_the_parameters():
         assert torch.allclose(PT.mlp_eval(seq, x.clone()), seq(x.clone()), atol=1e-6)
 
 
+@pytest.mark.parametrize("given", ["all", "none", "bias", "scale+shift"])
+@pytest.mark.parametrize("xyz_first", [True, False])
+def test_sa_packers_write_the_layout_the_header_documents(given, xyz_first):
+    """sa_fused.pack_first_layer / pack_second_layer / pad16 against a numpy restatement of the operand layout of the fused
+    set-abstraction kernels as include/tgn_pointops.h words it (tgn_sa_point_transform, tgn_sa_gather_max, tgn_sa_direct_max,
+    tgn_sa_mlp2_max), entry by entry.  Every product and sum is one fp32 operation on both sides, so the comparison is exact; an absent
+    bias / scale / shift is skipped, so what is present arrives bit for bit (HotPath passes a bias only, TransitionDown scale and shift
+    only), the sign of a zero included."""
+    import numpy as np
+    import torch
+    from toothgroupnetwork_amd import sa_fused as F
+    assert [F.pad16(c) for c in (1, 15, 16, 17, 24, 32, 100, 784)] == [16, 16, 16, 32, 32, 32, 112, 784]
+    rng = np.random.default_rng(5)
+    f32 = lambda *shape: rng.normal(size=shape).astype(np.float32)
+    opt = lambda name, a: torch.from_numpy(a) if (given == "all" or name in given.split("+")) else None
+
+    def folded_bias(bias, scale, shift, C):                                     # shift + scale * bias, of the terms there are
+        b = None if bias is None else bias.numpy()
+        if b is not None and scale is not None:
+            b = scale.numpy() * b
+        if shift is not None:
+            b = shift.numpy() if b is None else shift.numpy() + b
+        return np.zeros(C, np.float32) if b is None else b
+
+    for D in (0, 6, 13, 14, 61):
+        for C1 in (24, 32, 100):
+            W = f32(C1, 3 + D)
+            W[::5, ::2] = -0.0
+            bias, scale, shift = opt("bias", f32(C1)), opt("scale", f32(C1)), opt("shift", f32(C1))
+            f = F.pack_first_layer(torch.from_numpy(W), bias, scale, shift, D, xyz_first)
+            col_x, col_f = (0, 3) if xyz_first else (D, 0)                      # where the caller keeps x, y, z and the features
+            rows = [col_f + j for j in range(D)] + [col_x, col_x + 1, col_x + 2]
+            Wt = np.stack([W[:, c] if scale is None else W[:, c] * scale.numpy() for c in rows])       # rows [features..., x, y, z]
+            Wd = np.zeros((16, C1), np.float32)                                                          # rows [x, y, z, features..., 0]
+            if 3 + D <= 16:
+                Wd[:3], Wd[3:3 + D] = Wt[D:], Wt[:D]
+            b = folded_bias(bias, scale, shift, C1)
+            assert f["C1"] == C1 and set(f) == {"Wt", "Wxs", "Wd", "b", "C1"}
+            for name, want in (("Wt", Wt), ("Wxs", Wt[D:]), ("Wd", Wd), ("b", b)):
+                got = f[name].numpy()
+                assert f[name].is_contiguous() and got.dtype == np.float32 and got.shape == want.shape, (name, D, C1)
+                assert np.array_equal(got, want) and np.array_equal(np.signbit(got), np.signbit(want)), (name, D, C1)
+            assert np.signbit(f["Wt"].numpy()).any()
+            C1p = F.pad16(C1)
+            for C2 in (48, 200):
+                W2 = f32(C2, C1)
+                W2[::3, ::7] = -0.0
+                bias2, scale2, shift2 = opt("bias", f32(C2)), opt("scale", f32(C2)), opt("shift", f32(C2))
+                W2f, b2 = F.pack_second_layer(torch.from_numpy(W2), bias2, scale2, shift2, C1p)
+                want = np.zeros((C1p // 8, C2, 8), np.float32)
+                for k in range(C1):                                             # W2f[kb][c][i] = scale[c] * W[c, 8 kb + i]
+                    want[k // 8, :, k % 8] = W2[:, k] if scale2 is None else W2[:, k] * scale2.numpy()
+                wb = folded_bias(bias2, scale2, shift2, C2)
+                assert W2f.is_contiguous() and tuple(W2f.shape) == want.shape
+                for got, w in ((W2f.numpy(), want), (b2.numpy(), wb)):
+                    assert np.array_equal(got, w) and np.array_equal(np.signbit(got), np.signbit(w)), (D, C1, C2)
+
+
 def test_derived_operand_memo_follows_storage_swaps_and_copies():
     """toothgroupnetwork_amd/_derived.py: a memoised operand must be rebuilt when a source parameter is written in place (version),
     when its storage is swapped under the same Parameter object (`module.double()`, `.to(device)`, `p.data = ...`: same object, same

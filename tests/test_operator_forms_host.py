@@ -1,7 +1,7 @@
 """CPU: the operator table of tests/operator_forms.py is complete and its form builders do what they say.
 
 Every public callable of toothgroupnetwork_amd.pointops that the reference's pointops.py defines has a row, and so has every
-function or class of pointops, pointnet2_utils, dgcnn, crops, cluster, tsegnet and point_transformer whose source reaches
+function or class of pointops, pointnet2_utils, sa_fused, dgcnn, crops, cluster, tsegnet and point_transformer whose source reaches
 ``ptr(`` (the raw device pointer of a tensor) -- or it is listed in INTERNAL with the row that covers it.  A wrapper added later
 without a row fails here.
 """

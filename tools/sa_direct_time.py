@@ -9,7 +9,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from toothgroupnetwork_amd import _lib, pointnet2_utils as U, synth  # noqa: E402
+from toothgroupnetwork_amd import _lib, pointnet2_utils as U, sa_fused as F, synth  # noqa: E402
 
 dev = torch.device("cuda", 0)
 L = _lib.lib()
@@ -23,16 +23,13 @@ for B, S, K, D, C1, C2, r in ((256, 4096, 32, 6, 64, 128, 0.05), (8, 1024, 32, 6
     new_xyz = U.index_points(xyz, fidx).contiguous()
     gidx = U.query_ball_point(r, K, xyz, new_xyz).int().contiguous()
     g = torch.Generator().manual_seed(0)
-    C1p = (C1 + 15) // 16 * 16
-    Wd = torch.zeros(16, C1p)
-    Wd[:9, :C1] = torch.randn(9, C1, generator=g) / 3.0
-    b1 = torch.zeros(C1p)
-    W2 = torch.zeros(C2, C1p)
-    W2[:, :C1] = torch.randn(C2, C1, generator=g) / C1 ** 0.5
-    W2f = W2.view(C2, C1p // 8, 8).permute(1, 0, 2).contiguous().to(dev)
-    W2s = U.split_second_layer(W2f)
-    b2 = torch.zeros(C2, device=dev)
-    Wd, b1 = Wd.to(dev), b1.to(dev)
+    W1 = (torch.randn(9, C1, generator=g) / 3.0).t()                         # (C1, 3 + D), columns [x, y, z, features...]
+    W2 = torch.randn(C2, C1, generator=g) / C1 ** 0.5
+    first = {k: v.to(dev) if torch.is_tensor(v) else v for k, v in F.pack_first_layer(W1, None, None, None, D, True).items()}
+    second = tuple(t.to(dev) for t in F.pack_second_layer(W2, None, None, None, F.pad16(C1)))
+    plan = F.plan_branch(first, second, K, D, bf16x3=True)
+    assert plan["direct"]
+    C1p, Wd, b1, W2f, W2s, b2 = (plan[k] for k in ("C1p", "W1", "b1", "W2f", "W2s", "b2"))
     out = torch.empty(B, S, C2, device=dev)
 
     def run():

@@ -11,7 +11,7 @@
 //         scale*(W*[x[idx]-c, f[idx]] + bias) + shift  =  A[idx] - Wxs*c + b2,     A = [f, x] * Wt   per POINT,
 //     so the contraction runs over the N points once (tgn_sa_point_transform: an fp32-MFMA GEMM, S*K/N = 8x fewer
 //     flops than per grouped row) and the per-query part is a gather-max of A rows (tgn_sa_gather_max) or the
-//     gather-add-relu of gather.hip's tgn_sa_first_layer when more layers follow.
+//     gather-add-relu of tgn_sa_gather_act when more layers follow.
 // fp32 MFMA (v_mfma_f32_32x32x2_f32) is an exact fp32 fma chain (MI355X_MICROARCH.md): results differ from the
 // reference's BLAS only by summation order (tests: 1e-5 relative to the row magnitude).
 #include "tgn_common.h"

@@ -11,8 +11,9 @@ feature widths D=[6,128,512] (level l>0 groups synthetic features of the width t
 """
 import torch
 
-from . import _lib
+from . import _lib, config
 from ._lib import check, lib, ptr
+from .sa_fused import launch_branch, pack_first_layer, pack_second_layer, pad16, plan_branch
 
 SHAPE_A = dict(n=24000, npoint=[4096, 1024, 256], radius=[0.05, 0.1, 0.2], nsample=[32, 32, 32], d=[6, 128, 512],
                mlp=[[64, 128], [256, 512], [512, 1024]])   # fused mode only: the shared MLP of each level (one or two layers;
@@ -112,8 +113,8 @@ class HotPath:
     run times three launches (plan_schedule).  `plan=dict(spacer_us=.., last_query_early=..)` fixes them instead.
 
     fused=True: every level is a whole set-abstraction level (shape['mlp']: one- or two-layer shared MLP per (radius,
-    nsample) branch, eval-mode BatchNorm folded, synthetic seeded weights): FPS -> ball query -> tgn_sa_mlp2_max /
-    tgn_sa_direct_max / transform + gather-max; the branches of a multi-scale level write side by side into one tensor.  No grouped tensor and no (B,S,K,.) layer output is written; level l's (B,S,C_out) output is level l+1's
+    nsample) branch, eval-mode BatchNorm folded, synthetic seeded weights): FPS -> ball query -> the kernels sa_fused.launch_branch
+    picks, the ones the modules of pointnet2_utils run; the branches of a multi-scale level write side by side into one tensor.  No grouped tensor and no (B,S,K,.) layer output is written; level l's (B,S,C_out) output is level l+1's
     feature input.  These kernels are bound by the fp32 matrix cores and do not fit beside an FPS level-1 workgroup (120 VGPRs,
     62 KiB of LDS): the pipelined fused schedule is FPS + ball queries of step k+1 on stream F over the set-abstraction
     kernels of step k on stream G."""
@@ -215,45 +216,27 @@ class HotPath:
         return levels
 
     def _fused_operands(self, li, N, S, K, D, widths, device):
-        """Folded operands of level li's shared MLP (synthetic, seeded; BatchNorm = identity folded in): `layers` keeps the
-        plain (C_out, C_in) matrices in the [x, y, z, features...] column order and the biases for the parity tests."""
-        f32 = dict(dtype=torch.float32, device=device)
+        """Level li's shared MLP (synthetic, seeded; BatchNorm = identity, so no scale and no shift) as a plan of sa_fused: `layers`
+        keeps the plain (C_out, C_in) matrices in the [x, y, z, features...] column order and the biases for the parity tests."""
         g = torch.Generator(device="cpu").manual_seed(1000 + li)
         widths = list(widths)
         if len(widths) not in (1, 2):
             raise ValueError("HotPath(fused=True): one- or two-layer shared MLPs")
         C1 = widths[0]
-        C1p = (C1 + 15) // 16 * 16 if len(widths) == 2 else C1
         W1 = torch.randn(C1, 3 + D, generator=g) / float(D + 3) ** 0.5           # columns [x, y, z, features...]
         b1 = 0.1 * torch.randn(C1, generator=g)
         layers = [(W1.numpy().copy(), b1.numpy().copy())]
-        Wt = torch.zeros(D + 3, C1p)
-        Wt[:D, :C1], Wt[D:, :C1] = W1[:, 3:].t(), W1[:, :3].t()                   # rows [features..., x, y, z]
-        Wd = torch.zeros(16, C1p)
-        if D + 3 <= 16:
-            Wd[:3], Wd[3:3 + D] = Wt[D:], Wt[:D]
-        b1p = torch.zeros(C1p)
-        b1p[:C1] = b1
-        out = dict(C1=C1, C1p=C1p, C_out=widths[-1], nlayers=len(widths), Wt=Wt.to(device).contiguous(),
-                   Wxs=Wt[D:].to(device).contiguous(), Wd=Wd.to(device), b1=b1p.to(device))
-        if len(widths) == 1:
-            out["direct"] = bool(self.L.tgn_sa_direct_supported(K, D, C1))
-        else:
+        first = {k: v.to(device) if torch.is_tensor(v) else v for k, v in pack_first_layer(W1, b1, None, None, D, True).items()}
+        second = None
+        if len(widths) == 2:
             C2 = widths[1]
             W2 = torch.randn(C2, C1, generator=g) / float(C1) ** 0.5
             b2 = 0.1 * torch.randn(C2, generator=g)
             layers.append((W2.numpy().copy(), b2.numpy().copy()))
-            W2p = torch.zeros(C2, C1p)
-            W2p[:, :C1] = W2
-            out.update(W2f=W2p.view(C2, C1p // 8, 8).permute(1, 0, 2).contiguous().to(device), b2=b2.to(device),
-                       direct=bool(self.L.tgn_sa_mlp2_direct_supported(K, D)))
-            from . import pointnet2_utils as U
-            # second layer on the bf16 matrix cores at fp32 accuracy (tgn_sa_mlp2_max_bf16x3) unless TGN_SA_BF16X3=0
-            out["W2s"] = U.split_second_layer(out["W2f"]) if U.SA_BF16X3 else None
-            out["Wts"] = U.split_point_transform(out["Wt"]) if (U.SA_BF16X3 and not out["direct"]) else None
-        out["layers"] = layers
-        out["A"] = None if out["direct"] else torch.empty(self.B, N, C1p, **f32)
-        return out
+            second = tuple(t.to(device) for t in pack_second_layer(W2, b2, None, None, pad16(C1)))
+        plan = plan_branch(first, second, K, D, bf16x3=config.cfg.sa_bf16x3)
+        return dict(plan=plan, layers=layers, C1=C1, C_out=widths[-1],
+                    A=None if plan["direct"] else torch.empty(self.B, N, plan["C1p"], dtype=torch.float32, device=device))
 
     def _ball(self, lv, br, cur_xyz, st, prebuilt=False):
         fn = self.L.tgn_ball_query_prebuilt if prebuilt else self.L.tgn_ball_query
@@ -271,30 +254,8 @@ class HotPath:
 
     def _sa(self, lv, br, cur_xyz, pts, st):
         """one fused (radius, nsample) branch of a set-abstraction level on stream st"""
-        L, B = self.L, self.B
-        if not br["direct"] and br.get("Wts") is not None and B * lv["N"] <= 65535 * 128:
-            check(L.tgn_sa_point_transform_bf16x3(B * lv["N"], lv["D"], br["Wts"][1], br["C1p"], ptr(cur_xyz), ptr(pts), ptr(br["Wts"][0]),
-                                                  ptr(br["A"]), st), "sa_point_transform_bf16x3")
-        elif not br["direct"]:
-            check(L.tgn_sa_point_transform(B * lv["N"], lv["D"], br["C1p"], ptr(cur_xyz), ptr(pts), ptr(br["Wt"]), ptr(br["A"]), st),
-                  "sa_point_transform")
-        out = br["out"]
-        if br["nlayers"] == 2 and br["W2s"] is not None:
-            return check(L.tgn_sa_mlp2_max_bf16x3(B, lv["N"], lv["S"], br["K"], lv["D"], br["C1p"], br["C_out"], ptr(br["A"]), ptr(cur_xyz),
-                                                  ptr(pts), ptr(lv["new_xyz"]), ptr(br["Wd"] if br["direct"] else br["Wxs"]), ptr(br["b1"]),
-                                                  ptr(br["group_idx"]), self.idx64, ptr(br["W2s"]), ptr(br["b2"]), ptr(out),
-                                                  out.stride(1), st), "sa_mlp2_max_bf16x3")
-        if br["nlayers"] == 2:
-            return check(L.tgn_sa_mlp2_max(B, lv["N"], lv["S"], br["K"], lv["D"], br["C1p"], br["C_out"], ptr(br["A"]), ptr(cur_xyz),
-                                           ptr(pts), ptr(lv["new_xyz"]), ptr(br["Wd"] if br["direct"] else br["Wxs"]), ptr(br["b1"]),
-                                           ptr(br["group_idx"]), self.idx64, ptr(br["W2f"]), ptr(br["b2"]), ptr(out), out.stride(1), st),
-                         "sa_mlp2_max")
-        if br["direct"]:
-            return check(L.tgn_sa_direct_max(B, lv["N"], lv["S"], br["K"], lv["D"], br["C1"], ptr(cur_xyz), ptr(lv["new_xyz"]),
-                                             ptr(pts), ptr(br["Wd"]), ptr(br["b1"]), ptr(br["group_idx"]), self.idx64, 1,
-                                             ptr(out), st), "sa_direct_max")
-        return check(L.tgn_sa_gather_max(B, lv["N"], lv["S"], br["K"], br["C1"], ptr(br["A"]), ptr(lv["new_xyz"]), ptr(br["Wxs"]),
-                                         ptr(br["b1"]), ptr(br["group_idx"]), self.idx64, 1, ptr(out), st), "sa_gather_max")
+        return launch_branch(br["plan"], self.B, lv["N"], lv["S"], cur_xyz, lv["new_xyz"], pts, br["group_idx"], self.idx64, br["out"],
+                             br["A"], st)
 
     def _consume(self, i, lv, cur_xyz, feats, levels, st):
         """what follows the ball query of level i: the grouping (materialised) or the fused level"""

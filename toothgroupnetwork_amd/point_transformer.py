@@ -27,6 +27,7 @@ from torch.autograd import Function
 
 from . import _derived, _lib, pointnet2_utils as _U, pointops
 from ._lib import check, lib, ptr, stream
+from .sa_fused import bn_scale_shift as _bn_scale_shift, pack_first_layer
 
 _fwd = torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
 _bwd = torch.amp.custom_bwd(device_type="cuda")
@@ -241,11 +242,6 @@ def mlp_train(seq, t):
     return t
 
 
-def _bn_scale_shift(bn):
-    s = (bn.weight.detach() / torch.sqrt(bn.running_var + bn.eps)).float()
-    return s, (bn.bias.detach() - bn.running_mean * s).float()
-
-
 def folded_linear(lin, bn):
     """(W', b') with eval-mode `bn` folded into `lin`: bn(lin(x)) == x @ W'.T + b'; memoised on `bn`."""
     def fold():
@@ -427,10 +423,9 @@ class TransitionDown(nn.Module):
             m = n_p.shape[0]
 
             def fold():
-                s, t = _bn_scale_shift(self.bn)
-                W = self.linear.weight.detach().float()                    # (C1, 3+c), columns [xyz, features] (use_xyz=True)
-                Wt = torch.cat([W[:, 3:], W[:, :3]], 1).mul(s[:, None]).t().contiguous()   # rows [features..., x, y, z]
-                return Wt, Wt[c:].contiguous(), t.contiguous()
+                s, t = _bn_scale_shift(self.bn)                            # (the linear layer has no bias)
+                f = pack_first_layer(self.linear.weight.detach().float(), None, s, t, c, True)   # columns [xyz, features] (use_xyz=True)
+                return f["Wt"], f["Wxs"], f["b"]
             Wt, Wxyz, t = _derived.cached(self, "down", _derived.sources(self.linear, self.bn), c, fold)
             A = torch.empty(n, C1, dtype=torch.float32, device=x.device)
             L = lib()

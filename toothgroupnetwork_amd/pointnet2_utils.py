@@ -30,6 +30,8 @@ from . import _derived, _lib, config
 from . import _fps_prefix
 from ._fps_prefix import PrefixBook
 from ._lib import as_int, check, lib, ptr, require_cuda, stream
+from .sa_fused import (_f32c, bn_scale_shift, fold_first_layer, fold_second_layer, pad16, sa_all_mlp2_max,  # noqa: F401
+                       sa_first_layer, sa_level_max, sa_level_mlp2_max, sa_point_transform, split_point_transform, split_second_layer)
 
 _fwd = torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
 _bwd = torch.amp.custom_bwd(device_type="cuda")
@@ -46,26 +48,6 @@ def pc_normalize(pc):
     m = np.max(np.sqrt(np.sum(pc ** 2, axis=1)))
     pc = pc / m
     return pc
-
-
-def _f32c(t):
-    t = t if t.dtype == torch.float32 else t.float()
-    return t if t.is_contiguous() else t.contiguous()
-
-
-def _idxc(idx):
-    """Index tensors reach the kernels as packed int64 or int32 (a flag tells which); any other integer width is widened."""
-    if idx.dtype not in (torch.int64, torch.int32):
-        idx = idx.long()
-    return idx if idx.is_contiguous() else idx.contiguous()
-
-
-def _sa_operands(xyz, new_xyz, points, idx):
-    """The tensor arguments of the fused set-abstraction entries as the kernels read them: packed fp32 rows, packed indices.  The
-    modules pass them in that form already (then nothing is copied); a direct caller may pass any floating dtype or layout."""
-    require_cuda(xyz, new_xyz, points, idx)
-    return (_f32c(xyz.detach()), None if new_xyz is None else _f32c(new_xyz.detach()), None if points is None else _f32c(points.detach()),
-            None if idx is None else _idxc(idx))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -452,12 +434,13 @@ def three_interpolate(points2, dist, idx):
 
 
 # ---------------------------------------------------------------------------------------------
-# fused set abstraction (eval mode): the first shared-MLP layer without the grouped (B,S,K,3+D) tensor
+# fused set abstraction (eval mode): WHEN the modules below take the fused kernels.  Operand layout, kernel choice and the
+# operators (sa_level_max, sa_level_mlp2_max, sa_first_layer, sa_all_mlp2_max) are sa_fused.py's; the modules call them through
+# this module's names.
 # ---------------------------------------------------------------------------------------------
 # The switches of this module live in toothgroupnetwork_amd.config (cfg.fused_sa, cfg.commute_fp -- feature propagation: first
-# convolution on the coarse points, below --, cfg.sa_bf16x3 -- second layer of the chained set-abstraction kernel on the bf16 matrix
-# cores at fp32 accuracy: three-way bf16 split of both operands, six products, include/tgn_pointops.h tgn_sa_mlp2_max_bf16x3; False:
-# the exact-fp32 MFMA form).  FUSED_SA / COMMUTE_FP / SA_BF16X3 remain as live aliases of those fields (reads and writes).
+# convolution on the coarse points, below --, cfg.sa_bf16x3 -- sa_fused.plan_branch).  FUSED_SA / COMMUTE_FP / SA_BF16X3 remain as
+# live aliases of those fields (reads and writes).
 config.legacy_attributes(__name__, {"FUSED_SA": "fused_sa", "COMMUTE_FP": "commute_fp", "SA_BF16X3": "sa_bf16x3"})
 
 
@@ -479,226 +462,9 @@ def _fuse_pays(N, S, K, c_in, c1):
     return S * K * c_in > N * c1
 
 
-def fold_first_layer(conv, bn, D, xyz_first):
-    """The first Conv2d(1x1) + eval-mode BatchNorm2d of a shared MLP as the operands of the fused kernels
-    (include/tgn_pointops.h): scale = gamma/sqrt(var+eps) goes into the weight columns, shift + scale*bias into b2.
-      Wt  (D+3, C1) rows [features..., x, y, z]   -- tgn_sa_point_transform
-      Wxs (3, C1)   the x, y, z rows of Wt        -- centre term of tgn_sa_gather_max / tgn_sa_gather_act
-      Wd  (16, C1)  rows [x, y, z, features..., 0] -- tgn_sa_direct_max
-      b2  (C1,)
-    Memoised on `bn` until a parameter / running statistic of the two modules changes (_derived.cached)."""
-    return _derived.cached(bn, "first_layer", _derived.sources(conv, bn), (D, bool(xyz_first)),
-                           lambda: _fold_first_layer(conv, bn, D, xyz_first))
-
-
-def _fold_first_layer(conv, bn, D, xyz_first):
-    C1 = conv.out_channels
-    W = conv.weight.detach().reshape(C1, -1).float()                       # (C1, 3+D) in the module's channel order
-    bias = conv.bias.detach().float() if conv.bias is not None else torch.zeros(C1, device=W.device)
-    scale = (bn.weight.detach() / torch.sqrt(bn.running_var + bn.eps)).float()
-    shift = (bn.bias.detach() - bn.running_mean * scale).float()
-    Wx, Wp = (W[:, :3], W[:, 3:]) if xyz_first else (W[:, D:], W[:, :D])   # sample_and_group: [xyz, feat]; Msg: [feat, xyz]
-    Ws = W.new_empty(C1, 3 + D)
-    Ws[:, :D], Ws[:, D:] = Wp * scale[:, None], Wx * scale[:, None]
-    Wt = Ws.t().contiguous()                                               # (D+3, C1): [features..., x, y, z]
-    Wd = W.new_zeros(16, C1)
-    if 3 + D <= 16:
-        Wd[:3], Wd[3:3 + D] = Wt[D:], Wt[:D]
-    return dict(Wt=Wt, Wxs=Wt[D:].contiguous(), Wd=Wd, b2=(shift + scale * bias).contiguous(), C1=C1)
-
-
-def split_point_transform(Wt):
-    """The bf16 x 3 image of a per-point first-layer matrix Wt (D+3, C1) for tgn_sa_point_transform_bf16x3: rows padded with zeros
-    to a multiple of 16, arranged (Kp/8, C1, 8) and split like a second layer (tgn_sa_mlp2_split_weights)."""
-    Kc, C1 = Wt.shape
-    Kp = (Kc + 15) // 16 * 16
-    Wp = Wt.new_zeros(Kp, C1)
-    Wp[:Kc] = Wt
-    return split_second_layer(Wp.view(Kp // 8, 8, C1).permute(0, 2, 1).contiguous()), Kp
-
-
-def sa_point_transform(xyz, points, Wt, Wts=None):
-    """A[b,n,:] = [points[b,n,:], xyz[b,n,:]] @ Wt -- the per-POINT half of a fused first layer, on the matrix cores.
-    xyz (B,N,3), points (B,N,D) or None, Wt (D+3, C1) -> (B,N,C1).  Wts = split_point_transform(Wt): the bf16 x 3 form
-    (tgn_sa_point_transform_bf16x3, fp32-class rounding at up to 2.7x the rate); None: exact fp32 MFMA (tgn_sa_point_transform)."""
-    xyz, _, points, _ = _sa_operands(xyz, None, points, None)
-    Wt = _f32c(Wt)
-    B, N, _ = xyz.shape
-    D = 0 if points is None else points.shape[2]
-    if Wt.dim() != 2 or Wt.shape[0] != D + 3:
-        raise ValueError(f"sa_point_transform: Wt must be ({D + 3}, C1) for points with {D} channels, got {tuple(Wt.shape)}")
-    C1 = Wt.shape[1]
-    A = torch.empty(B, N, C1, dtype=torch.float32, device=xyz.device)
-    if Wts is not None and B * N <= 65535 * 128:
-        img, Kp = Wts
-        check(lib().tgn_sa_point_transform_bf16x3(B * N, D, Kp, C1, ptr(xyz), ptr(points), ptr(img), ptr(A), stream()), "sa_point_transform_bf16x3")
-    else:
-        check(lib().tgn_sa_point_transform(B * N, D, C1, ptr(xyz), ptr(points), ptr(Wt), ptr(A), stream()), "sa_point_transform")
-    return A
-
-
-def sa_level_max(xyz, new_xyz, points, idx, conv, bn, xyz_first):
-    """A whole single-layer set-abstraction level after sampling and ball query:
-        max_k relu(bn(conv([xyz[idx]-new_xyz, points[idx]])))  ->  (B,S,C1)
-    (pointnet2_utils.py:162-169 + 229-236, or 281-294 for Msg) with nothing of size S*K ever written: narrow inputs go
-    through the direct kernel (gather -> matrix cores -> max), wide ones through the per-point transform + gather-max."""
-    xyz, new_xyz, points, idx = _sa_operands(xyz, new_xyz, points, idx)
-    B, N, _ = xyz.shape
-    _, S, K = idx.shape
-    D = 0 if points is None else points.shape[2]
-    f = fold_first_layer(conv, bn, D, xyz_first)
-    C1 = f["C1"]
-    out = torch.empty(B, S, C1, dtype=torch.float32, device=xyz.device)
-    L = lib()
-    _lib.begin_index_check()
-    if L.tgn_sa_direct_supported(K, D, C1):
-        check(L.tgn_sa_direct_max(B, N, S, K, D, C1, ptr(xyz), ptr(new_xyz), ptr(points), ptr(f["Wd"]), ptr(f["b2"]), ptr(idx),
-                                  int(idx.dtype == torch.int64), 1, ptr(out), stream()), "sa_direct_max")
-    else:
-        A = sa_point_transform(xyz, points, f["Wt"])
-        check(L.tgn_sa_gather_max(B, N, S, K, C1, ptr(A), ptr(new_xyz), ptr(f["Wxs"]), ptr(f["b2"]), ptr(idx),
-                                  int(idx.dtype == torch.int64), 1, ptr(out), stream()), "sa_gather_max")
-    _lib.raise_on_index_error("set abstraction (grouping)")
-    return out
-
-
-def sa_first_layer(xyz, new_xyz, points, idx, conv, bn, xyz_first, reduce_max=False):
-    """relu(bn(conv(grouped))) of the FIRST shared-MLP layer without ever building `grouped`
-    (pointnet2_utils.py:162-169 + 229-233, or 281-292 for Msg).  The 1x1 convolution commutes with the gather:
-        W*[points[idx], xyz[idx]-c] + b = (W_p*points + W_x*xyz)[idx] + (b - W_x*c)
-    so the contraction runs over the N points (tgn_sa_point_transform, fp32 MFMA) instead of the S*K grouped rows and
-    the per-query kernel only gathers, adds the centre term and applies ReLU.  Returns (B,S,K,C1), or (B,S,C1) with
-    reduce_max (= sa_level_max).  Eval-mode BatchNorm statistics are folded in."""
-    if reduce_max:
-        return sa_level_max(xyz, new_xyz, points, idx, conv, bn, xyz_first)
-    xyz, new_xyz, points, idx = _sa_operands(xyz, new_xyz, points, idx)
-    B, N, _ = xyz.shape
-    _, S, K = idx.shape
-    D = 0 if points is None else points.shape[2]
-    f = fold_first_layer(conv, bn, D, xyz_first)
-    C1 = f["C1"]
-    A = sa_point_transform(xyz, points, f["Wt"])
-    out = torch.empty(B, S, K, C1, dtype=torch.float32, device=xyz.device)
-    _lib.begin_index_check()
-    check(lib().tgn_sa_gather_act(B, N, S, K, C1, ptr(A), ptr(new_xyz), ptr(f["Wxs"]), ptr(f["b2"]), ptr(idx),
-                                  int(idx.dtype == torch.int64), 1, ptr(out), stream()), "sa_gather_act")
-    _lib.raise_on_index_error("set abstraction (grouping)")
-    return out
-
-
-def fold_second_layer(conv, bn, C1p):
-    """The second Conv2d(1x1) + eval-mode BatchNorm2d of a shared MLP as the operands of tgn_sa_mlp2_max:
-      W2f (C1p/8, C2, 8): W2f[kb, c, i] = scale[c] * W[c, 8*kb + i], zero for the padded input channels
-      b2  (C2,)          = shift + scale * bias"""
-    return _derived.cached(bn, "second_layer", _derived.sources(conv, bn), C1p, lambda: _fold_second_layer(conv, bn, C1p))
-
-
-def _fold_second_layer(conv, bn, C1p):
-    C2, C1 = conv.out_channels, conv.in_channels
-    W = conv.weight.detach().reshape(C2, C1).float()
-    bias = conv.bias.detach().float() if conv.bias is not None else torch.zeros(C2, device=W.device)
-    scale = (bn.weight.detach() / torch.sqrt(bn.running_var + bn.eps)).float()
-    shift = (bn.bias.detach() - bn.running_mean * scale).float()
-    Wp = W.new_zeros(C2, C1p)
-    Wp[:, :C1] = W * scale[:, None]
-    W2f = Wp.view(C2, C1p // 8, 8).permute(1, 0, 2).contiguous()
-    return W2f, (shift + scale * bias).contiguous()
-
-
-def split_second_layer(W2f):
-    """The bf16 x 3 image of a folded second-layer weight matrix W2f (C1p/8, C2, 8) for tgn_sa_mlp2_max_bf16x3."""
-    C1p, C2 = W2f.shape[0] * 8, W2f.shape[1]
-    img = torch.empty(int(lib().tgn_sa_mlp2_split_bytes(C1p, C2)), dtype=torch.uint8, device=W2f.device)
-    check(lib().tgn_sa_mlp2_split_weights(C1p, C2, ptr(W2f), ptr(img), stream()), "sa_mlp2_split_weights")
-    return img
-
-
-def _pad_cols(t, C1p):
-    if t.shape[-1] == C1p:
-        return t.contiguous()
-    out = t.new_zeros(t.shape[:-1] + (C1p,))
-    out[..., :t.shape[-1]] = t
-    return out
-
-
-def sa_level_mlp2_max(xyz, new_xyz, points, idx, convs, bns, xyz_first, out=None):
-    """A whole set-abstraction level with a TWO-layer shared MLP after sampling and ball query:
-        max_k relu(bn2(conv2(relu(bn1(conv1([xyz[idx]-new_xyz, points[idx]]))))))  ->  (B,S,C2)
-    (pointnet2_utils.py:162-169 + 229-236, or 281-294 for Msg) in ONE kernel after the per-point transform of the first
-    layer (wide inputs) or with the first layer computed from the gathered rows (3+D <= 16): nothing of size S*K is
-    written, no torch convolution runs (tgn_sa_mlp2_max; the second layer on the fp32 matrix cores).  out: optional (B,S,C2)
-    view into a wider row-major tensor (last stride 1) -- a multi-scale level writes its branches side by side."""
-    xyz, new_xyz, points, idx = _sa_operands(xyz, new_xyz, points, idx)
-    B, N, _ = xyz.shape
-    _, S, K = idx.shape
-    D = 0 if points is None else points.shape[2]
-    L = lib()
-    direct = bool(L.tgn_sa_mlp2_direct_supported(K, D))
-
-    def operands():   # (memoised on the second BatchNorm: ~40 small launches per branch otherwise, every forward)
-        f = fold_first_layer(convs[0], bns[0], D, xyz_first)
-        C1p = (f["C1"] + 15) // 16 * 16
-        W2f, b2 = fold_second_layer(convs[1], bns[1], C1p)
-        return dict(C1p=C1p, W2f=W2f, b2=b2, b1=_pad_cols(f["b2"], C1p), W2s=split_second_layer(W2f) if config.cfg.sa_bf16x3 else None,
-                    W1=_pad_cols(f["Wd"] if direct else f["Wxs"], C1p),      # direct: (16, C1p) rows [x, y, z, features..., 0]
-                    Wt=None if direct else _pad_cols(f["Wt"], C1p),
-                    Wts=split_point_transform(_pad_cols(f["Wt"], C1p)) if (config.cfg.sa_bf16x3 and not direct) else None)
-    ops = _derived.cached(bns[1], "mlp2", _derived.sources(convs[0], bns[0], convs[1], bns[1]), (D, bool(xyz_first), direct, config.cfg.sa_bf16x3),
-                          operands)
-    C1p, W2f, b2, b1, W1 = ops["C1p"], ops["W2f"], ops["b2"], ops["b1"], ops["W1"]
-    C2 = b2.shape[0]
-    if out is None:
-        out = torch.empty(B, S, C2, dtype=torch.float32, device=xyz.device)
-    if out.dtype != torch.float32 or out.device != xyz.device:
-        raise TypeError(f"sa_level_mlp2_max: out must be float32 on {xyz.device}, got {out.dtype} on {out.device}")
-    if tuple(out.shape) != (B, S, C2) or out.stride(2) != 1 or out.stride(0) != S * out.stride(1):
-        raise ValueError(f"sa_level_mlp2_max: out must be ({B}, {S}, {C2}) with unit last stride and evenly spaced rows, got "
-                         f"{tuple(out.shape)} with strides {tuple(out.stride())}")
-    A1 = None if direct else sa_point_transform(xyz, points, ops["Wt"], ops["Wts"])      # (B, N, C1p)
-    _lib.begin_index_check()
-    if ops["W2s"] is not None:
-        check(L.tgn_sa_mlp2_max_bf16x3(B, N, S, K, D, C1p, C2, ptr(A1), ptr(xyz), ptr(points), ptr(new_xyz), ptr(W1), ptr(b1), ptr(idx),
-                                       int(idx.dtype == torch.int64), ptr(ops["W2s"]), ptr(b2), ptr(out), out.stride(1), stream()),
-              "sa_mlp2_max_bf16x3")
-    else:
-        check(L.tgn_sa_mlp2_max(B, N, S, K, D, C1p, C2, ptr(A1), ptr(xyz), ptr(points), ptr(new_xyz), ptr(W1), ptr(b1), ptr(idx),
-                                int(idx.dtype == torch.int64), ptr(W2f), ptr(b2), ptr(out), out.stride(1), stream()), "sa_mlp2_max")
-    _lib.raise_on_index_error("set abstraction (grouping)")
-    return out
-
-
-def sa_all_mlp2_max(xyz, points, convs, bns):
-    """PointNetSetAbstraction(group_all=True) with a two-layer shared MLP, eval mode (pointnet2_utils.py:178-195 + 229-236; the one
-    instantiation is tsg_seg_module.py:28, 515 -> [256, 512] over 256 points):
-        max_n relu(bn2(conv2(relu(bn1(conv1([xyz_n, points_n]))))))  ->  (B, C2)
-    The first layer runs once per point on the fp32 matrix cores (tgn_sa_point_transform; 3+D <= 16: inside the kernel), the second
-    layer and the maximum over the cloud in tgn_sa_all_mlp2_max: no (B,1,N,.) tensor, no torch convolution."""
-    xyz, _, points, _ = _sa_operands(xyz, None, points, None)
-    B, N, _ = xyz.shape
-    D = 0 if points is None else points.shape[2]
-    L = lib()
-    direct = bool(L.tgn_sa_mlp2_direct_supported(min(N, 64), D))
-
-    def operands():
-        f = fold_first_layer(convs[0], bns[0], D, True)
-        C1p = (f["C1"] + 15) // 16 * 16
-        W2f, b2 = fold_second_layer(convs[1], bns[1], C1p)
-        return dict(C1p=C1p, W2f=W2f, b2=b2, b1=_pad_cols(f["b2"], C1p), Wd=_pad_cols(f["Wd"], C1p) if direct else None,
-                    Wt=None if direct else _pad_cols(f["Wt"], C1p))
-    ops = _derived.cached(bns[1], "all_mlp2", _derived.sources(convs[0], bns[0], convs[1], bns[1]), (D, direct), operands)
-    C2 = ops["b2"].shape[0]
-    out = torch.empty(B, C2, dtype=torch.float32, device=xyz.device)
-    chunks = int(L.tgn_sa_all_chunks(N))
-    part = torch.empty(B, chunks, C2, dtype=torch.float32, device=xyz.device) if chunks > 1 else None
-    A1 = None if direct else sa_point_transform(xyz, points, ops["Wt"])
-    check(L.tgn_sa_all_mlp2_max(B, N, D, ops["C1p"], C2, ptr(A1), ptr(xyz), ptr(points), ptr(ops["Wd"]), ptr(ops["b1"]),
-                                ptr(ops["W2f"]), ptr(ops["b2"]), ptr(part), ptr(out), C2, stream()), "sa_all_mlp2_max")
-    return out
-
-
 def _mlp2_shape_ok(K, C1):
     """tgn_sa_mlp2_max keeps the per-query constants of its 4 (K <= 32) or 2 queries in LDS next to the tile buffers."""
-    return 1 <= K <= 64 and (4 if K <= 32 else 2) * ((C1 + 15) // 16 * 16) <= 8192
+    return 1 <= K <= 64 and (4 if K <= 32 else 2) * pad16(C1) <= 8192
 
 
 def _fused_level(xyz_c, new_xyz, points_c, idx, convs, bns, xyz_first, N, S, K):
@@ -887,8 +653,7 @@ class PointNetFeaturePropagation(nn.Module):
                 def fold():
                     out = []
                     for conv, bn in zip(self.mlp_convs, self.mlp_bns):
-                        sc = (bn.weight.detach() / torch.sqrt(bn.running_var + bn.eps)).float()
-                        sh = (bn.bias.detach() - bn.running_mean * sc).float()
+                        sc, sh = bn_scale_shift(bn)
                         Wc = conv.weight.detach().squeeze(-1).float()
                         bias = conv.bias.detach().float() if conv.bias is not None else torch.zeros_like(sh)
                         out.append(((Wc * sc[:, None]).contiguous(), (bias * sc + sh).contiguous()))
