@@ -68,6 +68,19 @@ def test_ctypes_table_matches_header():
     assert L.tgn_ball_query_workspace_bytes(1, 24000, 4096) >= 0
 
 
+def test_knnquery_refuses_more_than_128_neighbours_before_any_launch():
+    """The exact-heap kernel keeps kKnnHeapMax = 128 entries per query in LDS and there is no other kernel behind it: a larger
+    nsample is TGN_ERR_UNSUPPORTED with its message.  The check comes before the first HIP call (the buffers are never
+    touched), so it holds without a device."""
+    from toothgroupnetwork_amd import _lib
+    L = _lib.lib()
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    rc = L.tgn_knnquery(1, 1, 129, p, p, p, p, p, p, None)
+    assert rc == _lib.ERR_UNSUPPORTED
+    assert L.tgn_last_error().decode() == "tgn_knnquery: nsample 129 > 128 unsupported (the reference's limit is 100)"
+
+
 def test_ops_refuse_cpu_tensors_loudly():
     from toothgroupnetwork_amd import pointnet2_utils as U, pointops as P
     xyz = torch.rand(1, 64, 3)

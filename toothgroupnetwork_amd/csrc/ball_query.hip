@@ -24,7 +24,7 @@
 // r_eff * 1.001 wide or wider and cell coordinates of points and queries come from the same fp32
 // expression, so such a point is at most one cell away on every axis.  Clouds containing non-finite
 // coordinates (NaN compares as "inside" in the reference) take the scan path.
-#include "tgn_common.h"
+#include "grid_common.h"
 
 #include <stdlib.h>
 
@@ -67,8 +67,7 @@ __global__ __launch_bounds__(256) void ball_query_scan_kernel(int B, int N, int 
     const int lane = threadIdx.x & (kWave - 1);
     const int wpb = blockDim.x / kWave;
     const long long total = (long long)B * S;
-    const unsigned nb = gridDim.x;  // a multiple of 8; XCD-aware order, see ball_grid_query_kernel
-    const unsigned lb = (blockIdx.x & 7u) * (nb >> 3) + (blockIdx.x >> 3);
+    const unsigned nb = gridDim.x, lb = xcd_block_order();  // nb is a multiple of 8
     for (long long q = (long long)lb * wpb + __builtin_amdgcn_readfirstlane(threadIdx.x / kWave); q < total; q += (long long)nb * wpb) {
         const int b = (int)(q / S);
         ball_scan_row<IdxT>(N, K, r2, xyz + (size_t)b * N * 3, new_xyz[q * 3 + 0], new_xyz[q * 3 + 1],
@@ -79,19 +78,9 @@ __global__ __launch_bounds__(256) void ball_query_scan_kernel(int B, int N, int 
 // ------------------------------------------------------------------------------------------------
 // grid path
 // ------------------------------------------------------------------------------------------------
-constexpr int kGridCells = 16384;   // cells per cloud (LDS histogram: 64 KiB)
-constexpr int kGridThreads = 1024;
 constexpr int kHitCap = 512;        // per-wave hit buffer (indices)
 constexpr int kGridMaxK = 256;
 constexpr int kGridPermCap = 32768;   // clouds up to here sort through an LDS permutation of 16-bit point numbers
-
-struct GridHeader {   // one per cloud, 64 bytes
-    float lo[3];
-    float inv_h;
-    int g[3];
-    int use_scan;     // 1: this cloud must take the scan path (non-finite data, degenerate grid)
-    int pad[8];
-};
 
 // Per-cloud workspace: header | cell_start[kGridCells+1] (padded to 16 B) | N records float4(x, y, z, |p|^2) sorted by cell |
 // N int32 point indices in the same order.  The squared norm is the `sumsq3` the distance test needs (same expression, computed
@@ -100,24 +89,6 @@ constexpr size_t kGridRecOff = sizeof(GridHeader) + (size_t)((kGridCells + 1 + 3
 __host__ __device__ inline size_t grid_idx_off(int N) { return kGridRecOff + (size_t)N * sizeof(float4); }
 __host__ __device__ inline size_t grid_cloud_bytes(int N) { return grid_idx_off(N) + (size_t)((N + 3) / 4 * 4) * sizeof(int); }
 
-__device__ __forceinline__ int cell_coord(float p, float lo, float inv_h, int g) {
-    // identical expression for points and queries; clamped to [-1, g] so far-away queries stay comparable
-    float t = (p - lo) * inv_h;
-    t = fminf(fmaxf(t, -1.0f), (float)g);
-    return (int)floorf(t);
-}
-
-__device__ __forceinline__ float wave_min_f32(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_max_f32(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
 __global__ __launch_bounds__(kGridThreads) void ball_grid_build_kernel(int N, float r2, const float *__restrict__ xyz,
                                                                         unsigned char *__restrict__ ws) {
     __shared__ int cnt[kGridCells];
@@ -125,7 +96,7 @@ __global__ __launch_bounds__(kGridThreads) void ball_grid_build_kernel(int N, fl
     __shared__ float red[7][kGridThreads / kWave];
     __shared__ int wave_tot[kGridThreads / kWave];
     __shared__ GridHeader hdr_s;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.x, tid = threadIdx.x;
     const float *__restrict__ pts = xyz + (size_t)b * N * 3;
     unsigned char *base = ws + (size_t)b * grid_cloud_bytes(N);
     GridHeader *hdr = (GridHeader *)base;
@@ -134,70 +105,24 @@ __global__ __launch_bounds__(kGridThreads) void ball_grid_build_kernel(int N, fl
     int *ridx = (int *)(base + grid_idx_off(N));
 
     // 1. bounding box, largest |coordinate|, non-finite census
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    float bad = 0.0f;
-    for (int k = tid; k < N; k += kGridThreads) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float v = pts[(size_t)k * 3 + a];
-            if (!(fabsf(v) <= 3.0e38f)) bad = 1.0f;  // NaN or inf
-            lo[a] = fminf(lo[a], v);
-            hi[a] = fmaxf(hi[a], v);
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float l = wave_min_f32(lo[a]), h = wave_max_f32(hi[a]);
-        if (lane == 0) {
-            red[a][wave] = l;
-            red[3 + a][wave] = h;
-        }
-    }
-    {
-        const float bb = wave_max_f32(bad);
-        if (lane == 0) red[6][wave] = bb;
-    }
+    grid_box_partials<kGridThreads>(pts, N, 3.0e38f /* NaN or inf */, red);
     for (int i = tid; i < kGridCells; i += kGridThreads) cnt[i] = 0;
     __syncthreads();
     if (tid == 0) {
         GridHeader h;
-        float ext[3], m = 0.0f, any_bad = 0.0f;
-        for (int a = 0; a < 3; ++a) {
-            float l = INFINITY, u = -INFINITY;
-            for (int w = 0; w < kGridThreads / kWave; ++w) {
-                l = fminf(l, red[a][w]);
-                u = fmaxf(u, red[3 + a][w]);
-            }
-            h.lo[a] = l;
-            ext[a] = u - l;
-            m = fmaxf(m, fmaxf(fabsf(l), fabsf(u)));
-        }
-        for (int w = 0; w < kGridThreads / kWave; ++w) any_bad = fmaxf(any_bad, red[6][w]);
+        float hi[3], ext[3], m = 0.0f;
+        const float any_bad = grid_box_collect(red, h.lo, hi, ext);
+        for (int a = 0; a < 3; ++a) m = fmaxf(m, fmaxf(fabsf(h.lo[a]), fabsf(hi[a])));
         // queries may lie outside the points' box; their coordinates are bounded by the caller's data too,
         // but to stay safe the margin uses 4*M^2 (|q| up to 2M from the box still covered)
         const float r_eff = sqrtf(fmaxf(r2, 0.0f) + 4.0e-5f * m * m) * 1.001f + 1e-30f;
         float hcell = r_eff;
-        int g[3];
-        for (int it = 0; it < 64; ++it) {
-            const float inv = 1.0f / hcell;
-            long long cells = 1;
-            for (int a = 0; a < 3; ++a) {
-                const float t = ext[a] * inv;   // same expression as cell_coord(hi) -> floor(t) = g-1
-                g[a] = (t < 1.0e6f) ? (int)floorf(t) + 1 : 1000001;
-                cells *= g[a];
-            }
-            if (cells <= kGridCells) break;
-            hcell *= 1.1f;
-        }
+        const long long cells = grid_fit(ext, hcell, 64, h.g);
+        h.h = hcell;
         h.inv_h = 1.0f / hcell;
-        long long cells = 1;
-        for (int a = 0; a < 3; ++a) {
-            h.g[a] = g[a];
-            cells *= g[a];
-        }
         // degenerate grids (everything in a handful of cells) cannot prune: the early-exit scan is better
         h.use_scan = (any_bad > 0.0f || !(r2 >= 0.0f) || cells > kGridCells || cells < 8 || N == 0) ? 1 : 0;
-        for (int i = 0; i < 8; ++i) h.pad[i] = 0;
+        for (int i = 0; i < 7; ++i) h.pad[i] = 0;
         hdr_s = h;
         *hdr = h;
     }
@@ -206,42 +131,11 @@ __global__ __launch_bounds__(kGridThreads) void ball_grid_build_kernel(int N, fl
     if (h.use_scan) return;
 
     // 2. histogram
-    for (int k = tid; k < N; k += kGridThreads) {
-        const int cx = cell_coord(pts[(size_t)k * 3 + 0], h.lo[0], h.inv_h, h.g[0]);
-        const int cy = cell_coord(pts[(size_t)k * 3 + 1], h.lo[1], h.inv_h, h.g[1]);
-        const int cz = cell_coord(pts[(size_t)k * 3 + 2], h.lo[2], h.inv_h, h.g[2]);
-        atomicAdd(&cnt[(cz * h.g[1] + cy) * h.g[0] + cx], 1);
-    }
+    for (int k = tid; k < N; k += kGridThreads)
+        atomicAdd(&cnt[grid_cell_of<cell_coord>(h, pts[(size_t)k * 3 + 0], pts[(size_t)k * 3 + 1], pts[(size_t)k * 3 + 2])], 1);
     __syncthreads();
-    // 3. exclusive scan of the histogram: 16 cells per thread, wave scan, block scan
-    constexpr int PER = kGridCells / kGridThreads;
-    int local[PER];
-    int sum = 0;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-        local[i] = sum;
-        sum += cnt[tid * PER + i];
-    }
-    int incl = sum;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const int v = __shfl_up(incl, o);
-        if (lane >= o) incl += v;
-    }
-    if (lane == kWave - 1) wave_tot[wave] = incl;
-    __syncthreads();
-    int wave_base = 0;
-    for (int w = 0; w < wave; ++w) wave_base += wave_tot[w];
-    const int thread_base = wave_base + incl - sum;
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-        const int v = thread_base + local[i];
-        cell_start[tid * PER + i] = v;
-        cnt[tid * PER + i] = v;  // running insert position
-    }
-    if (tid == kGridThreads - 1) cell_start[kGridCells] = thread_base + sum;
-    __syncthreads();
+    // 3. exclusive scan of the histogram; cnt then holds the running insert positions
+    grid_scan_cells<kGridCells, kGridThreads>(cnt, wave_tot, cell_start);
     // 4. scatter (order inside a cell is arbitrary: the query kernel rank-selects by index).
     // Clouds of <= 32 768 points: the scatter goes into an LDS permutation (2 bytes per point) and the records are then written
     // in sorted order -- whole lines, 16 B per lane -- with the coordinates gathered from the cloud (288 KB at 24 000 points: L2 /
@@ -249,10 +143,8 @@ __global__ __launch_bounds__(kGridThreads) void ball_grid_build_kernel(int N, fl
     // lines evicted and fetched again (profiles/r05_pmc_traffic.json).
     if (N <= kGridPermCap) {
         for (int k = tid; k < N; k += kGridThreads) {
-            const int cx = cell_coord(pts[(size_t)k * 3 + 0], h.lo[0], h.inv_h, h.g[0]);
-            const int cy = cell_coord(pts[(size_t)k * 3 + 1], h.lo[1], h.inv_h, h.g[1]);
-            const int cz = cell_coord(pts[(size_t)k * 3 + 2], h.lo[2], h.inv_h, h.g[2]);
-            perm[atomicAdd(&cnt[(cz * h.g[1] + cy) * h.g[0] + cx], 1)] = (unsigned short)k;
+            const int c = grid_cell_of<cell_coord>(h, pts[(size_t)k * 3 + 0], pts[(size_t)k * 3 + 1], pts[(size_t)k * 3 + 2]);
+            perm[atomicAdd(&cnt[c], 1)] = (unsigned short)k;
         }
         __syncthreads();
 #pragma unroll 4
@@ -266,10 +158,7 @@ __global__ __launch_bounds__(kGridThreads) void ball_grid_build_kernel(int N, fl
     }
     for (int k = tid; k < N; k += kGridThreads) {
         const float px = pts[(size_t)k * 3 + 0], py = pts[(size_t)k * 3 + 1], pz = pts[(size_t)k * 3 + 2];
-        const int cx = cell_coord(px, h.lo[0], h.inv_h, h.g[0]);
-        const int cy = cell_coord(py, h.lo[1], h.inv_h, h.g[1]);
-        const int cz = cell_coord(pz, h.lo[2], h.inv_h, h.g[2]);
-        const int pos = atomicAdd(&cnt[(cz * h.g[1] + cy) * h.g[0] + cx], 1);
+        const int pos = atomicAdd(&cnt[grid_cell_of<cell_coord>(h, px, py, pz)], 1);
         rec[pos] = make_float4(px, py, pz, sumsq3(px, py, pz));
         ridx[pos] = k;
     }
@@ -322,11 +211,9 @@ __global__ __launch_bounds__(256) void ball_grid_query_kernel(int B, int N, int 
     int *keep = keep_s[wv];
     const long long total = (long long)B * S;
     const size_t cloud_bytes = grid_cloud_bytes(N);
-    // XCD-aware block order (hardware block i runs on XCD i % 8; gridDim.x is a multiple of 8): every XCD walks one
-    // contiguous range of queries, so a cloud's grid (cell table + records, ~0.45 MB at N = 24000, re-read ~60x by
-    // its S queries) is pulled into ONE XCD's L2 instead of all eight.  Speed only.
-    const unsigned nb = gridDim.x;
-    const unsigned lb = (blockIdx.x & 7u) * (nb >> 3) + (blockIdx.x >> 3);
+    // every XCD walks one contiguous range of queries: a cloud's grid (cell table + records, ~0.45 MB at N = 24000,
+    // re-read ~60x by its S queries) stays in ONE L2
+    const unsigned nb = gridDim.x, lb = xcd_block_order();  // nb is a multiple of 8
     for (long long q = (long long)lb * 4 + wv; q < total; q += (long long)nb * 4) {
         const int b = (int)(q / S);
         const unsigned char *base = ws + (size_t)b * cloud_bytes;
@@ -443,21 +330,8 @@ __global__ __launch_bounds__(256) void ball_grid_query_kernel(int B, int N, int 
 constexpr int kBmMaxN = 32768;
 constexpr int kBmHitCap = 256;
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t ball_rsrc(const void *base, unsigned bytes) {   // wave-uniform base
-    const unsigned long long a = (unsigned long long)base;
-    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc((void *)(((unsigned long long)hi << 32) | lo), 0,
-                                             __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-}
-
 constexpr int kChunkQ = 16;            // queries per chunk
 constexpr int kQBlk = 64;              // bytes per query block: 9 run entries (end u16 | delta i16 << 16), pad, (cx, cy, cz, |c|^2) at +48
-
-template <int CTRL, int ROW_MASK, int BANK_MASK>
-__device__ __forceinline__ int dpp_zero_i(int v) {   // lanes without a source / outside the masks receive 0
-    return __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, BANK_MASK, false);
-}
 
 template <typename IdxT, int NQ>
 __global__ __launch_bounds__(64) void ball_grid_query_chunk_kernel(int B, int N, int S, int K, float r2,
@@ -508,7 +382,7 @@ __global__ __launch_bounds__(64) void ball_grid_query_chunk_kernel(int B, int N,
         const GridHeader *hdr = (const GridHeader *)base;
         const float *__restrict__ cloud = xyz + (size_t)b * N * 3;
         // ---- chunk stage: the 16 queries' coordinates, cells, runs ------------------------------------------------------
-        const __amdgpu_buffer_rsrc_t rs_q = ball_rsrc(new_xyz + qg0 * 3, (unsigned)nq * 12u);
+        const __amdgpu_buffer_rsrc_t rs_q = make_rsrc_uniform(new_xyz + qg0 * 3, (unsigned)nq * 12u);
         const float cx = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_q, (unsigned)ql * 12u + 0u, 0, 0));
         const float cy = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_q, (unsigned)ql * 12u + 4u, 0, 0));
         const float cz = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_q, (unsigned)ql * 12u + 8u, 0, 0));
@@ -517,7 +391,7 @@ __global__ __launch_bounds__(64) void ball_grid_query_chunk_kernel(int B, int N,
         unsigned long long scanq = __builtin_amdgcn_ballot_w64(!fin && dyi == 0 && ql < nq);
         if (hdr->use_scan) scanq = 0x1111111111111111ull;
         {
-            const __amdgpu_buffer_rsrc_t rs_cells = ball_rsrc(base + sizeof(GridHeader), (kGridCells + 1) * 4u);
+            const __amdgpu_buffer_rsrc_t rs_cells = make_rsrc_uniform(base + sizeof(GridHeader), (kGridCells + 1) * 4u);
             const int gx = hdr->g[0], gy = hdr->g[1], gz = hdr->g[2];
             const float inv_h = hdr->inv_h;
             const int qx = cell_coord(cx, hdr->lo[0], inv_h, gx);
@@ -542,9 +416,9 @@ __global__ __launch_bounds__(64) void ball_grid_query_chunk_kernel(int B, int N,
             int e[3];
 #pragma unroll
             for (int ps = 0; ps < 3; ++ps)
-                e[ps] = len[ps] + dpp_zero_i<0x93, 0xF, 0xF>(len[ps])      // quad_perm [3,0,1,2]
-                        + dpp_zero_i<0x4F, 0xF, 0xF>(len[ps]);             // quad_perm [3,3,0,1]
-            const int t0 = dpp_zero_i<0xAA, 0xF, 0xF>(e[0]), t1 = dpp_zero_i<0xAA, 0xF, 0xF>(e[1]);   // quad_perm [2,2,2,2]
+                e[ps] = len[ps] + (int)dpp_or_zero<0x93, 0xF>((unsigned)len[ps])      // quad_perm [3,0,1,2]
+                        + (int)dpp_or_zero<0x4F, 0xF>((unsigned)len[ps]);             // quad_perm [3,3,0,1]
+            const int t0 = (int)dpp_or_zero<0xAA, 0xF>((unsigned)e[0]), t1 = (int)dpp_or_zero<0xAA, 0xF>((unsigned)e[1]);   // quad_perm [2,2,2,2]
             e[1] += t0;
             e[2] += t0 + t1;
             // the query block: entry r = end | (record of the run's first candidate - its position in the list) << 16; the
@@ -560,8 +434,8 @@ __global__ __launch_bounds__(64) void ball_grid_query_chunk_kernel(int B, int N,
         }
         wave_lds_fence();
         // ---- the queries of the chunk ---------------------------------------------------------------------------------------
-        const __amdgpu_buffer_rsrc_t rs_rec = ball_rsrc(base + kGridRecOff, (unsigned)N * 16u);
-        const __amdgpu_buffer_rsrc_t rs_idx = ball_rsrc(base + grid_idx_off(N), (unsigned)N * 4u);
+        const __amdgpu_buffer_rsrc_t rs_rec = make_rsrc_uniform(base + kGridRecOff, (unsigned)N * 16u);
+        const __amdgpu_buffer_rsrc_t rs_idx = make_rsrc_uniform(base + grid_idx_off(N), (unsigned)N * 4u);
         for (int i = 0; i < nq; ++i) {
             IdxT *__restrict__ orow = out + (qg0 + i) * K;
             const unsigned char *qb = lds + kOffQ + i * kQBlk;            // wave-uniform
@@ -570,7 +444,7 @@ __global__ __launch_bounds__(64) void ball_grid_query_chunk_kernel(int B, int N,
                 ball_scan_row<IdxT>(N, K, r2, cloud, qc.x, qc.y, qc.z, orow, lane);
                 continue;
             }
-            const __amdgpu_buffer_rsrc_t rs_out = ball_rsrc(orow, (unsigned)K * (unsigned)sizeof(IdxT));
+            const __amdgpu_buffer_rsrc_t rs_out = make_rsrc_uniform(orow, (unsigned)K * (unsigned)sizeof(IdxT));
             auto put = [&](int r, int v) {   // orow[r] = v
                 if constexpr (sizeof(IdxT) == 8)
                     __builtin_amdgcn_raw_buffer_store_b64(u32x2{(unsigned)v, 0u}, rs_out, (unsigned)r * 8u, 0, 0);   // indices are >= 0

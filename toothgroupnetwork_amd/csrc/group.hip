@@ -50,8 +50,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(24))) void grou
     const unsigned xo = xyz_first ? 0 : D;
     const unsigned fo = xyz_first ? 3 : 0;
     const int total = K * C;
-    const unsigned nb = gridDim.x;  // multiple of 8; hardware block i runs on XCD i % 8 (observed; speed only)
-    const unsigned lb = (blockIdx.x & 7u) * (nb >> 3) + (blockIdx.x >> 3);
+    const unsigned nb = gridDim.x, lb = xcd_block_order();  // nb is a multiple of 8
     for (long long q = (long long)lb * 4 + wv; q < queries; q += (long long)nb * 4) {
         const int b = (int)(q / S);
         const float cq0 = new_xyz[q * 3 + 0], cq1 = new_xyz[q * 3 + 1], cq2 = new_xyz[q * 3 + 2];
@@ -82,22 +81,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(24))) void grou
 
 // ---- v2 -------------------------------------------------------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// Raw buffer descriptor (gfx9 family): 48-bit base, stride 0, num_records in bytes, dword3 = 0x00020000 (untyped
-// 32-bit data format).  Accesses beyond num_records are dropped / return 0 in hardware.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)bytes, 0x00020000);
-}
-// The same for a base the caller KNOWS to be wave-uniform but hipcc may not (anything downstream of an integer
-// division): both halves go through v_readfirstlane, so the descriptor sits in SGPRs and the access is not wrapped in
-// a waterfall loop (cdna_hip_programming.md T20).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_uniform(const void *base, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)base;
-    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc((void *)(((unsigned long long)hi << 32) | lo), 0,
-                                             __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
-}
 
 // POLICY = the cache-policy immediate of the output stores: bit 0 sc0, bit 1 nt, bit 4 sc1 (gfx940+).
 // WIDE = rows of at least 64 floats and K <= 64 (Shape-A levels 2 and 3): a 64-float sub-step then lies in one row or

@@ -4,14 +4,13 @@
 //              preserved exactly (insertion history decides the order of equal distances).
 // three_nn   : the square_distance + full sort + [:3] of PointNetFeaturePropagation
 //              (pointnet2_utils.py:333-335) as a running top-3 by (distance, index).
-#include "tgn_common.h"
+#include "grid_common.h"
 #include <stdlib.h>
 
 namespace tgn {
 
 // ---------------------------------------------------------------------------------------------
-// kNN, exact heap semantics.  One thread per query; the heap lives in LDS (column per thread) so the
-// data-dependent sift never touches scratch memory.
+// kNN, exact heap semantics: the reference's sift and its segment look-up (the heap kernel itself: knn_heap_wave_kernel).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ void knn_reheap(float *hd, int *hi, int stride, int k) {
     // knnquery_cuda_kernel.cu:21-36
@@ -31,56 +30,14 @@ __device__ __forceinline__ void knn_reheap(float *hd, int *hi, int stride, int k
     }
 }
 
-template <int NT>
-__global__ __launch_bounds__(NT) void knn_heap_kernel(int b, int m, int nsample, const float *__restrict__ xyz,
-                                                       const float *__restrict__ new_xyz,
-                                                       const int *__restrict__ offset,
-                                                       const int *__restrict__ new_offset, int *__restrict__ idx,
-                                                       float *__restrict__ dist2, const int *__restrict__ only) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float *hd = (float *)smem + threadIdx.x;
-    int *hi = (int *)smem + (size_t)nsample * NT + threadIdx.x;
-    int pt = blockIdx.x * NT + threadIdx.x;
-    if (only) {  // second pass of the wave kernel: only[0] = count, only[1..] = the queries to redo exactly
-        if (pt >= only[0]) return;
-        pt = only[1 + pt];
-    }
-    if (pt >= m) return;
+// the segment [start, end) of query q; returns its number
+__device__ __forceinline__ int knn_segment(int q, int b, const int *__restrict__ offset, const int *__restrict__ new_offset,
+                                           int &start, int &end) {
     int bt = 0;  // get_bt_idx, knnquery_cuda_kernel.cu:51-62 (bounded by b here)
-    while (bt < b - 1 && !(pt < new_offset[bt])) ++bt;
-    const int start = bt == 0 ? 0 : offset[bt - 1];
-    const int end = offset[bt];
-    const float qx = new_xyz[(size_t)pt * 3 + 0], qy = new_xyz[(size_t)pt * 3 + 1], qz = new_xyz[(size_t)pt * 3 + 2];
-    for (int i = 0; i < nsample; ++i) {
-        hd[i * NT] = 1e10f;
-        hi[i * NT] = start;
-    }
-    float root = 1e10f;
-    for (int i = start; i < end; ++i) {
-        const float x = xyz[(size_t)i * 3 + 0], y = xyz[(size_t)i * 3 + 1], z = xyz[(size_t)i * 3 + 2];
-        const float ex = qx - x, ey = qy - y, ez = qz - z;
-        const float d2 = dist_direct_nofma(ex, ey, ez);  // knnquery_cuda_kernel.cu:96
-        if (d2 < root) {
-            hd[0] = d2;
-            hi[0] = i;
-            knn_reheap(hd, hi, NT, nsample);
-            root = hd[0];
-        }
-    }
-    // heap_sort, knnquery_cuda_kernel.cu:39-48
-    for (int i = nsample - 1; i > 0; --i) {
-        const float td = hd[0];
-        hd[0] = hd[i * NT];
-        hd[i * NT] = td;
-        const int ti = hi[0];
-        hi[0] = hi[i * NT];
-        hi[i * NT] = ti;
-        knn_reheap(hd, hi, NT, i);
-    }
-    for (int i = 0; i < nsample; ++i) {
-        idx[(size_t)pt * nsample + i] = hi[i * NT];
-        dist2[(size_t)pt * nsample + i] = hd[i * NT];
-    }
+    while (bt < b - 1 && !(q < new_offset[bt])) ++bt;
+    start = bt == 0 ? 0 : offset[bt - 1];
+    end = offset[bt];
+    return bt;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -95,10 +52,43 @@ __global__ __launch_bounds__(NT) void knn_heap_kernel(int b, int m, int nsample,
 // ---------------------------------------------------------------------------------------------
 constexpr int kKnnQ = 4;
 
-__device__ __forceinline__ float dpp_wave_shr1(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xF, 0xF, false));
+// insert candidate (dn, in) into the lane-sorted list: entries <= dn stay in front (an equal, earlier candidate keeps its place)
+__device__ __forceinline__ void knn_insert(float &ld, int &li, float &tau, float dn, int in, int k, int lane) {
+    // lanes 0..k hold the list: the lane mask is applied to the ballot as a (wave-uniform) constant, and the shifted-in
+    // value of lane 0 is never used, so the DPP moves (wave_shr:1) need no defined "old" operand
+    const unsigned long long kmask = (k >= 63) ? ~0ull : ((2ull << k) - 1ull);
+    const int pos = __popcll(__builtin_amdgcn_ballot_w64(ld <= dn) & kmask);
+    const float sd = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(ld), __float_as_int(ld), 0x138, 0xF, 0xF, false));
+    const int si = __builtin_amdgcn_update_dpp(li, li, 0x138, 0xF, 0xF, false);
+    ld = lane < pos ? ld : (lane == pos ? dn : sd);
+    li = lane < pos ? li : (lane == pos ? in : si);
+    tau = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ld), k));
 }
-__device__ __forceinline__ int dpp_wave_shr1(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xF, 0xF, false); }
+
+// feed the candidates of `mask` (lane = candidate, with its distance d2 and point index pi) to the list, in lane order
+__device__ __forceinline__ void knn_drain(unsigned long long mask, float d2, int pi, float &ld, int &li, float &tau, int k,
+                                          int lane) {
+    while (mask) {  // wave-uniform
+        const int src = __builtin_ctzll(mask);
+        mask &= mask - 1;
+        const float dn = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d2), src));
+        if (!(dn < tau)) continue;  // the threshold may have dropped meanwhile
+        knn_insert(ld, li, tau, dn, __builtin_amdgcn_readlane(pi, src), k, lane);
+    }
+}
+
+// store row q of the result; exact ties decide nothing here, the heap kernel settles them: such queries go to `redo`
+__device__ __forceinline__ void knn_store_row(int q, int k, float ld, int li, int *__restrict__ idx, float *__restrict__ dist2,
+                                              int *__restrict__ redo, int lane) {
+    if (lane < k) {
+        idx[(size_t)q * k + lane] = li;
+        dist2[(size_t)q * k + lane] = ld;
+    }
+    const float nd = __shfl_down(ld, 1);
+    const int ni = __shfl_down(li, 1);
+    const bool tie = lane < k && ld == nd && li != ni;
+    if (__any(tie) && lane == 0) redo[1 + atomicAdd(&redo[0], 1)] = q;
+}
 
 __global__ __launch_bounds__(256) void knn_wave_kernel(int b, int m, int k, const float *__restrict__ xyz,
                                                         const float *__restrict__ new_xyz,
@@ -114,10 +104,8 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(int b, int m, int k, cons
 #pragma unroll
     for (int j = 0; j < kKnnQ; ++j) {
         const int q = min(q0 + j, m - 1);
-        int bt = 0;  // get_bt_idx, knnquery_cuda_kernel.cu:51-62
-        while (bt < b - 1 && !(q < new_offset[bt])) ++bt;
-        st[j] = bt == 0 ? 0 : offset[bt - 1];
-        en[j] = q0 + j < m ? offset[bt] : st[j];  // padding queries scan nothing
+        knn_segment(q, b, offset, new_offset, st[j], en[j]);
+        if (q0 + j >= m) en[j] = st[j];  // padding queries scan nothing
         qx[j] = new_xyz[(size_t)q * 3 + 0];
         qy[j] = new_xyz[(size_t)q * 3 + 1];
         qz[j] = new_xyz[(size_t)q * 3 + 2];
@@ -139,6 +127,8 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(int b, int m, int k, cons
         for (int j = 0; j < kKnnQ; ++j) {
             const float ex = qx[j] - x, ey = qy[j] - y, ez = qz[j] - z;
             const float d2 = dist_direct_nofma(ex, ey, ez);  // knnquery_cuda_kernel.cu:96
+            // knn_drain + knn_insert written out: with four lists per wave the shared form (lane mask as a constant, DPP
+            // moves without an "old" operand, index by readlane) measured 5 % slower here (profiles/neighbour_shared_before_after.txt)
             unsigned long long mask = __ballot(i >= st[j] && i < en[j] && d2 < tau[j]);
             while (mask) {  // wave-uniform; candidates in ascending index order
                 const int src = __builtin_ctzll(mask);
@@ -148,8 +138,8 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(int b, int m, int k, cons
                 const int in = base + src;
                 // entries <= dn stay in front (an equal, earlier candidate keeps its place)
                 const int pos = __popcll(__ballot(lane <= k && ld[j] <= dn));
-                const float sd = dpp_wave_shr1(ld[j]);
-                const int si = dpp_wave_shr1(li[j]);
+                const float sd = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(ld[j]), 0x138, 0xF, 0xF, false));
+                const int si = __builtin_amdgcn_update_dpp(0, li[j], 0x138, 0xF, 0xF, false);
                 ld[j] = lane < pos ? ld[j] : (lane == pos ? dn : sd);
                 li[j] = lane < pos ? li[j] : (lane == pos ? in : si);
                 tau[j] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ld[j]), k));
@@ -158,17 +148,8 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(int b, int m, int k, cons
     }
 #pragma unroll
     for (int j = 0; j < kKnnQ; ++j) {
-        const int q = q0 + j;
-        if (q >= m) break;
-        if (lane < k) {
-            idx[(size_t)q * k + lane] = li[j];
-            dist2[(size_t)q * k + lane] = ld[j];
-        }
-        // exact ties decide nothing here; the heap kernel settles them
-        const float nd = __shfl_down(ld[j], 1);
-        const int ni = __shfl_down(li[j], 1);
-        const bool tie = lane < k && ld[j] == nd && li[j] != ni;
-        if (__any(tie) && lane == 0) redo[1 + atomicAdd(&redo[0], 1)] = q;
+        if (q0 + j >= m) break;
+        knn_store_row(q0 + j, k, ld[j], li[j], idx, dist2, redo, lane);
     }
 }
 
@@ -184,93 +165,33 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(int b, int m, int k, cons
 // distances are distinct the result is the brute-force one, and queries with exact ties go to the heap kernel just
 // like there.  Degenerate or tiny segments (flagged by the build) are scanned linearly by their query waves.
 // ---------------------------------------------------------------------------------------------
-constexpr int kKnnCells = 16384;
-constexpr int kKnnBuildThreads = 1024;
-
-__device__ __forceinline__ float wave_min_f32_x(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_max_f32_x(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
-struct KnnGridHeader {  // one per segment, 64 bytes
-    float lo[3];
-    float inv_h;
-    int g[3];
-    int use_scan;
-    float h;
-    int pad[7];
-};
-
 __host__ __device__ inline size_t knn_grid_off_headers(int m) { return (((size_t)m + 1) * sizeof(int) + 63) / 64 * 64; }
-__host__ __device__ inline size_t knn_grid_off_cells(int b, int m) { return knn_grid_off_headers(m) + (size_t)b * sizeof(KnnGridHeader); }
+__host__ __device__ inline size_t knn_grid_off_cells(int b, int m) { return knn_grid_off_headers(m) + (size_t)b * sizeof(GridHeader); }
 __host__ __device__ inline size_t knn_grid_off_records(int b, int m) {
-    return knn_grid_off_cells(b, m) + (size_t)b * (kKnnCells + 4) * sizeof(int);
+    return knn_grid_off_cells(b, m) + (size_t)b * (kGridCells + 4) * sizeof(int);
 }
 
-__device__ __forceinline__ int knn_cell(float p, float lo, float inv_h, int g) {
-    float t = (p - lo) * inv_h;           // the same expression for points and queries
-    t = fminf(fmaxf(t, 0.0f), (float)(g - 1));  // NaN -> 0; queries outside the box go to the border cell
-    return (int)t;
-}
-
-__global__ __launch_bounds__(kKnnBuildThreads) void knn_grid_build_kernel(int b_total, int m, int k, float scale, const float *__restrict__ xyz,
-                                                                          const int *__restrict__ offset,
-                                                                          unsigned char *__restrict__ ws) {
-    __shared__ int cnt[kKnnCells];
-    __shared__ float red[7][kKnnBuildThreads / kWave];
-    __shared__ int wave_tot[kKnnBuildThreads / kWave];
-    __shared__ KnnGridHeader hdr_s;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+__global__ __launch_bounds__(kGridThreads) void knn_grid_build_kernel(int b_total, int m, int k, float scale, const float *__restrict__ xyz,
+                                                                      const int *__restrict__ offset,
+                                                                      unsigned char *__restrict__ ws) {
+    __shared__ int cnt[kGridCells];
+    __shared__ float red[7][kGridThreads / kWave];
+    __shared__ int wave_tot[kGridThreads / kWave];
+    __shared__ GridHeader hdr_s;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const int st = b ? offset[b - 1] : 0, n = offset[b] - st;
     const float *__restrict__ pts = xyz + (size_t)st * 3;
-    KnnGridHeader *hdr = (KnnGridHeader *)(ws + knn_grid_off_headers(m)) + b;
-    int *cell_start = (int *)(ws + knn_grid_off_cells(b_total, m)) + (size_t)b * (kKnnCells + 4);
+    GridHeader *hdr = (GridHeader *)(ws + knn_grid_off_headers(m)) + b;
+    int *cell_start = (int *)(ws + knn_grid_off_cells(b_total, m)) + (size_t)b * (kGridCells + 4);
     float4 *rec = (float4 *)(ws + knn_grid_off_records(b_total, m)) + st;
 
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    float bad = 0.0f;
-    for (int i = tid; i < n; i += kKnnBuildThreads) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float v = pts[(size_t)i * 3 + a];
-            if (!(fabsf(v) <= 1.0e18f)) bad = 1.0f;  // NaN, Inf or so large that squared distances overflow
-            lo[a] = fminf(lo[a], v);
-            hi[a] = fmaxf(hi[a], v);
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float l = wave_min_f32_x(lo[a]), h = wave_max_f32_x(hi[a]);
-        if (lane == 0) {
-            red[a][wave] = l;
-            red[3 + a][wave] = h;
-        }
-    }
-    {
-        const float bb = wave_max_f32_x(bad);
-        if (lane == 0) red[6][wave] = bb;
-    }
-    for (int i = tid; i < kKnnCells; i += kKnnBuildThreads) cnt[i] = 0;
+    grid_box_partials<kGridThreads>(pts, n, 1.0e18f /* NaN, Inf or so large that squared distances overflow */, red);
+    for (int i = tid; i < kGridCells; i += kGridThreads) cnt[i] = 0;
     __syncthreads();
     if (tid == 0) {
-        KnnGridHeader h;
-        float ext[3], any_bad = 0.0f;
-        for (int a = 0; a < 3; ++a) {
-            float l = INFINITY, u = -INFINITY;
-            for (int w = 0; w < kKnnBuildThreads / kWave; ++w) {
-                l = fminf(l, red[a][w]);
-                u = fmaxf(u, red[3 + a][w]);
-            }
-            h.lo[a] = l;
-            ext[a] = u - l;
-        }
-        for (int w = 0; w < kKnnBuildThreads / kWave; ++w) any_bad = fmaxf(any_bad, red[6][w]);
+        GridHeader h;
+        float hi[3], ext[3];
+        const float any_bad = grid_box_collect(red, h.lo, hi, ext);
         // cell size ~ radius that holds k points of a SURFACE of area xy + yz + zx (half the box surface: a thin sheet
         // gives its own area); too small a guess only costs a second, larger block for some queries
         const float area = ext[0] * ext[1] + ext[1] * ext[2] + ext[0] * ext[2];
@@ -280,19 +201,8 @@ __global__ __launch_bounds__(kKnnBuildThreads) void knn_grid_build_kernel(int b_
         int g[3] = {1, 1, 1};
         bool ok = any_bad == 0.0f && n >= 512 && hcell > 0.0f && hcell < INFINITY;
         if (ok) {
-            for (int it = 0; it < 80; ++it) {
-                const float inv = 1.0f / hcell;
-                long long cells = 1;
-                for (int a = 0; a < 3; ++a) {
-                    const float t = ext[a] * inv;
-                    g[a] = (t < 1.0e6f) ? (int)t + 1 : 1000001;
-                    cells *= g[a];
-                }
-                if (cells <= kKnnCells) break;
-                hcell *= 1.1f;
-            }
-            long long cells = (long long)g[0] * g[1] * g[2];
-            ok = cells <= kKnnCells && cells >= 8;
+            const long long cells = grid_fit(ext, hcell, 80, g);
+            ok = cells <= kGridCells && cells >= 8;
         }
         h.h = hcell;
         h.inv_h = ok ? 1.0f / hcell : 0.0f;
@@ -303,64 +213,17 @@ __global__ __launch_bounds__(kKnnBuildThreads) void knn_grid_build_kernel(int b_
         *hdr = h;
     }
     __syncthreads();
-    const KnnGridHeader h = hdr_s;
+    const GridHeader h = hdr_s;
     if (h.use_scan) return;
-    for (int i = tid; i < n; i += kKnnBuildThreads) {
-        const int cx = knn_cell(pts[(size_t)i * 3 + 0], h.lo[0], h.inv_h, h.g[0]);
-        const int cy = knn_cell(pts[(size_t)i * 3 + 1], h.lo[1], h.inv_h, h.g[1]);
-        const int cz = knn_cell(pts[(size_t)i * 3 + 2], h.lo[2], h.inv_h, h.g[2]);
-        atomicAdd(&cnt[(cz * h.g[1] + cy) * h.g[0] + cx], 1);
-    }
+    for (int i = tid; i < n; i += kGridThreads)
+        atomicAdd(&cnt[grid_cell_of<knn_cell>(h, pts[(size_t)i * 3 + 0], pts[(size_t)i * 3 + 1], pts[(size_t)i * 3 + 2])], 1);
     __syncthreads();
-    constexpr int PER = kKnnCells / kKnnBuildThreads;
-    int local[PER];
-    int sum = 0;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-        local[i] = sum;
-        sum += cnt[tid * PER + i];
-    }
-    int incl = sum;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const int v = __shfl_up(incl, o);
-        if (lane >= o) incl += v;
-    }
-    if (lane == kWave - 1) wave_tot[wave] = incl;
-    __syncthreads();
-    int wave_base = 0;
-    for (int w = 0; w < wave; ++w) wave_base += wave_tot[w];
-    const int thread_base = wave_base + incl - sum;
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-        const int v = thread_base + local[i];
-        cell_start[tid * PER + i] = v;
-        cnt[tid * PER + i] = v;
-    }
-    if (tid == kKnnBuildThreads - 1) cell_start[kKnnCells] = thread_base + sum;
-    __syncthreads();
-    for (int i = tid; i < n; i += kKnnBuildThreads) {
+    grid_scan_cells<kGridCells, kGridThreads>(cnt, wave_tot, cell_start);
+    for (int i = tid; i < n; i += kGridThreads) {
         const float px = pts[(size_t)i * 3 + 0], py = pts[(size_t)i * 3 + 1], pz = pts[(size_t)i * 3 + 2];
-        const int cx = knn_cell(px, h.lo[0], h.inv_h, h.g[0]);
-        const int cy = knn_cell(py, h.lo[1], h.inv_h, h.g[1]);
-        const int cz = knn_cell(pz, h.lo[2], h.inv_h, h.g[2]);
-        const int pos = atomicAdd(&cnt[(cz * h.g[1] + cy) * h.g[0] + cx], 1);
+        const int pos = atomicAdd(&cnt[grid_cell_of<knn_cell>(h, px, py, pz)], 1);
         rec[pos] = make_float4(px, py, pz, __int_as_float(st + i));  // the packed (global) point index
     }
-}
-
-// insert candidate (dn, in) into the lane-sorted list (entries <= dn stay in front), as in knn_wave_kernel
-__device__ __forceinline__ void knn_insert(float &ld, int &li, float &tau, float dn, int in, int k, int lane) {
-    // lanes 0..k hold the list: the lane mask is applied to the ballot as a (wave-uniform) constant, and the shifted-in
-    // value of lane 0 is never used, so the DPP moves need no defined "old" operand
-    const unsigned long long kmask = (k >= 63) ? ~0ull : ((2ull << k) - 1ull);
-    const int pos = __popcll(__builtin_amdgcn_ballot_w64(ld <= dn) & kmask);
-    const float sd = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(ld), __float_as_int(ld), 0x138, 0xF, 0xF, false));
-    const int si = __builtin_amdgcn_update_dpp(li, li, 0x138, 0xF, 0xF, false);
-    ld = lane < pos ? ld : (lane == pos ? dn : sd);
-    li = lane < pos ? li : (lane == pos ? in : si);
-    tau = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ld), k));
 }
 
 __global__ __launch_bounds__(256) void knn_grid_query_kernel(int b, int m, int k, const float *__restrict__ xyz,
@@ -372,11 +235,10 @@ __global__ __launch_bounds__(256) void knn_grid_query_kernel(int b, int m, int k
     const int lane = threadIdx.x & (kWave - 1);
     const int q = blockIdx.x * (blockDim.x / kWave) + __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     if (q >= m) return;
-    int bt = 0;  // get_bt_idx, knnquery_cuda_kernel.cu:51-62
-    while (bt < b - 1 && !(q < new_offset[bt])) ++bt;
-    const int st = bt == 0 ? 0 : offset[bt - 1], en = offset[bt];
+    int st, en;
+    const int bt = knn_segment(q, b, offset, new_offset, st, en);
     const float qx = new_xyz[(size_t)q * 3 + 0], qy = new_xyz[(size_t)q * 3 + 1], qz = new_xyz[(size_t)q * 3 + 2];
-    const KnnGridHeader *hdr = (const KnnGridHeader *)(ws + knn_grid_off_headers(m)) + bt;
+    const GridHeader *hdr = (const GridHeader *)(ws + knn_grid_off_headers(m)) + bt;
     float ld = 1e10f, tau = 1e10f;  // knnquery_cuda_kernel.cu:88-91
     int li = st;
     const bool q_ok = fabsf(qx) <= 1.0e18f && fabsf(qy) <= 1.0e18f && fabsf(qz) <= 1.0e18f;
@@ -388,17 +250,10 @@ __global__ __launch_bounds__(256) void knn_grid_query_kernel(int b, int m, int k
                 const float ex = qx - xyz[(size_t)i * 3 + 0], ey = qy - xyz[(size_t)i * 3 + 1], ez = qz - xyz[(size_t)i * 3 + 2];
                 d2 = dist_direct_nofma(ex, ey, ez);
             }
-            unsigned long long mask = __ballot(i < en && d2 < tau);
-            while (mask) {
-                const int src = __builtin_ctzll(mask);
-                mask &= mask - 1;
-                const float dn = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d2), src));
-                if (!(dn < tau)) continue;
-                knn_insert(ld, li, tau, dn, base + src, k, lane);
-            }
+            knn_drain(__ballot(i < en && d2 < tau), d2, i, ld, li, tau, k, lane);
         }
     } else {
-        const int *__restrict__ cell_start = (const int *)(ws + knn_grid_off_cells(b, m)) + (size_t)bt * (kKnnCells + 4);
+        const int *__restrict__ cell_start = (const int *)(ws + knn_grid_off_cells(b, m)) + (size_t)bt * (kGridCells + 4);
         const float4 *__restrict__ rec = (const float4 *)(ws + knn_grid_off_records(b, m)) + st;
         const int gx = hdr->g[0], gy = hdr->g[1], gz = hdr->g[2];
         const float inv_h = hdr->inv_h, h = hdr->h;
@@ -459,14 +314,7 @@ __global__ __launch_bounds__(256) void knn_grid_query_kernel(int b, int m, int k
                                 d2 = dist_direct_nofma(ex, ey, ez);  // knnquery_cuda_kernel.cu:96
                                 pi = __float_as_int(p.w);
                             }
-                            unsigned long long mask = __ballot(j < e && d2 < tau);
-                            while (mask) {
-                                const int src = __builtin_ctzll(mask);
-                                mask &= mask - 1;
-                                const float dn = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d2), src));
-                                if (!(dn < tau)) continue;
-                                knn_insert(ld, li, tau, dn, __builtin_amdgcn_readlane(pi, src), k, lane);
-                            }
+                            knn_drain(__ballot(j < e && d2 < tau), d2, pi, ld, li, tau, k, lane);
                         }
                     }
                 }
@@ -479,14 +327,7 @@ __global__ __launch_bounds__(256) void knn_grid_query_kernel(int b, int m, int k
             if (cover > 0.0f && tau < cover * cover) break;
         }
     }
-    if (lane < k) {
-        idx[(size_t)q * k + lane] = li;
-        dist2[(size_t)q * k + lane] = ld;
-    }
-    const float nd = __shfl_down(ld, 1);
-    const int ni = __shfl_down(li, 1);
-    const bool tie = lane < k && ld == nd && li != ni;
-    if (__any(tie) && lane == 0) redo[1 + atomicAdd(&redo[0], 1)] = q;
+    knn_store_row(q, k, ld, li, idx, dist2, redo, lane);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -706,10 +547,8 @@ __global__ __launch_bounds__(256) void knn_heap_wave_kernel(int b, int m, int ns
     const int total = only ? only[0] : m;
     for (int w = blockIdx.x * 4 + wv; w < total; w += gridDim.x * 4) {
         const int pt = only ? only[1 + w] : w;
-        int bt = 0;
-        while (bt < b - 1 && !(pt < new_offset[bt])) ++bt;
-        const int start = bt == 0 ? 0 : offset[bt - 1];
-        const int end = offset[bt];
+        int start, end;
+        knn_segment(pt, b, offset, new_offset, start, end);
         const float qx = new_xyz[(size_t)pt * 3 + 0], qy = new_xyz[(size_t)pt * 3 + 1], qz = new_xyz[(size_t)pt * 3 + 2];
         for (int i = lane; i < nsample; i += kWave) {
             hd[i] = 1e10f;
@@ -758,29 +597,15 @@ __global__ __launch_bounds__(256) void knn_heap_wave_kernel(int b, int m, int ns
 
 static int knn_heap_launch(int b, int m, int nsample, const float *xyz, const float *new_xyz, const int *offset,
                            const int *new_offset, int *idx, float *dist2, const int *only, hipStream_t st) {
-    if (nsample <= kKnnHeapMax) {
-        // redo pass: the list is usually empty or a few queries; 64 blocks cover up to 256 of them per sweep
-        const int blocks = only ? 64 : (m + 3) / 4 < 256 * 16 ? (m + 3) / 4 : 256 * 16;
-        hipLaunchKernelGGL(knn_heap_wave_kernel, dim3(blocks), dim3(256), 0, st, b, m, nsample, xyz, new_xyz, offset,
-                           new_offset, idx, dist2, only);
-        return check_launch("knn_heap_wave_kernel");
-    }
-    // heap columns in LDS: nsample * 8 B per thread; keep a block under 64 KiB
-#define TGN_KNN_HEAP(NT_)                                                                                             \
-    hipLaunchKernelGGL((knn_heap_kernel<NT_>), dim3((m + NT_ - 1) / NT_), dim3(NT_), (size_t)nsample * NT_ * 8, st, b, \
-                       m, nsample, xyz, new_xyz, offset, new_offset, idx, dist2, only)
-    if (nsample <= 32)
-        TGN_KNN_HEAP(256);
-    else if (nsample <= 64)
-        TGN_KNN_HEAP(128);
-    else if (nsample <= 128)
-        TGN_KNN_HEAP(64);
-    else {
+    if (nsample > kKnnHeapMax) {
         set_error("tgn_knnquery: nsample %d > 128 unsupported (the reference's limit is 100)", nsample);
         return TGN_ERR_UNSUPPORTED;
     }
-#undef TGN_KNN_HEAP
-    return check_launch("knn_heap_kernel");
+    // redo pass: the list is usually empty or a few queries; 64 blocks cover up to 256 of them per sweep
+    const int blocks = only ? 64 : (m + 3) / 4 < 256 * 16 ? (m + 3) / 4 : 256 * 16;
+    hipLaunchKernelGGL(knn_heap_wave_kernel, dim3(blocks), dim3(256), 0, st, b, m, nsample, xyz, new_xyz, offset, new_offset,
+                       idx, dist2, only);
+    return check_launch("knn_heap_wave_kernel");
 }
 
 namespace tgn {
@@ -843,7 +668,7 @@ TGN_API int tgn_knnquery_grid(int b, int n, int m, int nsample, const float *xyz
         return TGN_ERR_LAUNCH;
     }
     const float scale = 1.0f;  // cell size relative to the estimated k-neighbour radius
-    hipLaunchKernelGGL(knn_grid_build_kernel, dim3(b), dim3(kKnnBuildThreads), 0, st, b, m, nsample, scale, xyz, offset,
+    hipLaunchKernelGGL(knn_grid_build_kernel, dim3(b), dim3(kGridThreads), 0, st, b, m, nsample, scale, xyz, offset,
                        (unsigned char *)workspace);
     if (int rc = check_launch("knn_grid_build_kernel")) return rc;
     hipLaunchKernelGGL(knn_grid_query_kernel, dim3((m + 3) / 4), dim3(256), 0, st, b, m, nsample, xyz, new_xyz, offset,

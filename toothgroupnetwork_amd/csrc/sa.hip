@@ -21,10 +21,6 @@ namespace tgn {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t sa_rsrc(const void *base, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)bytes, 0x00020000);
-}
-
 // ------------------------------------------------------------------------------------------------------------
 // Per-point transform: A[m, :] = [points[m, 0..D), xyz[m, 0..3)] * Wt      (M = B*N rows, Kc = D+3, C1 columns)
 // Wt: (D+3, C1) row-major, rows ordered [features..., x, y, z], BatchNorm scale already folded into its columns.
@@ -149,8 +145,7 @@ __global__ __launch_bounds__(256) void sa_gather_max_kernel(int B, int N, int S,
     const unsigned cblocks = ((unsigned)C1 + 127u) >> 7;
     const long long per_scan = (long long)cblocks * S;
     const long long items = per_scan * B;
-    const unsigned nb = gridDim.x;
-    const unsigned lb = (blockIdx.x & 7u) * (nb >> 3) + (blockIdx.x >> 3);   // XCD-contiguous item ranges (speed only)
+    const unsigned nb = gridDim.x, lb = xcd_block_order();   // XCD-contiguous item ranges
     for (long long it = (long long)lb * 4 + wv; it < items; it += (long long)nb * 4) {
         const int b = __builtin_amdgcn_readfirstlane((int)(it / per_scan));
         const unsigned r = (unsigned)(it - (long long)b * per_scan);
@@ -169,7 +164,7 @@ __global__ __launch_bounds__(256) void sa_gather_max_kernel(int B, int N, int S,
             roff = (unsigned)v * (unsigned)C1 * 4u;
         }
         if (err && cb == 0 && __any(bad) && lane == 0) atomicOr(err, kIndexErrGather);
-        const __amdgpu_buffer_rsrc_t rs = sa_rsrc(A + (size_t)b * N * C1, (unsigned)N * (unsigned)C1 * 4u);
+        const __amdgpu_buffer_rsrc_t rs = make_rsrc(A + (size_t)b * N * C1, (unsigned)N * (unsigned)C1 * 4u);
         f32x4 m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
         const bool live = c < (unsigned)C1;
         for (int k0 = 0; k0 < K; k0 += 16) {
@@ -234,8 +229,7 @@ __global__ __launch_bounds__(256) void sa_direct_max_kernel(long long queries, i
     float bias[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) bias[t] = b2[t * 32 + lo];
-    const unsigned nb = gridDim.x;
-    const unsigned lb = (blockIdx.x & 7u) * (nb >> 3) + (blockIdx.x >> 3);
+    const unsigned nb = gridDim.x, lb = xcd_block_order();
     for (long long q = (long long)lb * 4 + wv; q < queries; q += (long long)nb * 4) {
         const int b = __builtin_amdgcn_readfirstlane((int)(q / S));
         const float cq[3] = {new_xyz[q * 3 + 0], new_xyz[q * 3 + 1], new_xyz[q * 3 + 2]};
@@ -407,8 +401,7 @@ __global__ __launch_bounds__(256) void sa_gather_act_kernel(long long queries, i
                                                              float *__restrict__ out, int *__restrict__ err) {
     const unsigned lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const unsigned nb = gridDim.x;
-    const unsigned lb = (blockIdx.x & 7u) * (nb >> 3) + (blockIdx.x >> 3);
+    const unsigned nb = gridDim.x, lb = xcd_block_order();
     for (long long q = (long long)lb * 4 + wv; q < queries; q += (long long)nb * 4) {
         const int b = __builtin_amdgcn_readfirstlane((int)(q / S));
         const float cx = new_xyz[q * 3 + 0], cy = new_xyz[q * 3 + 1], cz = new_xyz[q * 3 + 2];
@@ -424,7 +417,7 @@ __global__ __launch_bounds__(256) void sa_gather_act_kernel(long long queries, i
             roff = (unsigned)v * (unsigned)C1 * 4u;
         }
         if (err && __any(bad) && lane == 0) atomicOr(err, kIndexErrGather);
-        const __amdgpu_buffer_rsrc_t rs = sa_rsrc(A + (size_t)b * N * C1, (unsigned)N * (unsigned)C1 * 4u);
+        const __amdgpu_buffer_rsrc_t rs = make_rsrc(A + (size_t)b * N * C1, (unsigned)N * (unsigned)C1 * 4u);
         for (unsigned c = lane * 4u; c < (unsigned)C1; c += 256u) {
             const f32x4 w0 = *(const f32x4 *)(Wxs + c), w1 = *(const f32x4 *)(Wxs + C1 + c), w2 = *(const f32x4 *)(Wxs + 2 * C1 + c);
             const f32x4 bb = *(const f32x4 *)(b2 + c);

@@ -390,8 +390,7 @@ __global__ __launch_bounds__(WM * 128, WM == 2 ? TGN_SA_SPLIT_BLOCKS : 1) void s
     }
     // ---- B: K tile t of 128-column tile j is 12 contiguous KiB of the image at (j T + t); a 256-wide workgroup takes tiles 2 ntile
     // and 2 ntile + 1 (the second may lie past the last one: the descriptor's bound then returns zeros).  Wave wv moves kPieces pieces.
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<unsigned char *>(W2s), 0, (int)((size_t)ntiles128 * T * kSplitTile), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(W2s, (unsigned)((size_t)ntiles128 * T * kSplitTile));
     auto dma = [&](int t, int buf) {
 #pragma unroll
         for (int p = 0; p < kPieces; ++p) {
@@ -637,8 +636,7 @@ __global__ __launch_bounds__(256, 2) void sa_point_transform_split_kernel(long l
     const long long grow = row0 + ar;
     const bool row_ok = grow < M;
     const bool feat4 = (D & 3) == 0 && points != nullptr;
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char *>(Wts), 0,
-                                                                          (int)((size_t)ntiles * T * kSplitTile), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(Wts, (unsigned)((size_t)ntiles * T * kSplitTile));
     auto dma = [&](int t, int buf) {
 #pragma unroll
         for (int p = 0; p < 3; ++p) {

@@ -48,6 +48,7 @@ inline int check_launch(const char *what) {
 
 // ---- wave-level primitives -----------------------------------------------------------------
 // DPP control words (gfx9 family): row_shr:n = 0x110+n, row_bcast:15 = 0x142, row_bcast:31 = 0x143.
+// quad_perm [a,b,c,d] = a | b << 2 | c << 4 | d << 6.
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ unsigned dpp_or_zero(unsigned v) {
     // lanes without a valid source (or outside ROW_MASK) receive 0
@@ -125,6 +126,29 @@ __device__ __forceinline__ float vmin_f32(float a, float b) {
     asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
+
+// ---- buffer descriptors and block order --------------------------------------------------------
+// Raw buffer descriptor (gfx9 family): 48-bit base, stride 0, num_records in bytes, dword3 = 0x00020000 (untyped
+// 32-bit data format).  Accesses beyond num_records are dropped / return 0 in hardware.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)bytes, 0x00020000);
+}
+// The same for a base the caller KNOWS to be wave-uniform but hipcc may not (anything downstream of an integer
+// division): both halves go through v_readfirstlane, so the descriptor sits in SGPRs and the access is not wrapped in
+// a waterfall loop (cdna_hip_programming.md T20).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_uniform(const void *base, unsigned bytes) {
+    const unsigned long long a = (unsigned long long)base;
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32));
+    return __builtin_amdgcn_make_buffer_rsrc((void *)(((unsigned long long)hi << 32) | lo), 0,
+                                             __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000);
+}
+
+// XCD-aware block order (hardware block i runs on XCD i % 8: observed dispatch; gridDim.x is a multiple of 8): block i
+// takes logical position (i % 8) * gridDim.x / 8 + i / 8, so every XCD walks ONE contiguous range of the work and
+// whatever that range re-reads (a cloud's grid, a scan's feature rows) is pulled into one XCD's L2 instead of all
+// eight.  Speed only.
+__device__ __forceinline__ unsigned xcd_block_order() { return (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3); }
 
 template <typename T>
 __device__ __forceinline__ T idx_load(const void *p, long long i, bool is64) {
