@@ -129,8 +129,9 @@ __global__ __launch_bounds__(NT) void fps_resident_kernel(FpsArgs a) {
 // the phased HotPath schedule: a lone wave issues about one instruction per 5 cycles WHATEVER its kind, so an iteration costs
 // what the wave that holds the winner ISSUES (fps_resident_kernel<64,16>: ~350 instructions per iteration); and the ball
 // queries that run beside FPS levels 2-3 are occupancy-bound by LDS (6 KB per wave), so every KB this kernel holds is theirs.
-//   * two points per instruction: the coordinates and running minima are fp32 PAIRS (v_pk_add_f32 / v_pk_mul_f32: each half an
-//     ordinary IEEE fp32 operation, nothing fused unless TGN_FPS_FMA asks for it);
+//   * the coordinates and running minima are kept as fp32 PAIRS (one v_max3_f32 per pair below), but every distance is computed
+//     with one-point instructions (lean_dist): the two-points-per-instruction form of rounds 6-12 (v_pk_add_f32 / v_pk_mul_f32)
+//     is not safe beside bf16-MFMA kernels;
 //   * the loop tracks the VALUE of the lane's maximum only (one v_max3_f32 per pair).  Points are dealt lane-major (lane t owns
 //     points t P .. t P + P - 1), so "first index wins" = first lane, then first slot inside it: a ballot finds the lane, and every
 //     lane looks up the first slot equal to its own maximum AND that slot's coordinates with a compare + four selects per slot --
@@ -161,6 +162,31 @@ template <int CTRL>
 __device__ __forceinline__ unsigned dpp_max_u32(unsigned v) {
     const unsigned t = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
     return t > v ? t : v;
+}
+
+// The squared distance of ONE point, one fp32 instruction per operation: ((dx*dx) + (dy*dy)) + (dz*dz), or the FMA contraction.
+// Written as single instructions so that the compiler cannot pair two points into v_pk_add_f32 / v_pk_mul_f32: with the packed
+// form a wave now and then picked a point that was not the farthest (always one held by its last sixteen lanes) while the bf16x3
+// set-abstraction kernels (bf16 MFMA) ran beside it -- alone, or beside the fp32-MFMA kernels, never; with this form never
+// (profiles/fps_overlap_before_after.txt; tests/test_gpu_hotpath_overlap.py runs the kernel beside those).
+template <bool FMA>
+__device__ __forceinline__ float lean_dist(float px, float py, float pz, float qx, float qy, float qz) {
+    float dx, dy, dz, r;
+    asm("v_sub_f32 %0, %1, %2" : "=v"(dx) : "v"(px), "v"(qx));
+    asm("v_sub_f32 %0, %1, %2" : "=v"(dy) : "v"(py), "v"(qy));
+    asm("v_sub_f32 %0, %1, %2" : "=v"(dz) : "v"(pz), "v"(qz));
+    asm("v_mul_f32 %0, %1, %1" : "=v"(r) : "v"(dx));
+    if constexpr (FMA) {
+        asm("v_fma_f32 %0, %1, %1, %2" : "=v"(r) : "v"(dy), "v"(r));
+        asm("v_fma_f32 %0, %1, %1, %2" : "=v"(r) : "v"(dz), "v"(r));
+    } else {
+        float sy, sz;
+        asm("v_mul_f32 %0, %1, %1" : "=v"(sy) : "v"(dy));
+        asm("v_mul_f32 %0, %1, %1" : "=v"(sz) : "v"(dz));
+        asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(r), "v"(sy));
+        asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(r), "v"(sz));
+    }
+    return r;
 }
 
 template <int NT, int P, int MODE>
@@ -211,17 +237,11 @@ __global__ __launch_bounds__(NT) void fps_lean_kernel(FpsArgs a) {
     if (tid == 0) outbuf[0] = make_float4(__int_as_float(0), qx, qy, qz);   // row 0: sampling_cuda_kernel.cu:39
 
     for (int j = 1; j < m; ++j) {
-        const f32x2 q2x = {qx, qx}, q2y = {qy, qy}, q2z = {qz, qz};
         float best = -1.0f;
 #pragma unroll
         for (int i = 0; i < H; ++i) {
-            const f32x2 dx = x[i] - q2x, dy = y[i] - q2y, dz = z[i] - q2z;
-            f32x2 dd;
-            if constexpr (FMA)
-                dd = __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, dx * dx));
-            else
-                dd = ((dx * dx) + (dy * dy)) + (dz * dz);
-            const float n0 = vmin_f32(dd[0], d[i][0]), n1 = vmin_f32(dd[1], d[i][1]);   // min(d, tmp[k]) sampling_cuda_kernel.cu:55
+            const float n0 = vmin_f32(lean_dist<FMA>(x[i][0], y[i][0], z[i][0], qx, qy, qz), d[i][0]);   // min(d, tmp[k]) sampling_cuda_kernel.cu:55
+            const float n1 = vmin_f32(lean_dist<FMA>(x[i][1], y[i][1], z[i][1], qx, qy, qz), d[i][1]);
             d[i][0] = n0;
             d[i][1] = n1;
             best = vmax3_f32(best, n0, n1);

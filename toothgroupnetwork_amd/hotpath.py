@@ -117,7 +117,14 @@ class HotPath:
     picks, the ones the modules of pointnet2_utils run; the branches of a multi-scale level write side by side into one tensor.  No grouped tensor and no (B,S,K,.) layer output is written; level l's (B,S,C_out) output is level l+1's
     feature input.  These kernels are bound by the fp32 matrix cores and do not fit beside an FPS level-1 workgroup (120 VGPRs,
     62 KiB of LDS): the pipelined fused schedule is FPS + ball queries of step k+1 on stream F over the set-abstraction
-    kernels of step k on stream G."""
+    kernels of step k on stream G.
+
+    Reproducibility: the results of a step do not depend on the schedule.  On one stream or pipelined, with whatever kernels of
+    the neighbouring step resident beside its own, every level's fps_idx / new_xyz / group_idx are the CPU oracle's on that
+    level's input and every fused level output is the one-stream output bit for bit (no float atomics on these paths).
+    tests/test_gpu_hotpath_overlap.py checks it at Shapes A and B with B = 8 over overlapping steps, both buffer sets, and runs
+    each small-cloud FPS kernel beside a single bf16x3 / fp32-MFMA set-abstraction launch in a guarded arena
+    (profiles/fps_overlap_before_after.txt: what used to go wrong there)."""
 
     def __init__(self, B, device, shape=SHAPE_A, index_dtype=torch.int32, pipeline=False, fps_prefix=False, fused=False,
                  plan=None, group_max_blocks=None, grid_stream="own", fps_low_valu=True, fps_ties="first"):
