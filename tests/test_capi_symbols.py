@@ -81,6 +81,18 @@ def test_knnquery_refuses_more_than_128_neighbours_before_any_launch():
     assert L.tgn_last_error().decode() == "tgn_knnquery: nsample 129 > 128 unsupported (the reference's limit is 100)"
 
 
+def test_pt_attention_refuses_an_uninstantiated_width_before_any_launch():
+    """tgn_pt_attention_forward passes its argument checks with 12 weight channels (at least 4, dividing c = 24), but the kernel exists
+    for 4, 8, 16, 32 and 64 only: the dispatch (csrc/dispatch.h) matches nothing, launches nothing and says which value it got."""
+    from toothgroupnetwork_amd import _lib
+    L = _lib.lib()
+    buf = ctypes.create_string_buffer(64 + 16)
+    p = ctypes.c_void_p((ctypes.addressof(buf) + 15) & ~15)          # x_k / x_v must be 16-byte aligned
+    rc = L.tgn_pt_attention_forward(1, 4, 24, 12, *([p] * 18), None)
+    assert rc == _lib.ERR_UNSUPPORTED
+    assert L.tgn_last_error().decode() == "tgn_pt_attention_forward: weight channels must be 4, 8, 16, 32 or 64 (got 12)"
+
+
 def test_ops_refuse_cpu_tensors_loudly():
     from toothgroupnetwork_amd import pointnet2_utils as U, pointops as P
     xyz = torch.rand(1, 64, 3)

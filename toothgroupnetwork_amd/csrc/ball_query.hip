@@ -24,6 +24,7 @@
 // r_eff * 1.001 wide or wider and cell coordinates of points and queries come from the same fp32
 // expression, so such a point is at most one cell away on every axis.  Clouds containing non-finite
 // coordinates (NaN compares as "inside" in the reference) take the scan path.
+#include "dispatch.h"
 #include "grid_common.h"
 
 #include <stdlib.h>
@@ -636,15 +637,12 @@ static int ball_query_impl(int B, int N, int S, int nsample, float r2, const flo
     if (grid) {
         if (build) {
             const size_t perm_bytes = N <= kGridPermCap ? ((size_t)N * 2 + 15) / 16 * 16 : 0;   // the LDS permutation of step 4
-            // 64 KiB cell table + up to 64 KiB permutation: past the 64-KiB default of dynamic + static LDS.  The attribute belongs to
-            // the (function, device) pair, so it is set on every launch (a host-side table look-up; a once-per-process flag would
-            // leave a second GPU of the process without it)
-            if (perm_bytes && hipFuncSetAttribute((const void *)ball_grid_build_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  kGridPermCap * 2) != hipSuccess) {
-                (void)hipGetLastError();
-                set_error("tgn_ball_query: cannot raise the grid build kernel's dynamic LDS limit to %d bytes", kGridPermCap * 2);
-                return TGN_ERR_LAUNCH;
-            }
+            // 64 KiB cell table (static) + up to 64 KiB permutation: with any dynamic byte the kernel is past the 64-KiB default of
+            // dynamic + static LDS
+            if (perm_bytes)
+                if (int rc = raise_dynamic_lds(ball_grid_build_kernel, "ball_grid_build_kernel", sizeof(int) * kGridCells + perm_bytes,
+                                               kGridPermCap * 2))
+                    return rc;
             hipLaunchKernelGGL(ball_grid_build_kernel, dim3(B), dim3(kGridThreads), perm_bytes, st, N, r2, xyz,
                                (unsigned char *)workspace);
             if (int rc = check_launch("ball_grid_build_kernel")) return rc;
@@ -658,39 +656,27 @@ static int ball_query_impl(int B, int N, int S, int nsample, float r2, const flo
             const long long cpx = B >= 8 ? (long long)((B + 7) / 8) * cpc : (total_chunks + 7) / 8;
             long long wpx = cpx < 1024 ? cpx : 1024;   // waves per XCD: what is resident at a time (32 CUs x <= 32), not more
             const unsigned nblk = (unsigned)(wpx * 8);
-#define TGN_BALL_CHUNK(T_, NQ_)                                                                                            \
-    hipLaunchKernelGGL((ball_grid_query_chunk_kernel<T_, NQ_>), dim3(nblk), dim3(64), 0, st, B, N, S, nsample, r2, xyz, \
-                       new_xyz, (const unsigned char *)workspace, (T_ *)idx, (int)cpx)
-            if (idx_is_int64) {
-                if (nquad == 1) TGN_BALL_CHUNK(long long, 1);
-                else if (nquad == 2) TGN_BALL_CHUNK(long long, 2);
-                else if (nquad == 3) TGN_BALL_CHUNK(long long, 3);
-                else TGN_BALL_CHUNK(long long, 4);
-            } else {
-                if (nquad == 1) TGN_BALL_CHUNK(int, 1);
-                else if (nquad == 2) TGN_BALL_CHUNK(int, 2);
-                else if (nquad == 3) TGN_BALL_CHUNK(int, 3);
-                else TGN_BALL_CHUNK(int, 4);
-            }
-#undef TGN_BALL_CHUNK
-            return check_launch("ball_grid_query_chunk_kernel");
+            return dispatch_idx(idx, idx_is_int64, [&](auto *ip) {
+                using IT = idx_elem_t<decltype(ip)>;
+                const bool found = dispatch_int<1, 2, 3, 4>(nquad, [&](auto nq) {   // kBmMaxN: at most four bitmap quads per lane
+                    hipLaunchKernelGGL((ball_grid_query_chunk_kernel<IT, decltype(nq)::value>), dim3(nblk), dim3(64), 0, st, B, N, S,
+                                       nsample, r2, xyz, new_xyz, (const unsigned char *)workspace, ip, (int)cpx);
+                });
+                return found ? check_launch("ball_grid_query_chunk_kernel") : dispatch_miss("tgn_ball_query", "nquad", nquad);
+            });
         }
-        if (idx_is_int64)
-            hipLaunchKernelGGL((ball_grid_query_kernel<long long>), dim3((unsigned)blocks), dim3(256), 0, st, B, N, S,
-                               nsample, r2, xyz, new_xyz, (const unsigned char *)workspace, (long long *)idx);
-        else
-            hipLaunchKernelGGL((ball_grid_query_kernel<int>), dim3((unsigned)blocks), dim3(256), 0, st, B, N, S, nsample,
-                               r2, xyz, new_xyz, (const unsigned char *)workspace, (int *)idx);
-        return check_launch("ball_grid_query_kernel");
+        return dispatch_idx(idx, idx_is_int64, [&](auto *ip) {
+            hipLaunchKernelGGL((ball_grid_query_kernel<idx_elem_t<decltype(ip)>>), dim3((unsigned)blocks), dim3(256), 0, st, B, N, S,
+                               nsample, r2, xyz, new_xyz, (const unsigned char *)workspace, ip);
+            return check_launch("ball_grid_query_kernel");
+        });
     }
     if (!query) return TGN_OK;
-    if (idx_is_int64)
-        hipLaunchKernelGGL((ball_query_scan_kernel<long long>), dim3((unsigned)blocks), dim3(256), 0, st, B, N, S,
-                           nsample, r2, xyz, new_xyz, (long long *)idx);
-    else
-        hipLaunchKernelGGL((ball_query_scan_kernel<int>), dim3((unsigned)blocks), dim3(256), 0, st, B, N, S, nsample, r2,
-                           xyz, new_xyz, (int *)idx);
-    return check_launch("ball_query_scan_kernel");
+    return dispatch_idx(idx, idx_is_int64, [&](auto *ip) {
+        hipLaunchKernelGGL((ball_query_scan_kernel<idx_elem_t<decltype(ip)>>), dim3((unsigned)blocks), dim3(256), 0, st, B, N, S, nsample,
+                           r2, xyz, new_xyz, ip);
+        return check_launch("ball_query_scan_kernel");
+    });
 }
 
 TGN_API int tgn_ball_query(int B, int N, int S, int nsample, float r2, const float *xyz, const float *new_xyz,

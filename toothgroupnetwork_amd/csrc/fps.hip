@@ -22,6 +22,7 @@
 //   TGN_FPS_FMA    : d = fma(dz,dz,fma(dy,dy,dx*dx)), the contraction nvcc applies to :54.
 //   Both together = "cuda-compat"; TREE_TIES alone = the reference source compiled without contraction,
 //   which is what oracle/_ref is and what the GPU tests pin this kernel against.
+#include "dispatch.h"
 #include "fps_common.h"
 
 #include <atomic>
@@ -512,10 +513,12 @@ static int fps_dispatch(int b, int n_max, FpsArgs a, hipStream_t stream) {
     }
     a.ref_log2_block = ref_log2_block(n_max);
     const bool tree = (a.flags & TGN_FPS_TREE_TIES) != 0, fma = (a.flags & TGN_FPS_FMA) != 0;
-    if (tree) return fma ? fps_launch<3>(b, n_max, a, stream) : fps_launch<2>(b, n_max, a, stream);
-    if (a.prefix_out)  // certificate wanted: the tracking variants (the tree tie order never carries the property)
-        return fma ? fps_launch<1 | kFpsModeCert>(b, n_max, a, stream) : fps_launch<kFpsModeCert>(b, n_max, a, stream);
-    return fma ? fps_launch<1>(b, n_max, a, stream) : fps_launch<0>(b, n_max, a, stream);
+    // certificate wanted: the tracking variants (the tree tie order never carries the property)
+    const int mode = (fma ? 1 : 0) | (tree ? 2 : a.prefix_out ? kFpsModeCert : 0);
+    int rc = TGN_OK;
+    if (!dispatch_int<0, 1, 2, 3, 4, 5>(mode, [&](auto m) { rc = fps_launch<decltype(m)::value>(b, n_max, a, stream); }))
+        return dispatch_miss("tgn_furthestsampling", "mode", mode);
+    return rc;
 }
 
 }  // namespace tgn

@@ -25,6 +25,7 @@
 // lattices and duplicated vertices (exact ties) and NaN coordinates.
 // Measured (profiles/): 24 000 -> 4096 drops from 2.3 us to 1.25 us per iteration (8.6 of 375 buckets touched on
 // average; what remains is the latency of ~3 bucket updates on the busiest wave plus the block hand-off).
+#include "dispatch.h"
 #include "fps_common.h"
 
 #include <type_traits>
@@ -813,16 +814,21 @@ __global__ __launch_bounds__(NT) void fps_bucket_owner_kernel(FpsArgs a) {
     if (a.prefix_out && tid == 0) a.prefix_out[blockIdx.x] = CERT ? cert.value(m) : 1;  // not tracked: no claim
 }
 
+// the arithmetic modes every FPS kernel is instantiated for: bit 0 FMA, bit 1 tree ties, bit 2 certificate tracking (never with
+// tree ties); any other value launches nothing
+template <typename F>
+static int fps_dispatch_mode(int mode, F &&f) {
+    int rc = TGN_OK;
+    if (!dispatch_int<0, 1, 2, 3, 4, 5>(mode, [&](auto m) { rc = f(m); })) return dispatch_miss("tgn_furthestsampling", "mode", mode);
+    return rc;
+}
+
 template <int G>
-static void fps_owner_launch_g(int mode, int b, const FpsArgs &a, hipStream_t stream) {
-    switch (mode) {
-        case 0: hipLaunchKernelGGL((fps_bucket_owner_kernel<0, G>), dim3(b), dim3(kStreamThreads), 0, stream, a); break;
-        case 1: hipLaunchKernelGGL((fps_bucket_owner_kernel<1, G>), dim3(b), dim3(kStreamThreads), 0, stream, a); break;
-        case 2: hipLaunchKernelGGL((fps_bucket_owner_kernel<2, G>), dim3(b), dim3(kStreamThreads), 0, stream, a); break;
-        case 3: hipLaunchKernelGGL((fps_bucket_owner_kernel<3, G>), dim3(b), dim3(kStreamThreads), 0, stream, a); break;
-        case 4: hipLaunchKernelGGL((fps_bucket_owner_kernel<4, G>), dim3(b), dim3(kStreamThreads), 0, stream, a); break;
-        default: hipLaunchKernelGGL((fps_bucket_owner_kernel<5, G>), dim3(b), dim3(kStreamThreads), 0, stream, a); break;
-    }
+static int fps_owner_launch_g(int mode, int b, const FpsArgs &a, hipStream_t stream) {
+    return fps_dispatch_mode(mode, [&](auto m) {
+        hipLaunchKernelGGL((fps_bucket_owner_kernel<decltype(m)::value, G>), dim3(b), dim3(kStreamThreads), 0, stream, a);
+        return check_launch("fps_bucket_owner_kernel");
+    });
 }
 
 size_t fps_stream_workspace_bytes(int b, int n_max) {
@@ -833,11 +839,10 @@ size_t fps_stream_workspace_bytes(int b, int n_max) {
 int fps_bucket_stream_launch(int mode, int b, int n_max, const FpsArgs &a, hipStream_t stream) {
     if (!a.ws || n_max > kStreamMaxBuckets * kWave || a.ws_bytes < fps_stream_workspace_bytes(b, n_max)) return -1;
     const int slots = ((n_max + 63) / 64 + 15) / 16;   // buckets per wave
-    if (slots <= 64) fps_owner_launch_g<1>(mode, b, a, stream);
-    else if (slots <= 128) fps_owner_launch_g<2>(mode, b, a, stream);
-    else if (slots <= 192) fps_owner_launch_g<3>(mode, b, a, stream);
-    else fps_owner_launch_g<4>(mode, b, a, stream);
-    return check_launch("fps_bucket_owner_kernel");
+    if (slots <= 64) return fps_owner_launch_g<1>(mode, b, a, stream);
+    if (slots <= 128) return fps_owner_launch_g<2>(mode, b, a, stream);
+    if (slots <= 192) return fps_owner_launch_g<3>(mode, b, a, stream);
+    return fps_owner_launch_g<4>(mode, b, a, stream);   // n_max <= kStreamMaxBuckets * kWave: at most 256 slots
 }
 
 // TGN_FPS_THROUGHPUT: 8 waves x 64 bucket lanes = 512 buckets = 32 768 points, 4096 Z-order cells (16 KiB of LDS), 58 VGPRs:
@@ -845,15 +850,11 @@ int fps_bucket_stream_launch(int mode, int b, int n_max, const FpsArgs &a, hipSt
 constexpr int kOwnerSmallThreads = 512, kOwnerSmallMax = kOwnerSmallThreads / kWave * kWave * kWave;
 int fps_bucket_owner_small_launch(int mode, int b, int n_max, const FpsArgs &a, hipStream_t stream) {
     if (!a.ws || n_max > kOwnerSmallMax || n_max <= 0 || a.ws_bytes < fps_stream_workspace_bytes(b, n_max)) return -1;
-    switch (mode) {
-        case 0: hipLaunchKernelGGL((fps_bucket_owner_kernel<0, 1, kOwnerSmallThreads, 4>), dim3(b), dim3(kOwnerSmallThreads), 0, stream, a); break;
-        case 1: hipLaunchKernelGGL((fps_bucket_owner_kernel<1, 1, kOwnerSmallThreads, 4>), dim3(b), dim3(kOwnerSmallThreads), 0, stream, a); break;
-        case 2: hipLaunchKernelGGL((fps_bucket_owner_kernel<2, 1, kOwnerSmallThreads, 4>), dim3(b), dim3(kOwnerSmallThreads), 0, stream, a); break;
-        case 3: hipLaunchKernelGGL((fps_bucket_owner_kernel<3, 1, kOwnerSmallThreads, 4>), dim3(b), dim3(kOwnerSmallThreads), 0, stream, a); break;
-        case 4: hipLaunchKernelGGL((fps_bucket_owner_kernel<4, 1, kOwnerSmallThreads, 4>), dim3(b), dim3(kOwnerSmallThreads), 0, stream, a); break;
-        default: hipLaunchKernelGGL((fps_bucket_owner_kernel<5, 1, kOwnerSmallThreads, 4>), dim3(b), dim3(kOwnerSmallThreads), 0, stream, a); break;
-    }
-    return check_launch("fps_bucket_owner_kernel<small>");
+    return fps_dispatch_mode(mode, [&](auto m) {
+        hipLaunchKernelGGL((fps_bucket_owner_kernel<decltype(m)::value, 1, kOwnerSmallThreads, 4>), dim3(b), dim3(kOwnerSmallThreads), 0,
+                           stream, a);
+        return check_launch("fps_bucket_owner_kernel<small>");
+    });
 }
 
 #define TGN_FPS_BUCKET_CONFIGS(X) X(256, 8) X(256, 16) X(512, 16) X(512, 24) X(512, 32) X(512, 48) X(512, 56)
@@ -901,14 +902,7 @@ int fps_bucket_launch(int mode, int b, int n_max, const FpsArgs &a, hipStream_t 
     int min_n = (a.flags & TGN_FPS_LOW_VALU) ? 2048 : 4097;
     if (const int forced = tuning(kTuneFpsBucketMin); forced >= 0) min_n = forced <= kFpsPlainMaxN ? forced : kFpsPlainMaxN + 1;
     if (n_max < min_n) return -1;
-    switch (mode) {  // bit 0 FMA, bit 1 tree ties, bit 2 certificate tracking (never with tree ties)
-        case 0: return bucket_launch_mode<0>(b, n_max, a, stream);
-        case 1: return bucket_launch_mode<1>(b, n_max, a, stream);
-        case 2: return bucket_launch_mode<2>(b, n_max, a, stream);
-        case 3: return bucket_launch_mode<3>(b, n_max, a, stream);
-        case 4: return bucket_launch_mode<4>(b, n_max, a, stream);
-        default: return bucket_launch_mode<5>(b, n_max, a, stream);
-    }
+    return fps_dispatch_mode(mode, [&](auto m) { return bucket_launch_mode<decltype(m)::value>(b, n_max, a, stream); });
 }
 
 }  // namespace tgn

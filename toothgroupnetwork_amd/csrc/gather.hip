@@ -11,6 +11,7 @@
 // The reference uses one thread per output ELEMENT with two integer divisions each; here a block is a
 // (rows x channel-lanes) tile: the gather index is read once per row, lanes run along the contiguous
 // channel axis (coalesced row reads and writes), and there is no per-element division.
+#include "dispatch.h"
 #include "tgn_common.h"
 
 #include <stdlib.h>
@@ -35,11 +36,14 @@ static RowShape row_shape(long long rows, int c) {
     return s;
 }
 
-#define TGN_ROW_LOOP(rows)                                                                          \
-    const int cx = 1 << cx_log2;                                                                    \
-    const int tx = threadIdx.x & (cx - 1);                                                          \
-    const int ty = threadIdx.x >> cx_log2;                                                          \
-    const int ry = blockDim.x >> cx_log2;                                                           \
+// a block is ry groups of cx = 2^cx_log2 lanes: lane tx of group ty
+#define TGN_ROW_LANES                       \
+    const int cx = 1 << cx_log2;            \
+    const int tx = threadIdx.x & (cx - 1);  \
+    const int ty = threadIdx.x >> cx_log2;  \
+    const int ry = blockDim.x >> cx_log2;
+#define TGN_ROW_LOOP(rows) \
+    TGN_ROW_LANES          \
     for (long long r = (long long)blockIdx.x * ry + ty; r < (rows); r += (long long)gridDim.x * ry)
 
 // ---- grouping ---------------------------------------------------------------------------------
@@ -200,12 +204,6 @@ static Vec4Shape vec4_shape(long long units, int c, int units_per_group_pass) {
 
 static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-#define TGN_V4_LANES                        \
-    const int cx = 1 << cx_log2;            \
-    const int tx = threadIdx.x & (cx - 1);  \
-    const int ty = threadIdx.x >> cx_log2;  \
-    const int ry = blockDim.x >> cx_log2;
-
 constexpr int kV4Rows = 4;  // output rows a lane keeps in flight
 
 template <bool SUB>
@@ -215,7 +213,7 @@ __global__ __launch_bounds__(256) void gather_rows_v4_kernel(long long rows, int
                                                               const int *__restrict__ idx, f4 *__restrict__ output) {
     // SUB = false: output[r] = input2[idx[r]]                    (grouping forward; input1 unused)
     // SUB = true : output[r] = input1[r / nsample] - input2[idx[r]]   (subtraction forward)
-    TGN_V4_LANES
+    TGN_ROW_LANES
     const long long step = (long long)gridDim.x * kV4Rows * ry;
     for (long long r0 = (long long)blockIdx.x * kV4Rows * ry + ty; r0 < rows; r0 += step) {
         int id[kV4Rows];
@@ -247,7 +245,7 @@ __global__ __launch_bounds__(256) void interpolation_fwd_v4_kernel(long long row
                                                                     const int *__restrict__ idx,
                                                                     const float *__restrict__ weight,
                                                                     f4 *__restrict__ output) {
-    TGN_V4_LANES
+    TGN_ROW_LANES
     for (long long r = (long long)blockIdx.x * ry + ty; r < rows; r += (long long)gridDim.x * ry) {
         for (int ci = tx; ci < c4; ci += cx) {
             f4 acc = output[(size_t)r * c4 + ci];  // the reference accumulates into the (pre-zeroed) output
@@ -263,7 +261,7 @@ __global__ __launch_bounds__(256) void aggregation_fwd_v4_kernel(long long n, in
                                                                   const f4 *__restrict__ weight,
                                                                   const int *__restrict__ idx, f4 *__restrict__ output) {
     // w4 = w_c / 4: channel quad ci reads weight quad ci % w4 (channels 4ci..4ci+3 -> weights (4ci % w_c)..+3)
-    TGN_V4_LANES
+    TGN_ROW_LANES
     for (long long p = (long long)blockIdx.x * ry + ty; p < n; p += (long long)gridDim.x * ry) {
         const int *__restrict__ ip = idx + p * nsample;
         for (int ci = tx; ci < c4; ci += cx) {
@@ -288,7 +286,7 @@ __global__ __launch_bounds__(256) void subtraction_bwd_own_kernel(long long n, i
                                                                    const float *__restrict__ grad_output,
                                                                    float *__restrict__ grad_input1,
                                                                    float *__restrict__ grad_input2) {
-    TGN_V4_LANES
+    TGN_ROW_LANES
     for (long long p = (long long)blockIdx.x * ry + ty; p < n; p += (long long)gridDim.x * ry) {
         const int *__restrict__ ip = idx + p * nsample;
         for (int ci = tx; ci < c; ci += cx) {
@@ -315,7 +313,7 @@ __global__ __launch_bounds__(256) void aggregation_bwd_own_kernel(long long n, i
                                                                    float *__restrict__ grad_position,
                                                                    float *__restrict__ grad_weight) {
     // c == cx lanes (a power of two <= 64), w_c a power of two dividing it: lanes tx, tx + w_c, ... share weight tx % w_c
-    TGN_V4_LANES
+    TGN_ROW_LANES
     const int c = cx;
     const int wci = tx & (w_c - 1);
     for (long long p = (long long)blockIdx.x * ry + ty; p < n; p += (long long)gridDim.x * ry) {
@@ -372,31 +370,19 @@ __global__ __launch_bounds__(256) void scatter_add_points_kernel(long long rows,
     }
 }
 
-template <typename IdxT>
-__global__ __launch_bounds__(256) void three_interpolate_kernel(long long rows, int N, int S, int C, int cx_log2,
-                                                                 const float *__restrict__ points2,
-                                                                 const float *__restrict__ dist,
-                                                                 const IdxT *__restrict__ idx, float *__restrict__ out,
-                                                                 float *__restrict__ weight) {
-    TGN_ROW_LOOP(rows) {  // r = b*N + n
-        const int b = (int)(r / N);
-        // pointnet2_utils.py:337-339: 1/(d + 1e-8), normalised by the row sum
-        const float r0 = 1.0f / (dist[r * 3 + 0] + 1e-8f);
-        const float r1 = 1.0f / (dist[r * 3 + 1] + 1e-8f);
-        const float r2 = 1.0f / (dist[r * 3 + 2] + 1e-8f);
-        const float norm = (r0 + r1) + r2;
-        const float w0 = r0 / norm, w1 = r1 / norm, w2 = r2 / norm;
-        if (weight && tx == 0) {
-            weight[r * 3 + 0] = w0;
-            weight[r * 3 + 1] = w1;
-            weight[r * 3 + 2] = w2;
-        }
-        const float *f0 = points2 + ((size_t)b * S + (long long)idx[r * 3 + 0]) * C;
-        const float *f1 = points2 + ((size_t)b * S + (long long)idx[r * 3 + 1]) * C;
-        const float *f2 = points2 + ((size_t)b * S + (long long)idx[r * 3 + 2]) * C;
-        float *dst = out + (size_t)r * C;
-        for (int ci = tx; ci < C; ci += cx)
-            dst[ci] = ((f0[ci] * w0) + (f1[ci] * w1)) + (f2[ci] * w2);
+// pointnet2_utils.py:337-339: the weights 1/(d + 1e-8) of row r's three neighbours, normalised by the row sum; lane 0 of the
+// row's group stores them when the caller wants them
+__device__ __forceinline__ void three_weights(const float *__restrict__ dist, long long r, int tx, float *__restrict__ weight,
+                                              float &w0, float &w1, float &w2) {
+    const float r0 = 1.0f / (dist[r * 3 + 0] + 1e-8f);
+    const float r1 = 1.0f / (dist[r * 3 + 1] + 1e-8f);
+    const float r2 = 1.0f / (dist[r * 3 + 2] + 1e-8f);
+    const float norm = (r0 + r1) + r2;
+    w0 = r0 / norm, w1 = r1 / norm, w2 = r2 / norm;
+    if (weight && tx == 0) {
+        weight[r * 3 + 0] = w0;
+        weight[r * 3 + 1] = w1;
+        weight[r * 3 + 2] = w2;
     }
 }
 
@@ -409,19 +395,11 @@ __global__ __launch_bounds__(256) void three_interpolate_v4_kernel(long long row
                                                                     const float *__restrict__ dist,
                                                                     const IdxT *__restrict__ idx, const f4 *add, int relu,
                                                                     f4 *out, float *__restrict__ weight) {
-    TGN_V4_LANES
+    TGN_ROW_LANES
     for (long long r = (long long)blockIdx.x * ry + ty; r < rows; r += (long long)gridDim.x * ry) {
         const int b = (int)(r / N);
-        const float r0 = 1.0f / (dist[r * 3 + 0] + 1e-8f);
-        const float r1 = 1.0f / (dist[r * 3 + 1] + 1e-8f);
-        const float r2 = 1.0f / (dist[r * 3 + 2] + 1e-8f);
-        const float norm = (r0 + r1) + r2;
-        const float w0 = r0 / norm, w1 = r1 / norm, w2 = r2 / norm;
-        if (weight && tx == 0) {
-            weight[r * 3 + 0] = w0;
-            weight[r * 3 + 1] = w1;
-            weight[r * 3 + 2] = w2;
-        }
+        float w0, w1, w2;
+        three_weights(dist, r, tx, weight, w0, w1, w2);
         const f4 *f0 = points2 + ((size_t)b * S + (long long)idx[r * 3 + 0]) * c4;
         const f4 *f1 = points2 + ((size_t)b * S + (long long)idx[r * 3 + 1]) * c4;
         const f4 *f2 = points2 + ((size_t)b * S + (long long)idx[r * 3 + 2]) * c4;
@@ -447,16 +425,8 @@ __global__ __launch_bounds__(256) void three_interpolate_epilogue_kernel(long lo
                                                                           int relu, float *out, float *__restrict__ weight) {
     TGN_ROW_LOOP(rows) {   // dword lanes: channel counts that are no multiple of 4 / unaligned rows
         const int b = (int)(r / N);
-        const float r0 = 1.0f / (dist[r * 3 + 0] + 1e-8f);
-        const float r1 = 1.0f / (dist[r * 3 + 1] + 1e-8f);
-        const float r2 = 1.0f / (dist[r * 3 + 2] + 1e-8f);
-        const float norm = (r0 + r1) + r2;
-        const float w0 = r0 / norm, w1 = r1 / norm, w2 = r2 / norm;
-        if (weight && tx == 0) {
-            weight[r * 3 + 0] = w0;
-            weight[r * 3 + 1] = w1;
-            weight[r * 3 + 2] = w2;
-        }
+        float w0, w1, w2;
+        three_weights(dist, r, tx, weight, w0, w1, w2);
         const float *f0 = points2 + ((size_t)b * S + (long long)idx[r * 3 + 0]) * C;
         const float *f1 = points2 + ((size_t)b * S + (long long)idx[r * 3 + 1]) * C;
         const float *f2 = points2 + ((size_t)b * S + (long long)idx[r * 3 + 2]) * C;
@@ -602,13 +572,11 @@ TGN_API int tgn_gather_points(int B, int N, int M, int C, const float *points, c
     if (rows <= 0 || C <= 0) return TGN_OK;
     int *err = index_error_word((hipStream_t)stream);
     const RowShape s = row_shape(rows, C);
-    if (idx_is_int64)
-        hipLaunchKernelGGL((gather_points_kernel<long long>), dim3(s.blocks), dim3(256), 0, (hipStream_t)stream, rows, N,
-                           M, C, s.cx_log2, points, (const long long *)idx, out, err);
-    else
-        hipLaunchKernelGGL((gather_points_kernel<int>), dim3(s.blocks), dim3(256), 0, (hipStream_t)stream, rows, N, M, C,
-                           s.cx_log2, points, (const int *)idx, out, err);
-    return check_launch("gather_points_kernel");
+    return dispatch_idx(idx, idx_is_int64, [&](auto *ip) {
+        hipLaunchKernelGGL((gather_points_kernel<idx_elem_t<decltype(ip)>>), dim3(s.blocks), dim3(256), 0, (hipStream_t)stream, rows, N, M,
+                           C, s.cx_log2, points, ip, out, err);
+        return check_launch("gather_points_kernel");
+    });
 }
 
 TGN_API int tgn_scatter_add_points(int B, int N, int M, int C, const float *grad_out, const void *idx,
@@ -616,27 +584,11 @@ TGN_API int tgn_scatter_add_points(int B, int N, int M, int C, const float *grad
     const long long rows = (long long)B * M;
     if (rows <= 0 || C <= 0) return TGN_OK;
     const RowShape s = row_shape(rows, C);
-    if (idx_is_int64)
-        hipLaunchKernelGGL((scatter_add_points_kernel<long long>), dim3(s.blocks), dim3(256), 0, (hipStream_t)stream,
-                           rows, N, M, C, s.cx_log2, grad_out, (const long long *)idx, grad_points);
-    else
-        hipLaunchKernelGGL((scatter_add_points_kernel<int>), dim3(s.blocks), dim3(256), 0, (hipStream_t)stream, rows, N,
-                           M, C, s.cx_log2, grad_out, (const int *)idx, grad_points);
-    return check_launch("scatter_add_points_kernel");
-}
-
-TGN_API int tgn_three_interpolate(int B, int N, int S, int C, const float *points2, const float *dist,
-                                  const void *idx, int idx_is_int64, float *out, float *weight, tgn_stream_t stream) {
-    const long long rows = (long long)B * N;
-    if (rows <= 0 || C <= 0) return TGN_OK;
-    const RowShape s = row_shape(rows, C);
-    if (idx_is_int64)
-        hipLaunchKernelGGL((three_interpolate_kernel<long long>), dim3(s.blocks), dim3(256), 0, (hipStream_t)stream, rows,
-                           N, S, C, s.cx_log2, points2, dist, (const long long *)idx, out, weight);
-    else
-        hipLaunchKernelGGL((three_interpolate_kernel<int>), dim3(s.blocks), dim3(256), 0, (hipStream_t)stream, rows, N, S,
-                           C, s.cx_log2, points2, dist, (const int *)idx, out, weight);
-    return check_launch("three_interpolate_kernel");
+    return dispatch_idx(idx, idx_is_int64, [&](auto *ip) {
+        hipLaunchKernelGGL((scatter_add_points_kernel<idx_elem_t<decltype(ip)>>), dim3(s.blocks), dim3(256), 0, (hipStream_t)stream, rows,
+                           N, M, C, s.cx_log2, grad_out, ip, grad_points);
+        return check_launch("scatter_add_points_kernel");
+    });
 }
 
 TGN_API int tgn_three_interpolate_ex(int B, int N, int S, int C, const float *points2, const float *dist, const void *idx,
@@ -648,25 +600,26 @@ TGN_API int tgn_three_interpolate_ex(int B, int N, int S, int C, const float *po
         set_error("tgn_three_interpolate_ex: null pointer");
         return TGN_ERR_INVALID_ARGUMENT;
     }
-    if (C % 4 == 0 && aligned16(points2) && aligned16(out) && (!add || aligned16(add))) {
-        const Vec4Shape v = vec4_shape(rows, C, 1);
-        if (idx_is_int64)
-            hipLaunchKernelGGL((three_interpolate_v4_kernel<long long>), dim3(v.blocks), dim3(256), 0, (hipStream_t)stream, rows, N, S,
-                               C / 4, v.cx_log2, (const f4 *)points2, dist, (const long long *)idx, (const f4 *)add, relu, (f4 *)out,
-                               weight);
-        else
-            hipLaunchKernelGGL((three_interpolate_v4_kernel<int>), dim3(v.blocks), dim3(256), 0, (hipStream_t)stream, rows, N, S, C / 4,
-                               v.cx_log2, (const f4 *)points2, dist, (const int *)idx, (const f4 *)add, relu, (f4 *)out, weight);
-        return check_launch("three_interpolate_v4_kernel");
-    }
-    const RowShape s = row_shape(rows, C);
-    if (idx_is_int64)
-        hipLaunchKernelGGL((three_interpolate_epilogue_kernel<long long>), dim3(s.blocks), dim3(256), 0, (hipStream_t)stream, rows, N,
-                           S, C, s.cx_log2, points2, dist, (const long long *)idx, add, relu, out, weight);
-    else
-        hipLaunchKernelGGL((three_interpolate_epilogue_kernel<int>), dim3(s.blocks), dim3(256), 0, (hipStream_t)stream, rows, N, S, C,
-                           s.cx_log2, points2, dist, (const int *)idx, add, relu, out, weight);
-    return check_launch("three_interpolate_epilogue_kernel");
+    const bool v4 = C % 4 == 0 && aligned16(points2) && aligned16(out) && (!add || aligned16(add));
+    return dispatch_idx(idx, idx_is_int64, [&](auto *ip) {
+        using IT = idx_elem_t<decltype(ip)>;
+        if (v4) {
+            const Vec4Shape v = vec4_shape(rows, C, 1);
+            hipLaunchKernelGGL((three_interpolate_v4_kernel<IT>), dim3(v.blocks), dim3(256), 0, (hipStream_t)stream, rows, N, S, C / 4,
+                               v.cx_log2, (const f4 *)points2, dist, ip, (const f4 *)add, relu, (f4 *)out, weight);
+            return check_launch("three_interpolate_v4_kernel");
+        }
+        const RowShape s = row_shape(rows, C);
+        hipLaunchKernelGGL((three_interpolate_epilogue_kernel<IT>), dim3(s.blocks), dim3(256), 0, (hipStream_t)stream, rows, N, S, C,
+                           s.cx_log2, points2, dist, ip, add, relu, out, weight);
+        return check_launch("three_interpolate_epilogue_kernel");
+    });
+}
+
+// the plain interpolation is the fused form without an epilogue
+TGN_API int tgn_three_interpolate(int B, int N, int S, int C, const float *points2, const float *dist, const void *idx,
+                                  int idx_is_int64, float *out, float *weight, tgn_stream_t stream) {
+    return tgn_three_interpolate_ex(B, N, S, C, points2, dist, idx, idx_is_int64, nullptr, 0, out, weight, stream);
 }
 
 // ---- reference ABI (default stream, void) ---------------------------------------------------------

@@ -14,6 +14,7 @@
 //     the feature block under 17 MB of output per scan; sc1 stores leave L2 to the gather source;
 //   * how many scans an XCD has in flight: each XCD walks ONE contiguous range of queries with a bounded
 //     number of resident blocks, so all its waves gather from the same scan's feature block.
+#include "dispatch.h"
 #include "tgn_common.h"
 
 #include <stdlib.h>
@@ -674,25 +675,17 @@ TGN_API int tgn_group_points_ex(int B, int N, int S, int K, int D, const float *
             if (blocks > 256) blocks = 256;                        // per XCD: 32 CUs x 8 blocks
             if (max_blocks > 0 && max_blocks / 8 < blocks) blocks = max_blocks / 8 > 0 ? max_blocks / 8 : 1;
             const dim3 grid((unsigned)blocks * 8u);
-#define TGN_GROUP_PAIRS(IT, DD)                                                                                        \
-    do {                                                                                                               \
-        if (store_policy == 0)                                                                                         \
-            hipLaunchKernelGGL((group_points_pairs_kernel<IT, DD, 0>), grid, dim3(256), 0, st, chunks, cpx, cps, N, log2K, xyz, \
-                               new_xyz, pts, (const IT *)idx, xyz_first, out, err);                                    \
-        else if (store_policy == 2)                                                                                    \
-            hipLaunchKernelGGL((group_points_pairs_kernel<IT, DD, 2>), grid, dim3(256), 0, st, chunks, cpx, cps, N, log2K, xyz, \
-                               new_xyz, pts, (const IT *)idx, xyz_first, out, err);                                    \
-        else                                                                                                           \
-            hipLaunchKernelGGL((group_points_pairs_kernel<IT, DD, 16>), grid, dim3(256), 0, st, chunks, cpx, cps, N, log2K, xyz, \
-                               new_xyz, pts, (const IT *)idx, xyz_first, out, err);                                    \
-    } while (0)
-            if (idx_is_int64) {
-                if (D == 0) TGN_GROUP_PAIRS(long long, 0); else if (D == 3) TGN_GROUP_PAIRS(long long, 3); else TGN_GROUP_PAIRS(long long, 6);
-            } else {
-                if (D == 0) TGN_GROUP_PAIRS(int, 0); else if (D == 3) TGN_GROUP_PAIRS(int, 3); else TGN_GROUP_PAIRS(int, 6);
-            }
-#undef TGN_GROUP_PAIRS
-            return check_launch("group_points_pairs_kernel");
+            if (store_policy != 0 && store_policy != 2) store_policy = 16;   // any other policy: sc1, the image kernels' third form
+            return dispatch_idx(idx, idx_is_int64, [&](auto *ip) {
+                bool found = false;
+                dispatch_int<0, 3, 6>(D, [&](auto dd) {
+                    found = dispatch_int<0, 2, 16>(store_policy, [&](auto pol) {
+                        hipLaunchKernelGGL((group_points_pairs_kernel<idx_elem_t<decltype(ip)>, decltype(dd)::value, decltype(pol)::value>),
+                                           grid, dim3(256), 0, st, chunks, cpx, cps, N, log2K, xyz, new_xyz, pts, ip, xyz_first, out, err);
+                    });
+                });
+                return found ? check_launch("group_points_pairs_kernel") : dispatch_miss("tgn_group_points", "D", D);
+            });
         }
     }
     // default: the row-piece kernel for wide rows (a bounded grid means "runs beside something that owns most of every
@@ -703,13 +696,11 @@ TGN_API int tgn_group_points_ex(int B, int N, int S, int K, int D, const float *
     if (impl == 1) {
         long long blocks = ((queries + 3) / 4 + 7) / 8 * 8;  // one query per wave, grid a multiple of the 8 XCDs
         if (blocks > (1LL << 30)) blocks = 1LL << 30;
-        if (idx_is_int64)
-            hipLaunchKernelGGL((group_points_kernel<long long>), dim3((unsigned)blocks), dim3(256), 0, st, queries, N, S,
-                               K, D, magicC, xyz, new_xyz, pts, (const long long *)idx, xyz_first, out, err);
-        else
-            hipLaunchKernelGGL((group_points_kernel<int>), dim3((unsigned)blocks), dim3(256), 0, st, queries, N, S, K, D,
-                               magicC, xyz, new_xyz, pts, (const int *)idx, xyz_first, out, err);
-        return check_launch("group_points_kernel");
+        return dispatch_idx(idx, idx_is_int64, [&](auto *ip) {
+            hipLaunchKernelGGL((group_points_kernel<idx_elem_t<decltype(ip)>>), dim3((unsigned)blocks), dim3(256), 0, st, queries, N, S, K,
+                               D, magicC, xyz, new_xyz, pts, ip, xyz_first, out, err);
+            return check_launch("group_points_kernel");
+        });
     }
     if (impl == 7) {
         if (store_policy < 0) store_policy = 2;   // nt, see the pairs kernel above
@@ -728,20 +719,20 @@ TGN_API int tgn_group_points_ex(int B, int N, int S, int K, int D, const float *
         long long capw = 32 * per_cu;            // ... per XCD: the grid is exactly what is resident
         if (max_blocks > 0 && (long long)max_blocks * 4 / 8 < capw) capw = (long long)max_blocks * 4 / 8 > 0 ? (long long)max_blocks * 4 / 8 : 1;
         if (nb > capw) nb = capw;
-#define TGN_GROUP_ROWS(IT, POL)                                                                                       \
-    do {                                                                                                              \
-        auto kfn = wide_dma ? group_points_rows_kernel<IT, POL, 4> : group_points_rows_kernel<IT, POL, 1>;            \
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(kfn, dim3((unsigned)(nb * 8)), dim3(64), lds, st, queries, qx, N, S, K, D, R, xyz, new_xyz, pts, \
-                           (const IT *)idx, xyz_first, out, err);                                                     \
-    } while (0)
-        if (idx_is_int64) {
-            if (store_policy == 0) TGN_GROUP_ROWS(long long, 0); else if (store_policy == 2) TGN_GROUP_ROWS(long long, 2); else TGN_GROUP_ROWS(long long, 16);
-        } else {
-            if (store_policy == 0) TGN_GROUP_ROWS(int, 0); else if (store_policy == 2) TGN_GROUP_ROWS(int, 2); else TGN_GROUP_ROWS(int, 16);
-        }
-#undef TGN_GROUP_ROWS
-        return check_launch("group_points_rows_kernel");
+        if (store_policy != 0 && store_policy != 2) store_policy = 16;   // any other policy: sc1, as in the pairs kernel
+        return dispatch_idx(idx, idx_is_int64, [&](auto *ip) {
+            int rc = TGN_OK;
+            const bool found = dispatch_int<0, 2, 16>(store_policy, [&](auto pol) {
+                dispatch_bool(wide_dma, [&](auto wide) {
+                    auto kfn = group_points_rows_kernel<idx_elem_t<decltype(ip)>, decltype(pol)::value, decltype(wide)::value ? 4 : 1>;
+                    if ((rc = raise_dynamic_lds(kfn, "group_points_rows_kernel", lds, lds)) != TGN_OK) return;
+                    hipLaunchKernelGGL(kfn, dim3((unsigned)(nb * 8)), dim3(64), lds, st, queries, qx, N, S, K, D, R, xyz, new_xyz, pts, ip,
+                                       xyz_first, out, err);
+                    rc = check_launch("group_points_rows_kernel");
+                });
+            });
+            return found ? rc : dispatch_miss("tgn_group_points", "store policy", store_policy);
+        });
     }
     // staged 16-B stores: per-XCD query ranges (whole scans when B >= 8), at most 8 blocks per CU resident
     long long q_per_xcd = B >= 8 ? (long long)((B + 7) / 8) * S : ((queries + 7) / 8 + 3) / 4 * 4;
@@ -750,32 +741,17 @@ TGN_API int tgn_group_points_ex(int B, int N, int S, int K, int D, const float *
     if (max_blocks > 0 && max_blocks / 8 < cap) cap = max_blocks / 8 > 0 ? max_blocks / 8 : 1;
     if (nbx > cap) nbx = cap;
     const dim3 grid((unsigned)(nbx * 8));
-#define TGN_GROUP_V2(IT, POL)                                                                                            \
-    do {                                                                                                                 \
-        if (C >= 64 && K <= 64)                                                                                          \
-            hipLaunchKernelGGL((group_points_v2_kernel<IT, POL, true>), grid, dim3(256), 0, st, queries, q_per_xcd, N,   \
-                               S, K, D, magicC, xyz, new_xyz, pts, (const IT *)idx, xyz_first, out, err);                \
-        else                                                                                                             \
-            hipLaunchKernelGGL((group_points_v2_kernel<IT, POL, false>), grid, dim3(256), 0, st, queries, q_per_xcd, N,  \
-                               S, K, D, magicC, xyz, new_xyz, pts, (const IT *)idx, xyz_first, out, err);                \
-    } while (0)
     if (store_policy < 0) store_policy = 16;   // write-through (profiles/r01_store_bench.txt)
-#define TGN_GROUP_V2_POL(IT)                                   \
-    switch (store_policy) {                                    \
-        case 0: TGN_GROUP_V2(IT, 0); break;                    \
-        case 2: TGN_GROUP_V2(IT, 2); break;                    \
-        case 17: TGN_GROUP_V2(IT, 17); break;                  \
-        case 18: TGN_GROUP_V2(IT, 18); break;                  \
-        default: TGN_GROUP_V2(IT, 16); break;                  \
-    }
-    if (idx_is_int64) {
-        TGN_GROUP_V2_POL(long long)
-    } else {
-        TGN_GROUP_V2_POL(int)
-    }
-#undef TGN_GROUP_V2_POL
-#undef TGN_GROUP_V2
-    return check_launch("group_points_v2_kernel");
+    if (store_policy != 0 && store_policy != 2 && store_policy != 17 && store_policy != 18) store_policy = 16;   // ... and any unknown policy
+    return dispatch_idx(idx, idx_is_int64, [&](auto *ip) {
+        const bool found = dispatch_int<0, 2, 16, 17, 18>(store_policy, [&](auto pol) {
+            dispatch_bool(C >= 64 && K <= 64, [&](auto wide) {
+                hipLaunchKernelGGL((group_points_v2_kernel<idx_elem_t<decltype(ip)>, decltype(pol)::value, decltype(wide)::value>), grid,
+                                   dim3(256), 0, st, queries, q_per_xcd, N, S, K, D, magicC, xyz, new_xyz, pts, ip, xyz_first, out, err);
+            });
+        });
+        return found ? check_launch("group_points_v2_kernel") : dispatch_miss("tgn_group_points", "store policy", store_policy);
+    });
 }
 
 TGN_API int tgn_group_points(int B, int N, int S, int K, int D, const float *xyz, const float *new_xyz,

@@ -4,6 +4,7 @@
 //              preserved exactly (insertion history decides the order of equal distances).
 // three_nn   : the square_distance + full sort + [:3] of PointNetFeaturePropagation
 //              (pointnet2_utils.py:333-335) as a running top-3 by (distance, index).
+#include "dispatch.h"
 #include "grid_common.h"
 #include <stdlib.h>
 
@@ -697,22 +698,15 @@ TGN_API int tgn_three_nn(int B, int N, int S, const float *xyz1, const float *xy
         set_error("tgn_three_nn: bad argument");
         return TGN_ERR_INVALID_ARGUMENT;
     }
-    if (S <= kTnnTile && S >= 16 && (long long)B * N <= 32768) {   // few queries: four waves per 64 queries (three_nn_split_kernel)
-        dim3 grid4((N + kWave - 1) / kWave, B);
-        if (idx_is_int64)
-            hipLaunchKernelGGL((three_nn_split_kernel<long long>), grid4, dim3(256), 0, (hipStream_t)stream, B, N, S, xyz1, xyz2, dist,
-                               (long long *)idx);
-        else
-            hipLaunchKernelGGL((three_nn_split_kernel<int>), grid4, dim3(256), 0, (hipStream_t)stream, B, N, S, xyz1, xyz2, dist,
-                               (int *)idx);
-        return check_launch("three_nn_split_kernel");
-    }
-    dim3 grid((N + 255) / 256, B);
-    if (idx_is_int64)
-        hipLaunchKernelGGL((three_nn_kernel<long long>), grid, dim3(256), 0, (hipStream_t)stream, B, N, S, xyz1, xyz2,
-                           dist, (long long *)idx);
-    else
-        hipLaunchKernelGGL((three_nn_kernel<int>), grid, dim3(256), 0, (hipStream_t)stream, B, N, S, xyz1, xyz2, dist,
-                           (int *)idx);
-    return check_launch("three_nn_kernel");
+    hipStream_t st = (hipStream_t)stream;
+    return dispatch_idx(idx, idx_is_int64, [&](auto *ip) {
+        using IT = idx_elem_t<decltype(ip)>;
+        if (S <= kTnnTile && S >= 16 && (long long)B * N <= 32768) {   // few queries: four waves per 64 queries (three_nn_split_kernel)
+            hipLaunchKernelGGL((three_nn_split_kernel<IT>), dim3((N + kWave - 1) / kWave, B), dim3(256), 0, st, B, N, S, xyz1, xyz2, dist,
+                               ip);
+            return check_launch("three_nn_split_kernel");
+        }
+        hipLaunchKernelGGL((three_nn_kernel<IT>), dim3((N + 255) / 256, B), dim3(256), 0, st, B, N, S, xyz1, xyz2, dist, ip);
+        return check_launch("three_nn_kernel");
+    });
 }

@@ -14,6 +14,7 @@
 //     need batch statistics and stay torch modules.  This is the reference's `aggregation` operator
 //     (aggregation_cuda_kernel.cu:5-39) with the softmax fused in front and without its per-element atomics on
 //     grad_weight.
+#include "dispatch.h"
 #include "tgn_common.h"
 
 namespace tgn {
@@ -318,18 +319,14 @@ TGN_API int tgn_pt_attention_forward(int n, int nsample, int c, int g, const flo
     long long blocks = ((long long)n + 3) / 4;
     if (blocks > 256 * 16) blocks = 256 * 16;
     hipStream_t st = (hipStream_t)stream;
-#define TGN_PT(GG) hipLaunchKernelGGL((pt_attention_fwd_kernel<GG>), dim3((unsigned)blocks), dim3(256), 0, st, n, nsample, c, p, xq, xk, xv, idx, P, out)
-    switch (g) {
-        case 4: TGN_PT(4); break;
-        case 8: TGN_PT(8); break;
-        case 16: TGN_PT(16); break;
-        case 32: TGN_PT(32); break;
-        case 64: TGN_PT(64); break;
-        default:
-            set_error("tgn_pt_attention_forward: weight channels must be 4, 8, 16, 32 or 64 (got %d)", g);
-            return TGN_ERR_UNSUPPORTED;
+    const bool found = dispatch_int<4, 8, 16, 32, 64>(g, [&](auto gg) {
+        hipLaunchKernelGGL((pt_attention_fwd_kernel<decltype(gg)::value>), dim3((unsigned)blocks), dim3(256), 0, st, n, nsample, c, p, xq,
+                           xk, xv, idx, P, out);
+    });
+    if (!found) {
+        set_error("tgn_pt_attention_forward: weight channels must be 4, 8, 16, 32 or 64 (got %d)", g);
+        return TGN_ERR_UNSUPPORTED;
     }
-#undef TGN_PT
     return check_launch("pt_attention_fwd_kernel");
 }
 

@@ -14,6 +14,7 @@
 //     gather-add-relu of tgn_sa_gather_act when more layers follow.
 // fp32 MFMA (v_mfma_f32_32x32x2_f32) is an exact fp32 fma chain (MI355X_MICROARCH.md): results differ from the
 // reference's BLAS only by summation order (tests: 1e-5 relative to the row magnitude).
+#include "dispatch.h"
 #include "tgn_common.h"
 
 namespace tgn {
@@ -325,13 +326,11 @@ TGN_API int tgn_sa_gather_max(int B, int N, int S, int K, int C1, const float *A
     }
     long long blocks = ((items + 3) / 4 + 7) / 8 * 8;
     if (blocks > 256 * 8) blocks = 256 * 8;
-    if (idx_is_int64)
-        hipLaunchKernelGGL((sa_gather_max_kernel<long long>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, B, N, S,
-                           K, C1, A, new_xyz, Wxs, b2, (const long long *)idx, relu, out, err);
-    else
-        hipLaunchKernelGGL((sa_gather_max_kernel<int>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, B, N, S, K, C1,
-                           A, new_xyz, Wxs, b2, (const int *)idx, relu, out, err);
-    return check_launch("sa_gather_max_kernel");
+    return dispatch_idx(idx, idx_is_int64, [&](auto *ip) {
+        hipLaunchKernelGGL((sa_gather_max_kernel<idx_elem_t<decltype(ip)>>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, B,
+                           N, S, K, C1, A, new_xyz, Wxs, b2, ip, relu, out, err);
+        return check_launch("sa_gather_max_kernel");
+    });
 }
 
 // 1 if tgn_sa_direct_max takes this shape
@@ -355,36 +354,21 @@ TGN_API int tgn_sa_direct_max(int B, int N, int S, int K, int D, int C1, const f
     int *err = index_error_word((hipStream_t)stream);
     long long blocks = ((queries + 3) / 4 + 7) / 8 * 8;
     if (blocks > 256 * 8) blocks = 256 * 8;
-    const int ks = (3 + D + 1) / 2, nt = C1 / 32;
+    // the k-steps of 3 + D channels, rounded up to the instantiated 2 / 5 / 8 (the extra steps multiply zero rows of Wd)
+    const int ks = 3 + D <= 4 ? 2 : 3 + D <= 10 ? 5 : 8;
+    const int nt = C1 / 32;
     const float *pts = points ? points : xyz;
-    hipStream_t st = (hipStream_t)stream;
-#define TGN_SA_DIRECT(IT, KS, NT)                                                                                         \
-    hipLaunchKernelGGL((sa_direct_max_kernel<IT, KS, NT>), dim3((unsigned)blocks), dim3(256), 0, st, queries, N, S, K, D, C1, \
-                       xyz, new_xyz, pts, Wd, b2, (const IT *)idx, relu, out, err)
-#define TGN_SA_DIRECT_NT(IT, KS)                                                            \
-    switch (nt) {                                                                           \
-        case 1: TGN_SA_DIRECT(IT, KS, 1); break;                                            \
-        case 2: TGN_SA_DIRECT(IT, KS, 2); break;                                            \
-        case 3: TGN_SA_DIRECT(IT, KS, 3); break;                                            \
-        case 4: TGN_SA_DIRECT(IT, KS, 4); break;                                            \
-        case 5: TGN_SA_DIRECT(IT, KS, 5); break;                                            \
-        case 6: TGN_SA_DIRECT(IT, KS, 6); break;                                            \
-        case 7: TGN_SA_DIRECT(IT, KS, 7); break;                                            \
-        default: TGN_SA_DIRECT(IT, KS, 8); break;                                           \
-    }
-#define TGN_SA_DIRECT_KS(IT)                                                                \
-    if (ks <= 2) { TGN_SA_DIRECT_NT(IT, 2) }                                                \
-    else if (ks <= 5) { TGN_SA_DIRECT_NT(IT, 5) }                                           \
-    else { TGN_SA_DIRECT_NT(IT, 8) }
-    if (idx_is_int64) {
-        TGN_SA_DIRECT_KS(long long)
-    } else {
-        TGN_SA_DIRECT_KS(int)
-    }
-#undef TGN_SA_DIRECT_KS
-#undef TGN_SA_DIRECT_NT
-#undef TGN_SA_DIRECT
-    return check_launch("sa_direct_max_kernel");
+    return dispatch_idx(idx, idx_is_int64, [&](auto *ip) {
+        bool found = false;
+        dispatch_int<2, 5, 8>(ks, [&](auto ks_c) {
+            found = dispatch_int<1, 2, 3, 4, 5, 6, 7, 8>(nt, [&](auto nt_c) {
+                hipLaunchKernelGGL((sa_direct_max_kernel<idx_elem_t<decltype(ip)>, decltype(ks_c)::value, decltype(nt_c)::value>),
+                                   dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, queries, N, S, K, D, C1, xyz, new_xyz, pts,
+                                   Wd, b2, ip, relu, out, err);
+            });
+        });
+        return found ? check_launch("sa_direct_max_kernel") : dispatch_miss("tgn_sa_direct_max", "C1 / 32", nt);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -465,11 +449,9 @@ TGN_API int tgn_sa_gather_act(int B, int N, int S, int K, int C1, const float *A
     int *err = index_error_word((hipStream_t)stream);
     long long blocks = ((queries + 3) / 4 + 7) / 8 * 8;
     if (blocks > 256 * 32) blocks = 256 * 32;
-    if (idx_is_int64)
-        hipLaunchKernelGGL((sa_gather_act_kernel<long long>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, queries,
-                           N, S, K, C1, A, new_xyz, Wxs, b2, (const long long *)idx, relu, out, err);
-    else
-        hipLaunchKernelGGL((sa_gather_act_kernel<int>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, queries, N, S,
-                           K, C1, A, new_xyz, Wxs, b2, (const int *)idx, relu, out, err);
-    return check_launch("sa_gather_act_kernel");
+    return dispatch_idx(idx, idx_is_int64, [&](auto *ip) {
+        hipLaunchKernelGGL((sa_gather_act_kernel<idx_elem_t<decltype(ip)>>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                           queries, N, S, K, C1, A, new_xyz, Wxs, b2, ip, relu, out, err);
+        return check_launch("sa_gather_act_kernel");
+    });
 }

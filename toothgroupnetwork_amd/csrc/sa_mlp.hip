@@ -20,6 +20,7 @@
 //   * the max over a query's neighbours is taken on the accumulators (bias and ReLU commute with it) and (B,S,C2) is all
 //     that is written.
 // Rows past K (K < 32 or 32 < K < 64) repeat neighbour 0, which a max does not see.
+#include "dispatch.h"
 #include "tgn_common.h"
 #include <type_traits>
 
@@ -791,70 +792,42 @@ static int sa_mlp2_launch(const char *who, int B, int N, int S, int K, int D, in
     hipStream_t st = (hipStream_t)stream;
     int *err = idx ? index_error_word(st) : nullptr;
     if (direct && !points) points = xyz;   // D == 0: never read
-#define TGN_MLP2(IT, DIR)                                                                                                 \
-    if (lds > 48 * 1024)                                                                                                  \
-        (void)hipFuncSetAttribute((const void *)sa_mlp2_max_kernel<IT, DIR>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  80 * 1024);                                                                             \
-    hipLaunchKernelGGL((sa_mlp2_max_kernel<IT, DIR>), dim3((unsigned)blocks), dim3(256), lds, st, Q, N, S, K, D, C1p, C2, out_stride, \
-                       A1, xyz, points, new_xyz, W1, b1, (const IT *)idx, W2f, b2, out, err)
-#define TGN_MLP2S(IT, DIR, WM_, TN_, LDS_, BLOCKS_)                                                                                \
-    if ((LDS_) > 48 * 1024)                                                                                                        \
-        (void)hipFuncSetAttribute((const void *)sa_mlp2_max_split_kernel<IT, DIR, WM_, TN_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  (int)(LDS_));                                                                                    \
-    hipLaunchKernelGGL((sa_mlp2_max_split_kernel<IT, DIR, WM_, TN_>), dim3((unsigned)(BLOCKS_)), dim3(WM_ * 128), (LDS_), st, Q, N, S, K, D, \
-                       C1p, C2, out_stride, A1, xyz, points, new_xyz, W1, b1, (const IT *)idx, (const unsigned char *)W2f, b2, out, err)
-    if (split) {
-        if (ntiles * (long long)(C1p / kMlpKT) * kSplitTile > 0x7FFFFFFFLL || ((uintptr_t)W2f & 15)) {
-            set_error("%s: split weight image too large or misaligned", who);
-            return TGN_ERR_UNSUPPORTED;
-        }
-        // 256 x 256 tiles (512 threads, one workgroup per CU) where the level is wide and tall enough to fill the chip with them:
-        // half the weight and gather traffic per flop of the 128 x 128 form, which the memory system bounds ("sa_tile": 0 picks,
-        // 128 / 256 force)
-        const int qpt_big = K > 32 ? 4 : 8;
-        const long long mt_big = (Q + qpt_big - 1) / qpt_big, nt_big = (C2 + 255) / 256;
-        const size_t lds_big = (size_t)4 * 2 * kSplitTile + (size_t)qpt_big * C1p * sizeof(float);
-        const int forced = tuning(kTuneSaTile);
-        const bool big = !direct && lds_big <= 150 * 1024 && forced != 128 &&
-                         (forced == 256 || (C2 % 256 == 0 && mt_big * nt_big >= 256));
-        if (big) {
-            const long long blocks_big = (mt_big * nt_big + 7) / 8 * 8;
-            if (idx_is_int64) {
-                TGN_MLP2S(long long, false, 4, 4, lds_big, blocks_big);
-            } else {
-                TGN_MLP2S(int, false, 4, 4, lds_big, blocks_big);
-            }
-        } else if (idx_is_int64) {
-            if (direct) {
-                TGN_MLP2S(long long, true, 2, 2, lds, blocks);
-            } else {
-                TGN_MLP2S(long long, false, 2, 2, lds, blocks);
-            }
-        } else {
-            if (direct) {
-                TGN_MLP2S(int, true, 2, 2, lds, blocks);
-            } else {
-                TGN_MLP2S(int, false, 2, 2, lds, blocks);
-            }
-        }
-        return check_launch("sa_mlp2_max_split_kernel");
+    if (split && (ntiles * (long long)(C1p / kMlpKT) * kSplitTile > 0x7FFFFFFFLL || ((uintptr_t)W2f & 15))) {
+        set_error("%s: split weight image too large or misaligned", who);
+        return TGN_ERR_UNSUPPORTED;
     }
-    if (idx_is_int64) {
-        if (direct) {
-            TGN_MLP2(long long, true);
-        } else {
-            TGN_MLP2(long long, false);
-        }
-    } else {
-        if (direct) {
-            TGN_MLP2(int, true);
-        } else {
-            TGN_MLP2(int, false);
-        }
-    }
-#undef TGN_MLP2
-#undef TGN_MLP2S
-    return check_launch("sa_mlp2_max_kernel");
+    // 256 x 256 tiles (512 threads, one workgroup per CU) where the level is wide and tall enough to fill the chip with them:
+    // half the weight and gather traffic per flop of the 128 x 128 form, which the memory system bounds ("sa_tile": 0 picks,
+    // 128 / 256 force)
+    const int qpt_big = K > 32 ? 4 : 8;
+    const long long mt_big = (Q + qpt_big - 1) / qpt_big, nt_big = (C2 + 255) / 256;
+    const size_t lds_big = (size_t)4 * 2 * kSplitTile + (size_t)qpt_big * C1p * sizeof(float);
+    const int forced = tuning(kTuneSaTile);
+    const bool big = split && !direct && lds_big <= 150 * 1024 && forced != 128 &&
+                     (forced == 256 || (C2 % 256 == 0 && mt_big * nt_big >= 256));
+    return dispatch_idx(idx, idx_is_int64, [&](auto *ip) {
+        using IT = idx_elem_t<decltype(ip)>;
+        // WM x TN waves of 64 x 64: the 128 x 128 form for both first layers, the 256 x 256 form for the gathered one only
+        auto launch_split = [&](auto dir, auto wm, auto tn, size_t bytes, long long nblocks) {
+            constexpr int WM = decltype(wm)::value;
+            auto kfn = sa_mlp2_max_split_kernel<IT, decltype(dir)::value, WM, decltype(tn)::value>;
+            if (int rc = raise_dynamic_lds(kfn, "sa_mlp2_max_split_kernel", bytes, bytes)) return rc;
+            hipLaunchKernelGGL(kfn, dim3((unsigned)nblocks), dim3(WM * 128), bytes, st, Q, N, S, K, D, C1p, C2, out_stride, A1, xyz, points,
+                               new_xyz, W1, b1, ip, (const unsigned char *)W2f, b2, out, err);
+            return check_launch("sa_mlp2_max_split_kernel");
+        };
+        using I2 = std::integral_constant<int, 2>;
+        using I4 = std::integral_constant<int, 4>;
+        if (big) return launch_split(std::false_type{}, I4{}, I4{}, lds_big, (mt_big * nt_big + 7) / 8 * 8);
+        return dispatch_bool(direct, [&](auto dir) {
+            if (split) return launch_split(dir, I2{}, I2{}, lds, blocks);
+            auto kfn = sa_mlp2_max_kernel<IT, decltype(dir)::value>;
+            if (int rc = raise_dynamic_lds(kfn, "sa_mlp2_max_kernel", lds, 80 * 1024)) return rc;   // the limit of every width
+            hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(256), lds, st, Q, N, S, K, D, C1p, C2, out_stride, A1, xyz, points,
+                               new_xyz, W1, b1, ip, W2f, b2, out, err);
+            return check_launch("sa_mlp2_max_kernel");
+        });
+    });
 }
 
 // Bytes of the split (bf16 x 3) image of a second-layer weight matrix, and the one-off conversion (device to device, on `stream`).
