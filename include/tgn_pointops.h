@@ -614,6 +614,28 @@ int tgn_obj_read(const char *path, double *vertices, long long *faces, long long
  */
 int tgn_vertex_normals(const double *vertices, long long nv, const long long *triangles, long long nf, double *normals);
 /*
+ * One pass of open3d's TriangleMesh::SubdivideMidpoint (what the inference pipelines do to a mesh below 24 000 vertices,
+ * inference_pipeline_sem.py:25-26), on the GPU: unlike its neighbours in this section it takes DEVICE pointers and a stream.
+ * vertices (nv,3) double, normals (nv,3) double or NULL, triangles (nf,3) int64 ZERO-based.  The triangles are walked in order and,
+ * per triangle (a, b, c), the edges (a,b), (b,c), (c,a); an edge is the unordered pair {min, max}.  The first time an edge is met it
+ * gets vertex nv + (number of distinct edges met before it) = 0.5 * (V[p] + V[q]), with normal 0.5 * (N[p] + N[q]) (not renormalised)
+ * when normals are given; triangle t becomes (a, ab, ca), (ab, b, bc), (bc, c, ca), (ab, bc, ca) at rows 4t .. 4t+3.  Old vertices keep
+ * their indices and bits; a repeated index (a == b) is no special case (the edge {a, a} gets a copy of V[a]); unreferenced vertices
+ * are kept.  The contract is restated from open3d's source: parity unpinned (no open3d here).
+ * out_vertices / out_normals: room for the upper bound, (nv + 3 nf, 3) double; rows [0, nv + *n_new) are written.  out_normals may
+ * be NULL when normals is.  out_triangles (4 nf, 3) int64.  n_new: one int of device memory that receives the number of new vertices
+ * (distinct edges), or -(error bits) when the pass failed: bit 1 = a triangle index outside [0, nv), bit 2 = a probe sequence of the
+ * edge table ran out (every loop on the device is bounded).  After a failure the outputs are unspecified.  The result does not depend
+ * on how the threads are scheduled.  workspace: at least tgn_subdivide_midpoint_workspace_bytes(nf) bytes of device memory
+ * (12 bytes per slot of a table of the next power of two >= 6 nf, + 24 nf); that function returns 0 for an unsupported nf.
+ * nv + 3 nf >= 2^31 is TGN_ERR_UNSUPPORTED; negative counts and NULL pointers are TGN_ERR_INVALID_ARGUMENT (the vertex arrays may be NULL
+ * when nv = 0, the triangle arrays when nf = 0: then nothing is read or written through them); both before any HIP call.
+ */
+size_t tgn_subdivide_midpoint_workspace_bytes(long long nf);
+int tgn_subdivide_midpoint(long long nv, long long nf, const double *vertices, const double *normals, const long long *triangles,
+                           double *out_vertices, double *out_normals, long long *out_triangles, int *n_new, void *workspace,
+                           size_t workspace_bytes, tgn_stream_t stream);
+/*
  * One scan of the preprocess loop in one call that never holds the interpreter lock (preprocess_data.py:37-52): reads the
  * ground-truth json ({"jaw": "upper"|"lower", "labels": [FDI numbers]}), remaps the labels to 0..16 (:39-44), reads the OBJ
  * with tgn_obj_read's semantics, computes the vertex normals, centres the vertices and maps [y_min, y_max] to [-1, 1]

@@ -136,6 +136,8 @@ SIGNATURES = {
     "tgn_obj_count": (c_int, [ctypes.c_char_p, _P, _P]),
     "tgn_obj_read": (c_int, [ctypes.c_char_p, _P, _P, ctypes.c_longlong, ctypes.c_longlong, _P, _P]),
     "tgn_vertex_normals": (c_int, [_P, ctypes.c_longlong, _P, ctypes.c_longlong, _P]),
+    "tgn_subdivide_midpoint_workspace_bytes": (c_size_t, [ctypes.c_longlong]),     # (device pointers + stream, unlike its neighbours)
+    "tgn_subdivide_midpoint": (c_int, [ctypes.c_longlong, ctypes.c_longlong, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "tgn_scan_open": (c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_double, ctypes.c_double, _P, _P, ctypes.c_char_p, c_int]),
     "tgn_scan_take": (c_int, [_P, _P, _P]),
     "tgn_scan_pool_trim": (c_int, []),

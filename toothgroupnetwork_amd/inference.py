@@ -11,7 +11,12 @@ single scan is bound by the host enqueuing its ~350 launches; the saving is the 
 
 Pinned against the reference's own class executed on CPU (tests/golden/make_golden_r3_pipeline.py: loader, FPS and .cuda() served,
 everything else the reference's code): the same label on every vertex.
-Not covered: meshes with fewer than 24 000 vertices, which the reference subdivides with open3d (:25-26).
+Meshes with fewer than 24 000 vertices are subdivided once at their edge midpoints first, as the reference does with open3d's
+subdivide_midpoint(number_of_iterations=1) (:25-26): on the GPU (preprocess.subdivide_midpoint, csrc/subdivide.hip), inside the "sample"
+stage, and the subdivided vertices with their interpolated normals are what is sampled (`points_to_sample`).  One iteration is all the
+pipelines use.  Parity with open3d is unpinned: the vertex order is restated from open3d's source, and neither open3d nor trimesh is
+available where the fixtures are made.  A mesh that still has no more than 24 000 points after the pass is NotImplementedError: the
+reference fails on it too (gen_utils.py:136-137).
 
 TSegNetInferencePipeLine is the same for tsegnet (inference_pipelines/inference_pipeline_tsegnet.py): the centroid module, the join and
 the painting on the GPU (tsegnet.py), pinned against the reference's class in the same way (tests/golden/make_golden_r11_tsegnet.py)."""
@@ -32,6 +37,38 @@ def normalise_for_inference(vertices, scaler=1.8, shifter=0.8):
     lo, hi = np.min(v[:, 1]), np.max(v[:, 1])
     v[:, :3] = ((v[:, :3] - lo) / (hi - lo)) * scaler - shifter
     return v
+
+
+_TOO_SMALL = ("a mesh that still has no more than 24 000 points after one midpoint subdivision cannot be sampled to 24 000: the reference "
+              "fails on such a mesh too (gen_utils.py:136-137)")
+
+
+def needs_subdivision(nv, nf):
+    """True for a mesh below 24 000 vertices, which the reference's three pipelines subdivide once (inference_pipeline_sem.py:25-28,
+    inference_pipeline_tsegnet.py:26-27, inference_pipeline_tgn.py:35-37).  A pass adds at most 3 nf vertices: where nv + 3 nf cannot
+    exceed 24 000 the reference fails in gen_utils.fps afterwards, and this raises NotImplementedError before any launch."""
+    if nv >= N_POINTS:
+        return False
+    if nv + 3 * nf <= N_POINTS:
+        raise NotImplementedError(_TOO_SMALL)
+    return True
+
+
+def subdivided_rows(org_feats, triangles):
+    """(nv, 6) normalised vertices + normals of a small mesh -> the (nv + edges, 6) rows of the mesh subdivided once on the GPU: old
+    rows first, then every edge midpoint with the mean of its end points' normals (preprocess.subdivide_midpoint)."""
+    sub = preprocess.subdivide_midpoint({"vertices": org_feats[:, :3], "triangles": triangles, "vertex_normals": org_feats[:, 3:6]}, 1)
+    if sub["vertices"].shape[0] <= N_POINTS:
+        raise NotImplementedError(_TOO_SMALL)
+    return np.concatenate([sub["vertices"], sub["vertex_normals"]], axis=1)
+
+
+def points_to_sample(org_feats, triangles):
+    """The rows the pipelines sample 24 000 points from: the mesh's own (org_feats, which stays what the labels are transferred back
+    onto) or, below 24 000 vertices, the subdivided mesh's."""
+    if needs_subdivision(org_feats.shape[0], int(np.asarray(triangles).shape[0])):
+        return subdivided_rows(org_feats, triangles)
+    return org_feats
 
 
 def fdi_from_classes(cls):
@@ -59,10 +96,9 @@ class InferencePipeLine:
         t.append(time.perf_counter())
         vertices = normalise_for_inference(mesh["vertices"], self.scaler, self.shifter)
         org_feats = np.concatenate([vertices, mesh["vertex_normals"]], axis=1)
-        if org_feats.shape[0] < N_POINTS:
-            raise NotImplementedError("meshes below 24 000 vertices are subdivided with open3d in the reference (inference_pipeline_sem.py:25-26)")
-        idx = resample.fps(org_feats[:, :3], N_POINTS, prefix=True)               # gen_utils.resample_pcd(..., "fps")
-        sampled_feats = org_feats[idx[:N_POINTS]]
+        dense = points_to_sample(org_feats, mesh["triangles"])
+        idx = resample.fps(dense[:, :3], N_POINTS, prefix=True)                   # gen_utils.resample_pcd(..., "fps")
+        sampled_feats = dense[idx[:N_POINTS]]
         t.append(time.perf_counter())
         with torch.no_grad():
             inp = torch.from_numpy(np.ascontiguousarray(sampled_feats.astype("float32"))[None]).cuda().permute(0, 2, 1)
@@ -84,7 +120,7 @@ class TSegNetInferencePipeLine:
     sampled points, then tsegnet.py's join WITHOUT crop subsampling (every cluster centre is cropped, :37-56; the fused crop kernel
     writes the distance feature, so `get_ddf` is not called), the segmentation module on all crops, the painting loop (:60-66) as
     tsegnet.paint_labels, the FDI relabelling (:69-70) and the nearest-sample transfer onto every vertex (:72-74).
-    `times` holds the stage times of the last call.  Meshes below 24 000 vertices: NotImplementedError, as InferencePipeLine."""
+    `times` holds the stage times of the last call.  Meshes below 24 000 vertices: subdivided once, as in InferencePipeLine."""
 
     def __init__(self, model):
         self.model = model
@@ -98,10 +134,9 @@ class TSegNetInferencePipeLine:
         t.append(time.perf_counter())
         vertices = normalise_for_inference(mesh["vertices"], self.scaler, self.shifter)
         org_feats = np.concatenate([vertices, mesh["vertex_normals"]], axis=1)
-        if org_feats.shape[0] < N_POINTS:
-            raise NotImplementedError("meshes below 24 000 vertices are subdivided with open3d in the reference (inference_pipeline_tsegnet.py:26-27)")
-        idx = resample.fps(org_feats[:, :3], N_POINTS)                             # gen_utils.resample_pcd(..., "fps")
-        sampled_feats = org_feats[idx[:N_POINTS]]
+        dense = points_to_sample(org_feats, mesh["triangles"])
+        idx = resample.fps(dense[:, :3], N_POINTS)                                 # gen_utils.resample_pcd(..., "fps")
+        sampled_feats = dense[idx[:N_POINTS]]
         t.append(time.perf_counter())
         with torch.no_grad():
             inp = torch.from_numpy(np.ascontiguousarray(sampled_feats.astype("float32"))[None]).cuda().permute(0, 2, 1).contiguous()
@@ -131,6 +166,8 @@ def infer_scans(paths, model, batch=8, workers=None):
     interpreter lock), a sampler thread that packs 4 x `batch` scans into ONE FPS launch on its own stream, and the calling thread, which
     runs the network on (batch, 6, 24000) and hands the label transfer to helper threads.  Same stage functions, same results per scan
     as InferencePipeLine (tests/test_gpu_whole_nets.py); returns the list of {"sem", "ins"} in the order of `paths`.
+    A mesh below 24 000 vertices is subdivided once in the sampler stage, on that thread's stream (the loaders only decide that it
+    needs it), and joins the same FPS launch (tests/test_gpu_subdivide.py).
     `model`: as for InferencePipeLine, batch-capable (nets.PointTransformerSeg is)."""
     import os
     import threading
@@ -156,13 +193,16 @@ def infer_scans(paths, model, batch=8, workers=None):
     def load(path):
         feats, mesh = preprocess.read_txt_obj_ls(path, ret_mesh=True)
         org = np.concatenate([normalise_for_inference(mesh["vertices"]), mesh["vertex_normals"]], axis=1)
-        if org.shape[0] < N_POINTS:
-            raise NotImplementedError("meshes below 24 000 vertices are subdivided with open3d in the reference (inference_pipeline_sem.py:25-26)")
-        return org, np.ascontiguousarray(org[:, :3], dtype=np.float32)
+        if needs_subdivision(org.shape[0], mesh["triangles"].shape[0]):           # (host arithmetic only: the pass itself is the sampler's)
+            return org, None, mesh["triangles"]
+        return org, np.ascontiguousarray(org[:, :3], dtype=np.float32), None
 
     def sample(loaded):
-        idx = on_own_stream(resample.fps_batch, [x32 for _, x32 in loaded], N_POINTS)
-        return [org[ix[:N_POINTS]] for (org, _), ix in zip(loaded, idx)]
+        # (sampler thread) small meshes are subdivided here, on this thread's stream, then one FPS launch over the whole chunk
+        dense = [org if tri is None else on_own_stream(subdivided_rows, org, tri) for org, _, tri in loaded]
+        xyz = [x32 if tri is None else np.ascontiguousarray(d[:, :3], dtype=np.float32) for (_, x32, tri), d in zip(loaded, dense)]
+        idx = on_own_stream(resample.fps_batch, xyz, N_POINTS)
+        return [d[ix[:N_POINTS]] for d, ix in zip(dense, idx)]
 
     def finish(sampled, cls, org):
         return on_own_stream(preprocess.transfer_labels, sampled[:, :3], fdi_from_classes(cls), org[:, :3]).reshape(-1)
@@ -182,7 +222,7 @@ def infer_scans(paths, model, batch=8, workers=None):
                     inp = torch.from_numpy(np.stack([s_.astype("float32") for s_ in part])).cuda().permute(0, 2, 1).contiguous()
                     out = model([inp])
                     cls_pred = (out["cls_pred"] if isinstance(out, dict) else out[0]).argmax(dim=1).cpu().numpy()  # (B, N)
-                for (org, _), s_, c in zip(loaded[b0:b0 + step], part, cls_pred):
+                for (org, _, _), s_, c in zip(loaded[b0:b0 + step], part, cls_pred):
                     pending.append(finishers.submit(finish, s_, c, org))
         for f in pending:
             r = f.result()

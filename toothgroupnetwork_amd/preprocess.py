@@ -56,6 +56,81 @@ def vertex_normals(vertices, triangles):
     return out
 
 
+def _check_mesh_for_subdivision(mesh, number_of_iterations):
+    """The host-side checks of subdivide_midpoint, before anything touches the device -> (vertices, normals or None, triangles)."""
+    if int(number_of_iterations) < 1:
+        raise ValueError(f"number_of_iterations must be at least 1 (got {number_of_iterations})")
+    v = np.ascontiguousarray(mesh["vertices"], dtype=np.float64).reshape(-1, 3)
+    t = np.ascontiguousarray(mesh["triangles"], dtype=np.int64).reshape(-1, 3)
+    n = mesh.get("vertex_normals")
+    if n is not None:
+        n = np.ascontiguousarray(n, dtype=np.float64).reshape(-1, 3)
+        if n.shape != v.shape:
+            raise ValueError(f"vertex_normals has shape {n.shape}, the vertices {v.shape}")
+    bad = np.flatnonzero(((t < 0) | (t >= v.shape[0])).any(axis=1))
+    if bad.size:
+        raise ValueError(f"triangle {int(bad[0])} = {t[bad[0]].tolist()} has an index outside [0, {v.shape[0]})")
+    return v, n, t
+
+
+def subdivide_midpoint_device(vertices, normals, triangles, number_of_iterations=1):
+    """subdivide_midpoint on tensors that already live on the GPU (float64 (nv,3), float64 (nv,3) or None, int64 (nf,3), contiguous)
+    -> the same three for the subdivided mesh, on the current stream.  One host synchronisation per iteration: the number of new
+    vertices.  The triangle indices are checked on the device; a bad one raises ValueError after the pass."""
+    import torch
+    L = _lib.lib()
+    _lib.require_cuda(vertices, normals, triangles)
+    v, n, t = vertices.contiguous(), (None if normals is None else normals.contiguous()), triangles.contiguous()
+    if v.dtype != torch.float64 or t.dtype != torch.int64 or (n is not None and n.dtype != torch.float64):
+        raise TypeError("subdivide_midpoint_device takes float64 vertices and normals and int64 triangles")
+    for _ in range(int(number_of_iterations)):
+        nv, nf = v.shape[0], t.shape[0]
+        if nf == 0:
+            break
+        need = L.tgn_subdivide_midpoint_workspace_bytes(nf)
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=v.device)
+        out_v = torch.empty((nv + 3 * nf, 3), dtype=torch.float64, device=v.device)
+        out_n = torch.empty_like(out_v) if n is not None else None
+        out_t = torch.empty((4 * nf, 3), dtype=torch.int64, device=v.device)
+        count = torch.empty(1, dtype=torch.int32, device=v.device)
+        _lib.check(L.tgn_subdivide_midpoint(nv, nf, _lib.ptr(v), _lib.ptr(n), _lib.ptr(t), _lib.ptr(out_v), _lib.ptr(out_n), _lib.ptr(out_t),
+                                            _lib.ptr(count), _lib.ptr(ws), need, _lib.stream()), "tgn_subdivide_midpoint")
+        new = int(count.item())                                  # the one synchronisation of the pass
+        if new < 0:
+            if -new & 1:
+                raise ValueError(f"subdivide_midpoint: a triangle index outside [0, {nv})")
+            raise RuntimeError(f"tgn_subdivide_midpoint: the edge table overflowed (error bits {-new}); this is a bug in its sizing")
+        v, t = out_v[:nv + new], out_t
+        n = out_n[:nv + new] if n is not None else None
+    return v, n, t
+
+
+def subdivide_midpoint(mesh, number_of_iterations=1):
+    """open3d's TriangleMesh.subdivide_midpoint on the dict read_txt_obj_ls(..., ret_mesh=True) returns ({"vertices" (nv,3) float64,
+    "triangles" (nf,3) zero-based, optionally "vertex_normals"}) -> a dict with the same keys: every edge gets a vertex at its
+    midpoint (with the mean of the end points' normals, not renormalised), numbered from nv in the order the edges are first met
+    when the triangles are walked in order and each triangle's edges as (a,b), (b,c), (c,a); triangle t becomes the four triangles
+    (a, ab, ca), (ab, b, bc), (bc, c, ca), (ab, bc, ca) at rows 4t .. 4t+3.  The contract is include/tgn_pointops.h's
+    tgn_subdivide_midpoint, restated from open3d's source; parity with open3d itself is unpinned (it is not installed where the
+    fixtures are made).  Runs on the GPU (csrc/subdivide.hip), one host synchronisation per iteration.  Raises ValueError for a triangle
+    index outside [0, nv) (naming the first such row) and for number_of_iterations < 1, before anything touches the device."""
+    v, n, t = _check_mesh_for_subdivision(mesh, number_of_iterations)
+    if t.shape[0] == 0:
+        out = {"vertices": v.copy(), "triangles": t.copy()}
+        if n is not None:
+            out["vertex_normals"] = n.copy()
+        return out
+    import torch
+    dev = torch.device("cuda")
+    dv, dt = torch.from_numpy(v).to(dev), torch.from_numpy(t).to(dev)
+    dn = torch.from_numpy(n).to(dev) if n is not None else None
+    dv, dn, dt = subdivide_midpoint_device(dv, dn, dt, number_of_iterations)
+    out = {"vertices": dv.cpu().numpy(), "triangles": dt.cpu().numpy()}
+    if dn is not None:
+        out["vertex_normals"] = dn.cpu().numpy()
+    return out
+
+
 def read_txt_obj_ls(path, ret_mesh=False, use_tri_mesh=False):
     """gen_utils.read_txt_obj_ls (gen_utils.py:201-240): [ (n,6) float64 = vertices + vertex normals ]; with ret_mesh also
     a dict {"vertices", "triangles" (zero-based), "vertex_normals"} standing in for the open3d mesh object."""
