@@ -597,6 +597,43 @@ int tgn_edgeconv2_max(int B, int N, int K, const float *P, const float *Q, const
 int tgn_edgeconv1_max(int B, int N, int K, const float *P, const float *Q, const long long *idx, float *out, long long ostride, int coff,
                       tgn_stream_t stream);
 
+/*
+ * Scoring a predicted segmentation against its ground truth: the reference's cal_metric (eval_visualize_results.py:20-57), which runs
+ * about ten full-length numpy passes per predicted instance on the host.  Here the vertices are read once, into two integer tables per
+ * scan, and the scores are computed from the tables.  Labels are int64; 2 <= nlab <= 64 (FDI numbers reach 48), anything else is
+ * TGN_ERR_UNSUPPORTED with a message before any HIP call.
+ *   tgn_seg_confusion_chunk: the number of vertices one workgroup of tgn_seg_confusion takes per pass (tests size their edge cases from it).
+ *   tgn_seg_confusion: b scans packed end to end, n vertices in all, scan i = vertices [offset[i-1], offset[i]) (pointops-style cumulative
+ *     int32 offset (b), device memory, as tgn_dbscan takes it; an empty scan is allowed; a vertex at or beyond offset[b-1] belongs to
+ *     no scan; whatever offset holds, no access leaves the arrays).  ins_gt and ins_sem (b, nlab, nlab) int32: ins_gt[i][p][g] is the
+ *     number of vertices of scan i with ins == p and gt == g, ins_sem[i][p][s] the number with ins == p and sem == s.  The call zeroes
+ *     both tables itself, in stream order.  A vertex whose gt, sem or ins lies outside [0, nlab) is left out of BOTH tables and latches
+ *     bit 1 of the stream's error word (tgn_take_index_error), as tgn_label_centroids does.  sem and ins may be the same array.
+ *     0 <= n < 2^31; b = 0 does nothing, n = 0 zeroes the tables and launches nothing.
+ *   tgn_seg_confusion_logits: the same tables, (B, C, C), for a semantic network's output with the argmax fused in.  logits (B, C, N)
+ *     channel-first float32, 2 <= C <= 64.  A vertex's prediction is torch.argmax over its C logits: equal values go to the lowest
+ *     channel, a NaN counts as larger than every number and the first NaN wins.  The prediction is both sem and ins; gt (B, N) int64 is
+ *     counted as gt + gt_shift (the loaders hand gingiva as -1: callers pass 1).  A vertex whose shifted gt lies outside [0, C) is
+ *     left out and latches bit 1.  B <= 65535.
+ *   tgn_seg_scores: one workgroup per scan.  With A = ins_gt[i], S = ins_sem[i], n = sum(A), insc[p] = sum_g A[p][g] and
+ *     gtc[g] = sum_p A[p][g]: for every p = 1 .. nlab-1 with insc[p] > 0, ascending, g = the first maximum of row A[p] and s = the first
+ *     maximum of row S[p] (np.unique + argmax: ties to the smallest label), TP = A[p][g], FP = insc[p] - TP, FN = gtc[g] - TP,
+ *     TN = n - TP - FP - FN, and in float64, unfused: acc += (TP+TN)/(FP+TP+FN+TN); prec = TP/(TP+FP); rec = TP/(TP+FN);
+ *     f1 += (2*(prec*rec))/(prec+rec); iou += TP/(FP+TP+FN); sem_acc += 1 when s == g, or when is_half and s + 8 == g.  The sums run
+ *     sequentially in ascending p and are divided by the number of instances at the end.  scores (b, 4) float64 = IoU, F1, ACC,
+ *     SEM_ACC, bit-equal to the reference's; instances (b) int32 = the number of labels p >= 1 that occur; iou_per_instance (b, nlab)
+ *     float64 (NaN where p is absent or 0); matched_gt (b, nlab) int32 = g (-1 where p is absent or 0).  A scan without an instance
+ *     gives four NaN and instances = 0.
+ * Deterministic: the only atomics are integer adds.  The calls neither allocate nor synchronise.
+ */
+int tgn_seg_confusion_chunk(void);
+int tgn_seg_confusion(int b, long long n, const int *offset, const long long *gt, const long long *sem, const long long *ins, int nlab,
+                      int *ins_gt, int *ins_sem, tgn_stream_t stream);
+int tgn_seg_confusion_logits(int B, int C, int N, const float *logits, const long long *gt, int gt_shift, int *ins_gt, int *ins_sem,
+                             tgn_stream_t stream);
+int tgn_seg_scores(int b, int nlab, const int *ins_gt, const int *ins_sem, int is_half, double *scores, int *instances,
+                   double *iou_per_instance, int *matched_gt, tgn_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * 4. Mesh input of the preprocess path (HOST pointers, CPU code): gen_utils.read_txt_obj_ls (gen_utils.py:207-233).
  * ---------------------------------------------------------------------------------------- */

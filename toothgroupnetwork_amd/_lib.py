@@ -132,6 +132,10 @@ SIGNATURES = {
     "tgn_feature_knn": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "tgn_edgeconv2_max": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, ctypes.c_longlong, c_int, _P]),
     "tgn_edgeconv1_max": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, ctypes.c_longlong, c_int, _P]),
+    "tgn_seg_confusion_chunk": (c_int, []),
+    "tgn_seg_confusion": (c_int, [c_int, ctypes.c_longlong, _P, _P, _P, _P, c_int, _P, _P, _P]),
+    "tgn_seg_confusion_logits": (c_int, [c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P]),
+    "tgn_seg_scores": (c_int, [c_int, c_int, _P, _P, c_int, _P, _P, _P, _P, _P]),
     # section 4 (host pointers)
     "tgn_obj_count": (c_int, [ctypes.c_char_p, _P, _P]),
     "tgn_obj_read": (c_int, [ctypes.c_char_p, _P, _P, ctypes.c_longlong, ctypes.c_longlong, _P, _P]),
@@ -146,7 +150,7 @@ SIGNATURES = {
 ERR_INVALID_ARGUMENT, ERR_LAUNCH, ERR_UNSUPPORTED = 1, 2, 3     # TGN_ERR_* of include/tgn_pointops.h
 # bits of a stream's error word (tgn_take_index_error; csrc/tgn_common.h: kIndexErrGather, kIndexErrCrop)
 INDEX_ERROR_GATHER = 1      # the gather family: an index outside the gathered dimension
-INDEX_ERROR_CROP = 2        # crop.hip, cluster.hip, tsegnet.hip: a label or a crop index out of range
+INDEX_ERROR_CROP = 2        # crop.hip, cluster.hip, tsegnet.hip, metrics.hip: a label or a crop index out of range
 
 FPS_FMA = 1
 FPS_LOCAL_INDEX = 2

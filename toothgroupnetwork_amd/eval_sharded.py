@@ -12,7 +12,8 @@ The model side is a *step object*: ``step(batch_idx, batch_item) -> {name_val: f
 fixed ``keys`` tuple (the metric schema must be the same on every rank, also on a rank whose shard is empty).
 ``PointNetPPStep`` / ``PointTransformerStep`` restate the "test" branch of models/pointnet_pp_model.py:14-39 and
 models/transformer_model.py:13-36 over this package's network mirrors (nets.py); they need the GPU like every operator
-of the package.  Tests of the control flow hand in their own step object.
+of the package.  ``ScoredClassStep`` and its two subclasses add the segmentation scores of every scan (metrics.py: IoU, F1,
+accuracy, SEM_ACC of the predicted classes) to the same meter.  Tests of the control flow hand in their own step object.
 """
 import glob
 import os
@@ -21,7 +22,7 @@ import time
 import numpy as np
 import torch
 
-from . import launch, sharding
+from . import launch, metrics, sharding
 
 
 class LossMeter:
@@ -100,6 +101,49 @@ class PointTransformerStep(_ClassStep):
 
     def __init__(self, module, device, weight=1):
         super().__init__(module, device, weight=weight, output_index=0)
+
+
+class ScoredClassStep:
+    """_ClassStep plus the scores of the step's prediction (metrics.confusion_from_logits on the class logits and gt_seg_label, then
+    metrics.scores): iou_val, f1_val, acc_val, sem_acc_val as cal_metric gives them for torch.argmax of the logits, with the classes
+    1..C-1 as instances and gingiva -1 counted as class 0.  The scores stay out of total_val, which remains the reference's sum of
+    losses.  A scan with no predicted instance (every vertex gingiva) contributes 0.0 to the four scores and 1.0 to unscored_val, so
+    the averages stay finite and the share of such scans is visible.  ONE host read per step fetches the loss and the scores."""
+    keys = ("tooth_class_loss_1_val", "total_val", "iou_val", "f1_val", "acc_val", "sem_acc_val", "unscored_val")
+
+    def __init__(self, module, device, weight=1, output_index=0, is_half=False):
+        self.module, self.device, self.weight, self.output_index = module.to(device).eval(), device, weight, output_index
+        self.is_half = is_half
+
+    def __call__(self, batch_idx, batch_item):
+        points = batch_item["feat"].to(self.device)
+        seg_label = batch_item["gt_seg_label"].to(self.device)
+        with torch.no_grad():
+            output = self.module([points, seg_label])
+        logits = output[self.output_index]
+        loss = tooth_class_loss(logits, seg_label)
+        sc = metrics.scores(*metrics.confusion_from_logits(logits, seg_label, gt_shift=1), is_half=self.is_half)
+        per_scan = torch.stack([sc.iou, sc.f1, sc.acc, sc.sem_acc])                                # (4, B) float64
+        scored = sc.instances > 0
+        means = torch.where(scored[None], per_scan, torch.zeros_like(per_scan)).mean(1)
+        host = torch.cat([loss.double().reshape(1), means, (~scored).double().mean().reshape(1)]).tolist()    # the one host read
+        out = print_dict({"tooth_class_loss_1": (host[0], self.weight)}, "val")
+        out.update(zip(self.keys[2:], host[1:]))
+        return out
+
+
+class ScoredPointNetPPStep(ScoredClassStep):
+    """PointNetPPStep with scores: class logits are output 6 of the network"""
+
+    def __init__(self, module, device, is_half=False):
+        super().__init__(module, device, weight=1, output_index=6, is_half=is_half)
+
+
+class ScoredPointTransformerStep(ScoredClassStep):
+    """PointTransformerStep with scores: `sem_1` is the first output of the segmentation network"""
+
+    def __init__(self, module, device, weight=1, is_half=False):
+        super().__init__(module, device, weight=weight, output_index=0, is_half=is_half)
 
 
 def reference_state_dict(state):
