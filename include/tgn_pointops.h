@@ -129,6 +129,12 @@ int tgn_furthestsampling_dense(int B, int N, int S, const float *xyz, float *tmp
                                int flags, tgn_stream_t stream);
 int tgn_fps_resident_capacity(void);
 /*
+ * The order in which the bucket-skipping FPS kernel deals a cloud's grid cells out to its buckets: out[x | y << bits |
+ * z << 2 * bits] = position of cell (x, y, z) along the kernel's space-filling curve (a Hilbert curve; bits = 4, 4096
+ * entries).  Host memory, no device needed: for tools/fps_bucket_model.py and the tests of the mapping.
+ */
+int tgn_fps_bucket_order(int bits, unsigned short *out);
+/*
  * Clouds larger than tgn_fps_resident_capacity() (raw scans, preprocess_data.py:55-56) run the bucket-skipping
  * kernel out of a cell-sorted workspace of tgn_fps_workspace_bytes(b, n_max) bytes (20 B per point; 0 when every
  * cloud fits the register-resident kernels; clouds above 262 144 points fall back to streaming through the same

@@ -3,9 +3,9 @@
 
   floor      tools/_bin/fps_floor (tools/fps_floor.hip): the dependent chain of one iteration with the data work removed
   best case  the PRODUCTION kernel on a cloud where every iteration can touch only the bucket that holds the new sample:
-             375 clusters of 64 points, each inside one Z-order cell, the clusters far apart compared with their size
+             375 clusters of 64 points, each inside one cell of the kernel's grid, the clusters far apart compared with their size
              (after the first ~375 samples a new sample's box distance to every other cluster exceeds that cluster's maximum)
-  bench      the PRODUCTION kernel on the benchmark's arch scans (8.6 of 375 buckets touched per iteration on average)
+  bench      the PRODUCTION kernel on the benchmark's arch scans (6.0 of 375 buckets touched per iteration on average)
 Per-iteration time = (launch of S samples - launch of 2 samples) / (S - 2): the set-up is measured and taken out."""
 import json
 import os
@@ -30,7 +30,7 @@ def cluster_cloud(n=24000, seed=0):
     centre = (np.stack([cx, cy, cz], 1) + 0.5) / 16.0 * 2.0 - 1.0           # one cluster per cell of the 16^3 grid over [-1, 1]^3
     pts = centre[:, None, :] + rng.uniform(-1e-3, 1e-3, size=(ncl, 64, 3))
     # one point of each corner cluster sits in the corner itself: the bounding box is [-1, 1]^3 exactly, so the kernel's 16^3
-    # Z-order cells are the cells above and every bucket (64 consecutive sorted positions) is one cluster
+    # cells are the cells above and every bucket (64 consecutive sorted positions, whatever the curve) is one cluster
     pts[0, 0], pts[1, 0] = (-1.0, -1.0, -1.0), (1.0, 1.0, 1.0)
     pts = pts.reshape(-1, 3)
     return pts[rng.permutation(pts.shape[0])].astype(np.float32)

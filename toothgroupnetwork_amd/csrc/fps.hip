@@ -527,6 +527,16 @@ using namespace tgn;
 
 TGN_API int tgn_fps_resident_capacity(void) { return kFpsResidentCapacity; }
 
+TGN_API int tgn_fps_bucket_order(int bits, unsigned short *out) {
+    static constexpr FpsCellOrder<4> order4{};   // the table fps_bucket_kernel reads (fps_common.h); host copy, no device needed
+    if (bits != 4 || !out) {
+        set_error("tgn_fps_bucket_order: the bucket kernel orders 4-bit cells (bits = 4), out must hold 4096 entries");
+        return TGN_ERR_INVALID_ARGUMENT;
+    }
+    for (int c = 0; c < 4096; ++c) out[c] = order4.v[c];
+    return TGN_OK;
+}
+
 TGN_API int tgn_furthestsampling(int b, int n_max, const float *xyz, const int *offset, const int *new_offset,
                                  float *tmp, void *idx, float *new_xyz, int flags, tgn_stream_t stream) {
     if (b > 0 && (!offset || !new_offset)) {

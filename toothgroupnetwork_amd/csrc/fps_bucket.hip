@@ -6,9 +6,12 @@
 // point that is farther from the new sample q than its current minimum distance, and after the first
 // few hundred samples that is almost the whole cloud.  So:
 //
-//   * once per cloud the points are ordered along a Z-order curve (5+5+5-bit cell code | 15-bit index,
-//     one in-LDS bitonic sort by the workgroup) and dealt out so that every (wave, register slot) pair
-//     -- a "bucket" of 64 points, one per lane -- is a compact patch of the scan;
+//   * once per cloud the points are ordered along a Hilbert curve over the 16^3 cells of the cloud's bounding box (one
+//     counting sort in LDS by the 12-bit Hilbert index of a point's cell, fps_common.h) and dealt out so that every
+//     (wave, register slot) pair -- a "bucket" of 64 points, one per lane -- is a compact patch of the scan.  Consecutive
+//     cells of a Hilbert curve are face neighbours, so 64 consecutive points are ONE patch; along a Z-order curve, which
+//     jumps, the box of such a stretch reaches across the jump and a sample touches half as many buckets again
+//     (tools/fps_bucket_model.py: 8.8 - 9.0 -> 6.0 per iteration on 24 000-point scans, 2.26 -> 1.6 on the busiest wave);
 //   * lane s of a wave keeps bucket s's bounding box, its current largest minimum distance `bmax` and the
 //     tie key of the point that attains it;
 //   * per iteration the P metadata lanes of every wave evaluate, with the SAME operation order as the
@@ -23,8 +26,9 @@
 // Results are bit-identical to the plain kernel and to the oracle by construction (skipped updates are
 // provably no-ops); tests/test_gpu_parity.py runs every launch shape against the oracle, including
 // lattices and duplicated vertices (exact ties) and NaN coordinates.
-// Measured (profiles/): 24 000 -> 4096 drops from 2.3 us to 1.25 us per iteration (8.6 of 375 buckets touched on
-// average; what remains is the latency of ~3 bucket updates on the busiest wave plus the block hand-off).
+// Measured (profiles/fps_bucket_order_before_after.txt): 24 000 -> 4096 runs at 0.75 us per iteration (6.0 of 375 buckets
+// touched on average, 3.2 of them with a point that changes; what remains is the latency of the 1.6 bucket updates on the
+// busiest wave plus the block hand-off).
 #include "dispatch.h"
 #include "fps_common.h"
 
@@ -36,29 +40,27 @@
 #ifndef TGN_REFRESH_SKIP
 #define TGN_REFRESH_SKIP 1
 #endif
-// Which wave holds Z-order bucket b = 8*s + i in its register slot s.  Plain round robin (i) sends buckets b, b+8, b+16,
-// b+64 ... to the SAME wave, and those are exactly the index distances of spatial neighbours along a Z-order curve: the
-// ~9 buckets one sample touches then pile up on a few waves and everyone else waits at the barrier (wave 0 spends 38 % of
-// an iteration there).  XOR-folding the slot number into the wave number keeps every group of 8 consecutive buckets on
-// 8 different waves and moves the power-of-two neighbours apart as well.
-#ifndef TGN_FPS_PERM
-#define TGN_FPS_PERM 1
-#endif
+// Which wave holds bucket b = NW * s + i of the curve in its register slot s: wave (i + s) % NW.  The buckets one sample touches
+// are a run of neighbours along the curve plus whatever the curve folds next to them.  Every NW consecutive buckets sit on NW
+// different waves, and the rotation by the slot number keeps b, b + NW, b + 2 NW ... apart as well.  The XOR fold of the slot into
+// the wave number, written for the Z-order curve (neighbours at index distances 1, 2, 4, 8, 64), is last on the model's busiest-wave
+// count (round robin 1.58, this 1.61, XOR fold 1.64 - 1.66 touched buckets) and last on the GPU; this rotation and plain round
+// robin are within 0.02 ms per launch of each other there, this one ahead on levels 1 + 2 together in each of three A/B rounds
+// (profiles/fps_bucket_order_before_after.txt).
 // (applied where the sorted order is written -- tab[] is stored in (slot, wave) order -- so the loop's look-ups are unchanged)
 template <int NW>
 __device__ __forceinline__ unsigned fps_bucket_slot(unsigned pos) {   // sorted position -> position in (slot, wave, lane) order
     const unsigned b = pos >> 6, sl = b / NW, i = b & (NW - 1);
-#if TGN_FPS_PERM == 1
-    const unsigned w = i ^ ((sl ^ (sl >> 3)) & (NW - 1));
-#elif TGN_FPS_PERM == 2
-    const unsigned w = (i + 3u * sl + (sl >> 3)) & (NW - 1);
-#else
-    const unsigned w = i;
-#endif
+    const unsigned w = (i + sl) & (NW - 1);
     return ((sl * NW + w) << 6) | (pos & 63u);
 }
 
 namespace tgn {
+
+// cell x | y << 4 | z << 8 -> its Hilbert index, built by the compiler (fps_common.h).  One vector look-up per point out of 8 KB
+// that stay cache-resident; the index computed in registers (four levels of the transform) measured 0.003 ms more set-up per
+// launch and the same iteration.
+__device__ const FpsCellOrder<4> kFpsCellOrder4{};
 
 // deposit a wave-uniform value into one lane of a per-lane register (the metadata lane of a bucket)
 // (one v_writelane_b32: a select would need a lane mask per slot -- 2 x 48 SGPRs, spilled to VGPR lanes)
@@ -84,7 +86,7 @@ __global__ __launch_bounds__(NT) void fps_bucket_kernel(FpsArgs a) {
     constexpr int CAP = NT * P;
     static_assert(P <= kWave, "bucket metadata lives in lanes 0..P-1");
     static_assert(CAP <= 32768, "15-bit local indices");
-    // Set-up: 4096 Z-order cells (CB = 4 bits per axis), two 16-bit counters per word (a cloud has < 65 536 points); once the
+    // Set-up: 4096 cells (CB = 4 bits per axis) in Hilbert order, two 16-bit counters per word (a cloud has < 65 536 points); once the
     // points are placed the same LDS holds the result staging buffer and the bucket arg-max planes.
     // The order only decides which bucket a point lands in, never a result, and 12 bits are as good as round 1's 15 for buckets
     // of 64 points (24 000 -> 4096: 3.76 vs 3.75 ms per 256 scans) -- but the workgroup then holds 63 KiB of LDS instead of
@@ -150,8 +152,8 @@ __global__ __launch_bounds__(NT) void fps_bucket_kernel(FpsArgs a) {
         gscale[c] = (ext > 0.0f && ext < 3.0e38f) ? (float)(1 << CB) / ext : 0.0f;
     }
 
-    // ---- 2. counting sort by 15-bit Z-order cell (LDS atomics; the order inside a cell is arbitrary -- it only decides
-    //         which of two neighbouring buckets a point lands in, never a result) -------------------------------------
+    // ---- 2. counting sort by the 12-bit Hilbert index of the cell (LDS atomics; the order inside a cell is arbitrary -- it
+    //         only decides which of two neighbouring buckets a point lands in, never a result) -------------------------
     auto cell_of = [&](int i) -> unsigned {
         unsigned cc[3];
 #pragma unroll
@@ -160,18 +162,29 @@ __global__ __launch_bounds__(NT) void fps_bucket_kernel(FpsArgs a) {
             t = fminf(fmaxf(t, 0.0f), (float)((1 << CB) - 1));  // NaN -> 0
             cc[c] = (unsigned)(int)t;
         }
-        return spread5(cc[0]) | (spread5(cc[1]) << 1) | (spread5(cc[2]) << 2);
+        return kFpsCellOrder4.v[cc[0] | (cc[1] << CB) | (cc[2] << (2 * CB))];
     };
     for (int i = tid; i < kCellWords; i += NT) cells[i] = 0u;
     for (int i = n + tid; i < CAP; i += NT) tab[fps_bucket_slot<NW>((unsigned)i)] = (unsigned short)0xFFFF;
     __syncthreads();
-    #pragma unroll 4
-    for (int i = tid; i < n; i += NT) {
-        const unsigned code = cell_of(i);
-        atomicAdd(&cells[code >> 1], 1u << ((code & 1u) << 4));
+    // The cell of a point is worked out ONCE: the codes stay in registers until the placing pass (two 12-bit codes per VGPR; the
+    // x, y, z, d arrays of the loop are not live yet), which then neither reads nor scales a point again.  The index is clamped
+    // rather than tested, so the loads of all rounds are unconditional and go out together.
+    unsigned codes[(P + 1) / 2] = {};
+    if (n > 0) {  // block-uniform
+#pragma unroll
+        for (int k = 0; k < P; ++k) {
+            const int i = tid + k * NT;
+            const unsigned code = cell_of(i < n ? i : n - 1);
+            if (i < n) atomicAdd(&cells[code >> 1], 1u << ((code & 1u) << 4));
+            if (k & 1)
+                codes[k >> 1] |= code << 16;
+            else
+                codes[k >> 1] = code;
+        }
     }
     __syncthreads();
-    {   // exclusive prefix over the 32 768 counters: thread t owns words [t*W, (t+1)*W)
+    {   // exclusive prefix over the 4096 counters: thread t owns words [t*W, (t+1)*W)
         constexpr int W = kCellWords / NT;
         unsigned sum = 0;
 #pragma unroll 4
@@ -198,18 +211,21 @@ __global__ __launch_bounds__(NT) void fps_bucket_kernel(FpsArgs a) {
         }
     }
     __syncthreads();
-    #pragma unroll 4
-    for (int i = tid; i < n; i += NT) {
-        const unsigned code = cell_of(i);
-        const unsigned sh = (code & 1u) << 4;
-        const unsigned old = atomicAdd(&cells[code >> 1], 1u << sh);  // cursor of the cell; never carries into its neighbour
-        tab[fps_bucket_slot<NW>((old >> sh) & 0xFFFFu)] = (unsigned short)i;
+#pragma unroll
+    for (int k = 0; k < P; ++k) {
+        const int i = tid + k * NT;
+        if (i < n) {
+            const unsigned code = (codes[k >> 1] >> ((k & 1) << 4)) & 0xFFFFu;
+            const unsigned sh = (code & 1u) << 4;
+            const unsigned old = atomicAdd(&cells[code >> 1], 1u << sh);  // cursor of the cell; never carries into its neighbour
+            tab[fps_bucket_slot<NW>((old >> sh) & 0xFFFFu)] = (unsigned short)i;
+        }
     }
     __syncthreads();
 
-    // ---- 5. my P points.  Z-order bucket b (sorted positions [64b, 64b+64)) goes to wave b % NW, slot b / NW:
-    //         neighbouring buckets -- the ones a new sample touches together -- sit in DIFFERENT waves, so
-    //         their updates run concurrently instead of queueing on one wave. ---------------------------------
+    // ---- 5. my P points.  Bucket b of the curve (sorted positions [64b, 64b+64)) sits in slot b / NW of the wave
+    //         fps_bucket_slot gives it: neighbouring buckets -- the ones a new sample touches together -- sit in
+    //         DIFFERENT waves, so their updates run concurrently instead of queueing on one wave. --------------
     float x[P], y[P], z[P], d[P];
 #pragma unroll
     for (int s = 0; s < P; ++s) {

@@ -227,6 +227,47 @@ __device__ __forceinline__ unsigned fps_block_argmax(float best, unsigned key, u
     }
 }
 
+// ---- the order of the buckets (fps_bucket.hip): Hilbert index of a grid cell ----------------------------------------------------
+// Index of cell (x, y, z) of a (2^bits)^3 grid along the 3-D Hilbert curve (Skilling's transpose form: undo the excess work of
+// the Gray-coded axes level by level, Gray-encode, interleave; x carries the most significant bit of each triple).  A bijection
+// onto 0 .. 8^bits - 1; index 0 is cell (0, 0, 0); consecutive indices are face-adjacent cells, so 64 consecutive points of a
+// cloud sorted by it form ONE compact patch -- a Z-order curve jumps, and the box of such a stretch then reaches across the jump.
+__host__ __device__ constexpr unsigned fps_hilbert3(unsigned x, unsigned y, unsigned z, int bits) {
+    unsigned X[3] = {x, y, z};
+    const unsigned M = 1u << (bits - 1);
+    for (unsigned Q = M; Q > 1u; Q >>= 1) {
+        const unsigned P = Q - 1u;
+        for (int i = 0; i < 3; ++i) {
+            if (X[i] & Q) {
+                X[0] ^= P;
+            } else {
+                const unsigned t = (X[0] ^ X[i]) & P;
+                X[0] ^= t;
+                X[i] ^= t;
+            }
+        }
+    }
+    X[1] ^= X[0];
+    X[2] ^= X[1];
+    unsigned t = 0u;
+    for (unsigned Q = M; Q > 1u; Q >>= 1)
+        if (X[2] & Q) t ^= Q - 1u;
+    unsigned h = 0u;
+    for (int b = bits - 1; b >= 0; --b)
+        for (int i = 0; i < 3; ++i) h = (h << 1) | (((X[i] ^ t) >> b) & 1u);
+    return h;
+}
+// The same mapping as a table, built by the compiler: v[x | y << bits | z << 2 bits].  The kernels read a __device__ copy (two
+// look-ups per point, 8 KB at 4 bits: cache-resident); tgn_fps_bucket_order exports the host copy to tools/fps_bucket_model.py.
+template <int BITS>
+struct FpsCellOrder {
+    unsigned short v[1 << (3 * BITS)];
+    constexpr FpsCellOrder() : v{} {
+        for (unsigned c = 0; c < (1u << (3 * BITS)); ++c)
+            v[c] = (unsigned short)fps_hilbert3(c & ((1u << BITS) - 1u), (c >> BITS) & ((1u << BITS) - 1u), c >> (2 * BITS), BITS);
+    }
+};
+
 // The plain register-resident kernels of fps.hip cover clouds of up to kFpsPlainMaxN points; every larger cloud takes the
 // bucket-skipping kernel of fps_bucket.hip, whose largest shape holds kFpsResidentCapacity points: the largest cloud that needs
 // no workspace (tgn_fps_resident_capacity).
