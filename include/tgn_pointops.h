@@ -604,6 +604,22 @@ int tgn_edgeconv1_max(int B, int N, int K, const float *P, const float *Q, const
                       tgn_stream_t stream);
 
 /*
+ * A pointwise linear layer fused with the max over the points: PointNet's stn.conv3, fstn.conv3 and feat.conv3
+ * (pointnet_utils.py:29-32, 69-72, 127-128) and DGCNN's conv6 (dgcnn.py:117-118) in eval mode, without the (B, C, N) tensor.
+ *   out[b, c] = max_{n < N} act( (sum_{k < K} x[b, k, n] * Wt[k, c]) + shift[c] )
+ * x (B, K, N) float32 channel-first with rows of N contiguous floats; Wt (K, C) row-major with the BatchNorm scale folded into its
+ * columns; shift (C) the folded bias and BatchNorm shift; act 0 = identity, 1 = relu, 2 = leaky relu with `slope`; out (B, C).
+ * The sum is the fp32 MFMA's fma chain over k ascending from 0, shift is added once after it, the activation comes before the max.
+ * A NaN candidate gives NaN (torch.max).  The max is exact, so scan b's result depends neither on B nor on how the launch cuts N:
+ * bit equality.  Two launches (partial maxima per point chunk into ws, then their reduction), no float atomics, no allocation, no
+ * synchronisation: capturable.  B, N, C >= 1 and 1 <= K <= 512; ws: at least tgn_linear_act_max_workspace_bytes(B, N, K, C) bytes
+ * of device memory (0 for a shape that is refused).
+ */
+size_t tgn_linear_act_max_workspace_bytes(int B, int N, int K, int C);
+int tgn_linear_act_max(int B, int N, int K, int C, const float *x, const float *Wt, const float *shift, int act, float slope,
+                       float *out, void *ws, size_t ws_bytes, tgn_stream_t stream);
+
+/*
  * Scoring a predicted segmentation against its ground truth: the reference's cal_metric (eval_visualize_results.py:20-57), which runs
  * about ten full-length numpy passes per predicted instance on the host.  Here the vertices are read once, into two integer tables per
  * scan, and the scores are computed from the tables.  Labels are int64; 2 <= nlab <= 64 (FDI numbers reach 48), anything else is

@@ -8,6 +8,7 @@ Point-Transformer subtraction / aggregation operators).
     toothgroupnetwork_amd.preprocess        preprocess_data.py / gen_utils.read_txt_obj_ls (OBJ -> 24 000-point .npy)
     toothgroupnetwork_amd.point_transformer mirrors of the cbl_point_transformer blocks (fused eval paths)
     toothgroupnetwork_amd.dgcnn             DGCNN: feature-space kNN, edge features, the DGCnnModule mirror (fused EdgeConv)
+    toothgroupnetwork_amd.pointnet          PointNet: the fused linear + max-over-points layer, the PointFirstModule mirror
     toothgroupnetwork_amd.tsegnet           tsegnet's join between its two networks and its label painting (proposals, clusters, crops)
     toothgroupnetwork_amd.losses            the geometric training losses of tgnet_fps and tsegnet (fused forward and backward kernels)
     toothgroupnetwork_amd.nets              whole-network mirrors (state_dict-compatible with the reference's modules)

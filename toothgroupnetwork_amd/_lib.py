@@ -133,6 +133,8 @@ SIGNATURES = {
     "tgn_feature_knn": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "tgn_edgeconv2_max": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, ctypes.c_longlong, c_int, _P]),
     "tgn_edgeconv1_max": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, ctypes.c_longlong, c_int, _P]),
+    "tgn_linear_act_max_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "tgn_linear_act_max": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, c_int, ctypes.c_float, _P, _P, c_size_t, _P]),
     "tgn_seg_confusion_chunk": (c_int, []),
     "tgn_seg_confusion": (c_int, [c_int, ctypes.c_longlong, _P, _P, _P, _P, c_int, _P, _P, _P]),
     "tgn_seg_confusion_logits": (c_int, [c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P]),

@@ -17,6 +17,9 @@ of the fused eval paths.  Parameter names and shapes equal the reference classes
                        contrastive-boundary criterion of training (heads.py:62-253) is the reference's own Python.
   DGCnnModule          models/modules/dgcnn.py:43-143 (the "dgcnn" model): three EdgeConv levels over feature-space kNN graphs,
                        fused in eval mode (dgcnn.py of this package, re-exported here).
+  PointFirstModule     models/modules/pointnet.py:49-68 (the "pointnet" model): PointNet at scale 2 with both transform regressors;
+                       its three linear + max-over-points layers are one fp32-MFMA kernel in eval mode (pointnet.py of this
+                       package, re-exported here).
   GroupingNetworkModule  models/modules/grouping_network_module.py:7-101, tgnet_fps's network (train_configs/tgnet_fps.py): a
                        PointTransformerSeg over the scan, on-device tooth crops (crops.tooth_crops), a second PointTransformerSeg over
                        all crops as one batch.  Without labels the centroids come from on-device clustering (cluster.py, which
@@ -36,6 +39,7 @@ import numpy as np
 
 from . import _derived, _lib, cluster as _cluster, crops as _crops, point_transformer as PT, pointops, tsegnet as _tsg
 from .dgcnn import DGCnnModule  # noqa: F401
+from .pointnet import PointFirstModule  # noqa: F401
 from .pointnet2_utils import PointNetFeaturePropagation, PointNetSetAbstraction, PointNetSetAbstractionMsg, linear_relu, square_distance
 
 
