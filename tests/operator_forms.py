@@ -28,7 +28,7 @@ rounding to that dtype of some value within the bound -- no tolerance of its own
 Not covered.  Offsets tensors whose VALUES are wrong (not cumulative, last != n): validating them costs a host synchronisation
 that knnquery deliberately avoids.  Tensors on different devices: the test machines have one GPU.
 
-INTERNAL lists the functions and classes that reach _lib.ptr( without a row of their own, with the row that covers them;
+INTERNAL lists the functions and classes that pass raw pointers to the library without a row of their own, with the row that covers them;
 tests/test_operator_forms_host.py fails for a wrapper that is neither a row nor listed there.
 """
 import torch
@@ -592,7 +592,7 @@ row("paint_labels", "tsegnet", ["paint_labels"], _paint_build,
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# wrappers that reach _lib.ptr( without a row of their own: name -> (module, the row that covers them, why)
+# wrappers that pass raw pointers to the library without a row of their own: name -> (module, the row that covers them, why)
 # ---------------------------------------------------------------------------------------------------------------------------
 INTERNAL = {
     "crop_knn": ("crops", "tooth_crops", "the host layer's launch for crops, cluster and tsegnet, whose wrappers validate and pack first; it "

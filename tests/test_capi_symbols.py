@@ -43,29 +43,98 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(handle, name), f"{name} declared in include/ but not exported"
 
 
-def _declared_arity():
+_C_SCALARS = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float, "double": ctypes.c_double,
+              "size_t": ctypes.c_size_t}
+_C_TYPE_WORDS = {"void", "char", "short", "int", "long", "unsigned", "float", "double", "size_t", "tgn_stream_t", "*"}
+
+
+def _ctype(decl):
+    """The ctypes mirror of one C result or parameter declaration: char * (const or not) -> c_char_p, any other pointer and
+    tgn_stream_t -> c_void_p, void -> None, a scalar -> its own type (an unknown one is a KeyError)."""
+    words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+    if words[-1] not in _C_TYPE_WORDS:
+        words = words[:-1]                                          # the parameter's name
+    if "*" in words:
+        return ctypes.c_char_p if words == ["char", "*"] else ctypes.c_void_p
+    if words == ["tgn_stream_t"]:
+        return ctypes.c_void_p
+    return None if words == ["void"] else _C_SCALARS[" ".join(words)]
+
+
+def _declared_signatures():
+    """name -> (restype, [argtypes]) of every function declared in include/*.h, in the form of _lib.SIGNATURES."""
     out = {}
     for h in glob.glob(os.path.join(REPO, "include", "*.h")):
         src = open(h).read()
         src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
         src = re.sub(r"//[^\n]*", "", src)
         src = re.sub(r"^\s*#[^\n]*", "", src, flags=re.M)
-        for m in re.finditer(r"\b([A-Za-z_][A-Za-z0-9_]*)\s*\(([^;{}()]*)\)\s*;", src):
-            args = m.group(2).strip()
-            out[m.group(1)] = 0 if args in ("", "void") else args.count(",") + 1
+        for m in re.finditer(r"([A-Za-z_][A-Za-z0-9_\s*]*?)\b([A-Za-z_][A-Za-z0-9_]*)\s*\(([^;{}()]*)\)\s*;", src):
+            args = m.group(3).strip()
+            out[m.group(2)] = (_ctype(m.group(1)), [] if args in ("", "void") else [_ctype(a) for a in args.split(",")])
     return out
 
 
 def test_ctypes_table_matches_header():
     from toothgroupnetwork_amd import _lib
     assert sorted(_lib.SIGNATURES) == _declared_functions()
-    arity = _declared_arity()
-    for name, (_, args) in _lib.SIGNATURES.items():     # a wrong count is a TypeError (or garbage arguments) at call time
-        assert len(args) == arity[name], (name, len(args), arity[name])
+    declared = _declared_signatures()
+    for name, (res, args) in _lib.SIGNATURES.items():     # a wrong count is a TypeError at call time, a wrong type garbage in the kernel
+        assert (res, list(args)) == declared[name], (name, (res, list(args)), declared[name])
     L = _lib.lib()
     assert b"gfx950" in L.tgn_version()
     assert L.tgn_fps_resident_capacity() >= 24000  # a whole 24 000-point scan stays in registers
     assert L.tgn_ball_query_workspace_bytes(1, 24000, 4096) >= 0
+
+
+def test_checked_view_checks_every_status_function():
+    """ops() raises for every c_int function that is not listed as value-returning, so a new entry point cannot go unchecked by
+    accident; the raw view checks nothing."""
+    from toothgroupnetwork_amd import _lib
+    ints = {name for name, (res, _) in _lib.SIGNATURES.items() if res is ctypes.c_int}
+    assert _lib.VALUE_RETURNING <= ints, sorted(_lib.VALUE_RETURNING - ints)
+    O, L = _lib.ops(), _lib.lib()
+    for name in _lib.SIGNATURES:
+        want = _lib._raise_on_status if name in ints - _lib.VALUE_RETURNING else None
+        assert getattr(O, name).errcheck is want, name
+        assert getattr(L, name).errcheck is None, name
+
+
+def test_checked_view_raises_with_the_name_of_the_function_that_failed():
+    """The two refusals below (the raw view's status 3, before any launch) as the package's operators see them."""
+    from toothgroupnetwork_amd import _lib
+    O = _lib.ops()
+    buf = ctypes.create_string_buffer(64 + 16)
+    p = ctypes.c_void_p((ctypes.addressof(buf) + 15) & ~15)
+    with pytest.raises(RuntimeError) as e:
+        O.tgn_knnquery(1, 1, 129, p, p, p, p, p, p, None)
+    assert str(e.value) == ("libtgn_pointops tgn_knnquery failed (status 3): "
+                            "tgn_knnquery: nsample 129 > 128 unsupported (the reference's limit is 100)")
+    with pytest.raises(RuntimeError, match=r"^libtgn_pointops tgn_pt_attention_forward failed \(status 3\): .*\(got 12\)$"):
+        O.tgn_pt_attention_forward(1, 4, 24, 12, *([p] * 18), None)
+
+
+def test_checked_view_converts_pointer_arguments():
+    """tgn_furthestsampling_dense with B = 0 returns TGN_OK before it looks at a pointer or makes a HIP call: None and c_void_p pass,
+    a CPU tensor (whose address must never reach a kernel) and anything that is no pointer are refused before the call."""
+    from toothgroupnetwork_amd import _lib
+    O = _lib.ops()
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    assert O.tgn_furthestsampling_dense(0, 0, 0, None, None, None, None, 0, None) == 0
+    assert O.tgn_furthestsampling_dense(0, 0, 0, p, None, p, p, 0, ctypes.c_void_p(0)) == 0
+    with pytest.raises(ctypes.ArgumentError, match="no CPU fallback"):
+        O.tgn_furthestsampling_dense(0, 0, 0, torch.zeros(3), None, None, None, 0, None)
+    with pytest.raises(ctypes.ArgumentError, match="TypeError: expected a CUDA tensor, None or a c_void_p, got int"):
+        O.tgn_furthestsampling_dense(0, 0, 0, ctypes.addressof(buf), None, None, None, 0, None)
+
+
+def test_checked_view_leaves_value_returning_functions_alone():
+    from toothgroupnetwork_amd import _lib
+    O, L = _lib.ops(), _lib.lib()
+    assert O.tgn_get_tuning(b"fps_lean", -1) == L.tgn_get_tuning(b"fps_lean", -1) != -1
+    assert O.tgn_get_tuning(b"no_such_switch", 77) == 77
+    assert O.tgn_fps_resident_capacity() == L.tgn_fps_resident_capacity() >= 24000
 
 
 def test_knnquery_refuses_more_than_128_neighbours_before_any_launch():
@@ -112,6 +181,8 @@ def test_missing_library_fails_loudly(monkeypatch):
     monkeypatch.setattr(_lib, "LIB_PATH", "/nonexistent/libtgn_pointops.so")
     with pytest.raises(_lib.TgnLibraryError, match="not been built"):
         _lib.lib()
+    with pytest.raises(_lib.TgnLibraryError, match="not been built"):
+        _lib.ops()
 
 
 def test_product_never_imports_the_oracle():

@@ -1,10 +1,11 @@
 """CPU: the operator table of tests/operator_forms.py is complete and its form builders do what they say.
 
 Every public callable of toothgroupnetwork_amd.pointops that the reference's pointops.py defines has a row, and so has every
-function or class of pointops, pointnet2_utils, sa_fused, dgcnn, crops, cluster, tsegnet and point_transformer whose source reaches
-``ptr(`` (the raw device pointer of a tensor) -- or it is listed in INTERNAL with the row that covers it.  A wrapper added later
-without a row fails here.
+function or class of pointops, pointnet2_utils, sa_fused, dgcnn, crops, cluster, tsegnet and point_transformer whose source calls
+a library function that takes a pointer (the binding passes it a tensor's raw device pointer) -- or it is listed in INTERNAL with
+the row that covers it.  A wrapper added later without a row fails here.
 """
+import ctypes
 import importlib
 import inspect
 import re
@@ -16,6 +17,8 @@ import operator_forms as T
 
 
 def _reaches_ptr(module):
+    from toothgroupnetwork_amd import _lib
+    takes_pointer = {name for name, (_, args) in _lib.SIGNATURES.items() if ctypes.c_void_p in args}
     mod = importlib.import_module("toothgroupnetwork_amd." + module)
     found = []
     for name, obj in vars(mod).items():
@@ -24,7 +27,7 @@ def _reaches_ptr(module):
                 source = inspect.getsource(obj)
             except (OSError, TypeError):         # a class made by a call (a namedtuple): no source, no pointer
                 continue
-            if re.search(r"\bptr\(", source):
+            if takes_pointer.intersection(re.findall(r"\b(tgn_\w+)\(", source)):
                 found.append(name)
     return mod, found
 
@@ -32,10 +35,10 @@ def _reaches_ptr(module):
 @pytest.mark.parametrize("module", T.SWEPT_MODULES)
 def test_every_wrapper_that_takes_a_raw_pointer_has_a_row(module):
     mod, found = _reaches_ptr(module)
-    assert found, f"{module}: no function reaches ptr( -- has the binding been renamed?"
+    assert found, f"{module}: no function calls a pointer-taking tgn_* function -- has the binding been renamed?"
     covered = T.covered_names(module)
     missing = [n for n in found if n not in covered]
-    assert not missing, f"{module}: {missing} reach _lib.ptr( but have neither a row in tests/operator_forms.py nor an INTERNAL entry"
+    assert not missing, f"{module}: {missing} pass raw pointers but have neither a row in tests/operator_forms.py nor an INTERNAL entry"
     stale = [n for n in covered if not hasattr(mod, n)]
     assert not stale, f"{module}: the table names {stale}, which the module does not define"
 

@@ -3,6 +3,11 @@
 This is the ONLY compute path of the package: there is no CPU or eager-PyTorch fallback.
 If the library has not been built (``python -c "import __graft_entry__ as g; g.build()"`` or
 ``make -C toothgroupnetwork_amd/csrc``) every operator raises, loudly.
+
+Two views of the one loaded library, both built from SIGNATURES.  ``ops()`` is what the package's operators call, a new one
+included: a non-zero status raises RuntimeError naming the function, and a pointer argument is a CUDA tensor, None or a c_void_p
+(a CPU tensor is refused before the call).  ``lib()`` is the raw handle, whose status codes come back as ints: for tests, tools/
+and the few callers that turn a status into something else themselves.
 """
 import ctypes
 import os
@@ -20,7 +25,8 @@ from . import config
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TGN_LIB_PATH") or os.path.join(_HERE, "csrc", "libtgn_pointops.so")   # TGN_LIB_PATH: A/B builds (tools/)
 
-_lib = None
+_lib = None     # lib(): the raw view
+_ops = None     # ops(): the checked view
 
 c_int = ctypes.c_int
 c_float = ctypes.c_float
@@ -149,6 +155,11 @@ SIGNATURES = {
     "tgn_scan_take": (c_int, [_P, _P, _P]),
     "tgn_scan_pool_trim": (c_int, []),
 }
+# The c_int functions above whose result is a value, not a TGN_* status.  ops() checks every other c_int function (and nothing
+# that returns size_t, char * or void), so a new entry point is checked unless it is named here.
+VALUE_RETURNING = frozenset({
+    "tgn_fps_resident_capacity", "tgn_get_fps_mode", "tgn_get_tuning", "tgn_sa_direct_supported", "tgn_sa_mlp2_direct_supported",
+    "tgn_sa_all_chunks", "tgn_seg_confusion_chunk", "tgn_take_index_error", "tgn_take_index_error_device"})
 
 ERR_INVALID_ARGUMENT, ERR_LAUNCH, ERR_UNSUPPORTED = 1, 2, 3     # TGN_ERR_* of include/tgn_pointops.h
 # bits of a stream's error word (tgn_take_index_error; csrc/tgn_common.h: kIndexErrGather, kIndexErrCrop)
@@ -186,7 +197,7 @@ def set_fps_mode(ties=None, fma=None):
     if fma is not None:
         _fps_mode["fma"] = bool(fma)
     if _lib is not None or os.path.exists(LIB_PATH):
-        lib().tgn_set_fps_mode(fps_flags())   # the reference-signature launcher (pointops_cuda shim) follows too
+        ops().tgn_set_fps_mode(fps_flags())   # the reference-signature launcher (pointops_cuda shim) follows too
     return prev
 
 
@@ -198,8 +209,8 @@ def set_tuning(key, value):
     """Select a kernel variant inside the library (include/tgn_pointops.h: tgn_set_tuning; keys "fps_bucket_min", "fps_lean",
     "ball_bitmap", "sa_tile", "gather_v4").  Returns the previous value.  A/B runs and parity tests only."""
     k = key.encode()
-    prev = lib().tgn_get_tuning(k, 0)
-    check(lib().tgn_set_tuning(k, int(value)), "tgn_set_tuning")
+    prev = ops().tgn_get_tuning(k, 0)
+    ops().tgn_set_tuning(k, int(value))
     return prev
 
 
@@ -233,28 +244,52 @@ class TgnLibraryError(RuntimeError):
     pass
 
 
+def _load(checked):
+    """A ctypes handle on the library with SIGNATURES applied (a second handle on one path shares the loaded library and its
+    state); checked: with the conversions and the status check of ops()."""
+    if not os.path.exists(LIB_PATH):
+        raise TgnLibraryError(
+            f"{LIB_PATH} not found: the HIP extension has not been built. Run "
+            "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C toothgroupnetwork_amd/csrc`). "
+            "toothgroupnetwork_amd has no CPU or eager fallback.")
+    handle = ctypes.CDLL(LIB_PATH)
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(handle, name)  # AttributeError if the .so is stale
+        fn.restype = res
+        fn.argtypes = [_Pointer if checked and a is c_void_p else a for a in args]
+        if checked and res is c_int and name not in VALUE_RETURNING:
+            fn.errcheck = _raise_on_status
+    return handle
+
+
 def lib():
-    """Load the HIP library; raise if it is missing (no fallback exists)."""
+    """Load the HIP library; raise if it is missing (no fallback exists).  The raw view: a status comes back as an int."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise TgnLibraryError(
-                f"{LIB_PATH} not found: the HIP extension has not been built. Run "
-                "`python -c 'import __graft_entry__ as g; g.build()'` (or `make -C toothgroupnetwork_amd/csrc`). "
-                "toothgroupnetwork_amd has no CPU or eager fallback.")
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError if the .so is stale
-            fn.restype = res
-            fn.argtypes = args
-        _lib = handle
+        _lib = _load(checked=False)
     return _lib
+
+
+def ops():
+    """The checked view of the same library, for the package's own calls: a status function raises on failure (naming itself),
+    a pointer argument is converted by _Pointer, and streams stay explicit arguments."""
+    global _ops
+    lib()       # the one gate to the library: it reports a missing build, and a host test that replaces it sees every caller
+    if _ops is None:
+        _ops = _load(checked=True)
+    return _ops
 
 
 def check(rc, what=""):
     if rc != 0:
-        msg = lib().tgn_last_error().decode("utf-8", "replace")
+        msg = lib().tgn_last_error().decode("utf-8", "replace")     # thread-local in capi.hip: the text of this thread's call
         raise RuntimeError(f"libtgn_pointops {what} failed (status {rc}): {msg}")
+
+
+def _raise_on_status(rc, fn, args):
+    if rc:
+        check(rc, fn.__name__)      # (ctypes names a function object after its symbol)
+    return rc
 
 
 def ptr(t):
@@ -275,6 +310,22 @@ def require_cuda(*tensors):
                 "there is deliberately no CPU fallback -- the CPU restatement lives in oracle/ and is test-only.")
 
 
+class _Pointer:
+    """What ops() takes where the C function takes a pointer or a stream: a CUDA tensor (its data_ptr(); strided views are
+    meant to pass, their stride is an argument of its own), None (NULL) or a c_void_p (a stream, a host array's
+    .ctypes.data_as).  ctypes reports a refusal as ctypes.ArgumentError, before the call."""
+
+    @staticmethod
+    def from_param(v):
+        if isinstance(v, torch.Tensor):
+            if not v.is_cuda:
+                require_cuda(v)     # raises; a backstop behind the operators' own require_cuda: a host address must not reach a kernel
+            return c_void_p(v.data_ptr())
+        if v is None or isinstance(v, c_void_p):
+            return v
+        raise TypeError(f"expected a CUDA tensor, None or a c_void_p, got {type(v).__name__}")
+
+
 # What the gather family does about an index outside [-N, N) -- where the reference's advanced indexing raises
 # (pointnet2_utils.py:56-60; an empty ball yields index N, :136-141).  The kernels latch a flag that belongs to the
 # (device, STREAM) they were launched on;
@@ -290,13 +341,13 @@ def require_cuda(*tensors):
 def take_index_error():
     """True (and the flag is cleared) if a gather launched on the CURRENT torch stream of the current device saw an out-of-range
     index since the last call.  Synchronises that stream."""
-    return bool(lib().tgn_take_index_error(stream()))
+    return bool(ops().tgn_take_index_error(stream()))
 
 
 def take_index_error_device():
     """True (and every flag of the device is cleared) if a gather on ANY stream of the current device saw an out-of-range index
     since the flags were last read.  Synchronises the device."""
-    return bool(lib().tgn_take_index_error_device())
+    return bool(ops().tgn_take_index_error_device())
 
 
 _check_state = threading.local()
@@ -311,7 +362,7 @@ def begin_index_check():
     training path's trusted gathers, TGN_INDEX_CHECK=off sections), in stream order and without a synchronisation, so that
     the IndexError raised afterwards belongs to this operator.  No-op inside a deferred_index_check() section."""
     if _checking() and not getattr(_check_state, "depth", 0):
-        lib().tgn_clear_index_error(stream())
+        ops().tgn_clear_index_error(stream())
 
 
 def raise_on_index_error(what):

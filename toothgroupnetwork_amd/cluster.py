@@ -61,7 +61,7 @@ def dbscan_counts(points, eps, min_samples, offset=None):
     _lib.require_cuda(pts)
     n = pts.shape[0]
     off = _offsets(offset, n)
-    L, dev, st = _lib.lib(), pts.device, _lib.stream()
+    L, dev, st = _lib.ops(), pts.device, _lib.stream()
     b = len(off)
     off_t = torch.tensor(off, dtype=torch.int32).to(dev, non_blocking=True)
     labels = torch.empty(n, dtype=torch.int64, device=dev)
@@ -69,17 +69,16 @@ def dbscan_counts(points, eps, min_samples, offset=None):
     counts = torch.empty(b, dtype=torch.int32, device=dev)
     wsb = L.tgn_dbscan_workspace_bytes(b, n)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    _lib.check(L.tgn_dbscan(b, n, _lib.ptr(pts), _lib.ptr(off_t), eps, min_samples, _lib.ptr(labels), _lib.ptr(core), _lib.ptr(counts),
-                            _lib.ptr(ws), wsb, st), "tgn_dbscan")
+    L.tgn_dbscan(b, n, pts, off_t, eps, min_samples, labels, core, counts, ws, wsb, st)
     return labels, core.bool(), counts
 
 
 def _mean_shift_seeds(pts, bandwidth, max_iter):
-    L, dev = _lib.lib(), pts.device
+    L, dev = _lib.ops(), pts.device
     n = pts.shape[0]
     means = torch.empty(n, 3, dtype=torch.float64, device=dev)
     counts = torch.empty(n, dtype=torch.int32, device=dev)
-    _lib.check(L.tgn_mean_shift(n, _lib.ptr(pts), bandwidth, max_iter, _lib.ptr(means), _lib.ptr(counts), _lib.stream()), "tgn_mean_shift")
+    L.tgn_mean_shift(n, pts, bandwidth, max_iter, means, counts, _lib.stream())
     return means, counts
 
 
@@ -121,8 +120,7 @@ def mean_shift(points, bandwidth, max_iter=MAX_ITER):
     centers = _post_process(means.cpu().numpy(), counts.cpu().numpy(), bandwidth)            # the one synchronisation
     cent = torch.from_numpy(centers).to(pts.device)
     labels = torch.empty(pts.shape[0], dtype=torch.int64, device=pts.device)
-    _lib.check(_lib.lib().tgn_nearest_center(pts.shape[0], _lib.ptr(pts), cent.shape[0], _lib.ptr(cent), _lib.ptr(labels), _lib.stream()),
-               "tgn_nearest_center")
+    _lib.ops().tgn_nearest_center(pts.shape[0], pts, cent.shape[0], cent, labels, _lib.stream())
     return labels, cent
 
 
@@ -181,7 +179,7 @@ def get_clustering_labels(moved_points, labels):
     pts = moved[lab != 0].contiguous()                                                        # sync 1
     if pts.shape[0] == 0:
         raise ValueError("get_clustering_labels: no foreground point (every label is 0); the reference's DBSCAN raises here too")
-    L, st = _lib.lib(), _lib.stream()
+    L, st = _lib.ops(), _lib.stream()
     dl, core, ncl = dbscan_counts(pts, DBSCAN_EPS, DBSCAN_MIN_SAMPLES)
     K = int(ncl.item())                                                                       # sync 2
     if K == 0:
@@ -190,8 +188,7 @@ def get_clustering_labels(moved_points, labels):
     mean = torch.empty(K, 3, dtype=torch.float64, device=dev)
     cov = torch.empty(K, 3, 3, dtype=torch.float64, device=dev)
     core8 = core.to(torch.uint8)
-    _lib.check(L.tgn_cluster_moments(pts.shape[0], _lib.ptr(pts), _lib.ptr(dl), _lib.ptr(core8), K, _lib.ptr(counts), _lib.ptr(mean),
-                                     _lib.ptr(cov), st), "tgn_cluster_moments")
+    L.tgn_cluster_moments(pts.shape[0], pts, dl, core8, K, counts, mean, cov, st)
     first = _eigen_first(counts.cpu().numpy(), cov.cpu().numpy())                             # sync 3
     out = dl.clone()
     for i, c in enumerate(split_candidates(first)):
@@ -211,7 +208,7 @@ def get_clustering_labels(moved_points, labels):
         idx = _crops.crop_knn(cand_pts.t().contiguous()[None], scan, q, VOTE_K)
         cand_labels = out[cand].contiguous()
         vote = torch.empty(q.shape[0], dtype=torch.int64, device=dev)
-        _lib.check(L.tgn_cluster_vote(q.shape[0], VOTE_K, _lib.ptr(idx), m, _lib.ptr(cand_labels), _lib.ptr(vote), st), "tgn_cluster_vote")
+        L.tgn_cluster_vote(q.shape[0], VOTE_K, idx, m, cand_labels, vote, st)
         out[noise] = vote
     return out.cpu().numpy() if as_numpy else out
 

@@ -85,8 +85,7 @@ def crop_knn(feats, scan, cent, k):
     k = check_k(k, N)
     T = cent.shape[0]
     idx = torch.empty(T, k, dtype=torch.int64, device=feats.device)
-    _lib.check(_lib.lib().tgn_crop_knn(B, N, C, _lib.ptr(feats), T, _lib.ptr(scan), _lib.ptr(cent), k, _lib.ptr(idx), _lib.stream()),
-               "tgn_crop_knn")
+    _lib.ops().tgn_crop_knn(B, N, C, feats, T, scan, cent, k, idx, _lib.stream())
     return idx
 
 
@@ -98,8 +97,7 @@ def label_centroids(feats, labels, nlab):
     B, C, N = feats.shape
     counts = torch.empty(B, nlab, dtype=torch.int32, device=feats.device)
     cent = torch.empty(B, nlab, 3, dtype=torch.float32, device=feats.device)
-    _lib.check(_lib.lib().tgn_label_centroids(B, N, C, _lib.ptr(feats), _lib.ptr(labels), nlab, _lib.ptr(counts), _lib.ptr(cent),
-                                              _lib.stream()), "tgn_label_centroids")
+    _lib.ops().tgn_label_centroids(B, N, C, feats, labels, nlab, counts, cent, _lib.stream())
     return counts, cent
 
 
@@ -128,9 +126,9 @@ def tooth_crops(feats, labels=None, centroids=None, k=3072, num_labels=NUM_LABEL
     B, C, N = feats.shape
     k = check_k(k, N)
     lab = labels_2d(labels, B, N, (torch.int32, torch.int64)) if labels is not None else None
-    L, dev, st = _lib.lib(), feats.device, _lib.stream()
+    L, dev, st = _lib.ops(), feats.device, _lib.stream()
     if centroids is None:
-        _lib.check(L.tgn_clear_index_error(st), "tgn_clear_index_error")
+        L.tgn_clear_index_error(st)
         counts, cent_all = label_centroids(feats, lab, num_labels)
         present = counts.cpu().numpy() > 0                                        # the one synchronisation
         if L.tgn_take_index_error(st) & _lib.INDEX_ERROR_CROP:
@@ -148,6 +146,5 @@ def tooth_crops(feats, labels=None, centroids=None, k=3072, num_labels=NUM_LABEL
     idx = crop_knn(feats, scan, cent, k)
     cropped = torch.empty(T, C, k, dtype=torch.float32, device=dev)
     crop_lab = torch.empty(T, 1, k, dtype=torch.int64, device=dev) if lab is not None else None
-    _lib.check(L.tgn_crop_gather_center(B, N, C, T, k, _lib.ptr(feats), _lib.ptr(scan), _lib.ptr(idx), _lib.ptr(lab), _lib.ptr(cropped),
-                                        _lib.ptr(crop_lab), st), "tgn_crop_gather_center")
+    L.tgn_crop_gather_center(B, N, C, T, k, feats, scan, idx, lab, cropped, crop_lab, st)
     return ToothCrops(cropped, list(idx.split(per_scan)), crop_lab, list(cent.split(per_scan)))

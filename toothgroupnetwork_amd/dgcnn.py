@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from . import _derived, _lib
-from ._lib import check, lib, ptr, require_cuda, stream
+from ._lib import ops, require_cuda, stream
 from .point_transformer import _bn_scale_shift, _frozen
 
 def feature_knn(x, k):
@@ -29,9 +29,9 @@ def feature_knn(x, k):
     k = int(k)
     idx = torch.empty(B, N, max(k, 0), dtype=torch.long, device=x.device)
     dist = torch.empty(B, N, max(k, 0), dtype=torch.float32, device=x.device)
-    ws_bytes = lib().tgn_feature_knn_workspace_bytes(B, N, k)
+    ws_bytes = ops().tgn_feature_knn_workspace_bytes(B, N, k)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
-    check(lib().tgn_feature_knn(B, N, D, k, ptr(x), ptr(idx), ptr(dist), ptr(ws), ws_bytes, stream()), "feature_knn")
+    ops().tgn_feature_knn(B, N, D, k, x, idx, dist, ws, ws_bytes, stream())
     return idx, dist
 
 
@@ -103,11 +103,10 @@ def edgeconv_max(x, idx, first, second=None, out=None, coff=0):
         out, coff = torch.empty(B, 64, N, dtype=torch.float32, device=x.device), 0
     _lib.begin_index_check()
     if second is None:
-        check(lib().tgn_edgeconv1_max(B, N, K, ptr(P), ptr(Q), ptr(idx), ptr(out), out.stride(0), coff, stream()), "edgeconv1_max")
+        ops().tgn_edgeconv1_max(B, N, K, P, Q, idx, out, out.stride(0), coff, stream())
     else:
         W2, b2 = (t.float().contiguous() for t in second)
-        check(lib().tgn_edgeconv2_max(B, N, K, ptr(P), ptr(Q), ptr(idx), ptr(W2), ptr(b2), ptr(out), out.stride(0), coff, stream()),
-              "edgeconv2_max")
+        ops().tgn_edgeconv2_max(B, N, K, P, Q, idx, W2, b2, out, out.stride(0), coff, stream())
     _lib.raise_on_index_error("DGCNN EdgeConv")
     return out
 

@@ -12,7 +12,7 @@ feature widths D=[6,128,512] (level l>0 groups synthetic features of the width t
 import torch
 
 from . import _lib, config
-from ._lib import check, lib, ptr
+from ._lib import ops
 from .sa_fused import launch_branch, pack_first_layer, pack_second_layer, pad16, plan_branch
 
 SHAPE_A = dict(n=24000, npoint=[4096, 1024, 256], radius=[0.05, 0.1, 0.2], nsample=[32, 32, 32], d=[6, 128, 512],
@@ -135,7 +135,7 @@ class HotPath:
         # on the device.  Off by default: the headline benchmark runs every level's sampling for real.
         self.fps_prefix = bool(fps_prefix)
         self.xyz_first = shape.get("xyz_first", True)
-        self.L = lib()
+        self.L = ops()
         self.pipeline = bool(pipeline)
         self.phased = self.pipeline and not self.fused
         # phase-2 placement of the NEXT step's level-1 grid build: "own" (default) on a stream of its own, released when the previous
@@ -247,17 +247,14 @@ class HotPath:
 
     def _ball(self, lv, br, cur_xyz, st, prebuilt=False):
         fn = self.L.tgn_ball_query_prebuilt if prebuilt else self.L.tgn_ball_query
-        return check(fn(self.B, lv["N"], lv["S"], br["K"], br["r2"], ptr(cur_xyz), ptr(lv["new_xyz"]),
-                        ptr(br["group_idx"]), self.idx64, ptr(br["ws"]), br["ws_bytes"], st), "ball_query")
+        fn(self.B, lv["N"], lv["S"], br["K"], br["r2"], cur_xyz, lv["new_xyz"], br["group_idx"], self.idx64, br["ws"], br["ws_bytes"], st)
 
     def _ball_build(self, lv, br, cur_xyz, st):
-        return check(self.L.tgn_ball_query_build(self.B, lv["N"], lv["S"], br["K"], br["r2"], ptr(cur_xyz), ptr(br["ws"]),
-                                                 br["ws_bytes"], st), "ball_query_build")
+        self.L.tgn_ball_query_build(self.B, lv["N"], lv["S"], br["K"], br["r2"], cur_xyz, br["ws"], br["ws_bytes"], st)
 
     def _group(self, lv, br, cur_xyz, pts, st):
-        return check(self.L.tgn_group_points_ex(self.B, lv["N"], lv["S"], br["K"], lv["D"], ptr(cur_xyz), ptr(lv["new_xyz"]),
-                                                ptr(pts), ptr(br["group_idx"]), self.idx64, int(self.xyz_first),
-                                                ptr(br["grouped"]), 0, -1, self.group_max_blocks, st), "group_points")
+        self.L.tgn_group_points_ex(self.B, lv["N"], lv["S"], br["K"], lv["D"], cur_xyz, lv["new_xyz"], pts, br["group_idx"], self.idx64,
+                                   int(self.xyz_first), br["grouped"], 0, -1, self.group_max_blocks, st)
 
     def _sa(self, lv, br, cur_xyz, pts, st):
         """one fused (radius, nsample) branch of a set-abstraction level on stream st"""
@@ -358,8 +355,7 @@ class HotPath:
         ev[1].record()
         scratch_idx = torch.empty(self.B, 2, dtype=torch.int32, device=self.device)
         ev[2].record()
-        check(self.L.tgn_furthestsampling_dense(self.B, lv0["N"], 2, ptr(xyz), None, ptr(scratch_idx), None, _lib.FPS_LOCAL_INDEX, st),
-              "fps set-up probe")
+        self.L.tgn_furthestsampling_dense(self.B, lv0["N"], 2, xyz, None, scratch_idx, None, _lib.FPS_LOCAL_INDEX, st)
         ev[3].record()
         cur = xyz
         for i, lv in enumerate(levels):      # everything the groupings need
@@ -390,12 +386,11 @@ class HotPath:
         flags = (_lib.FPS_LOCAL_INDEX | (_lib.FPS_LOW_VALU if (self.phased and i > 0 and self.fps_low_valu) else 0)
                  | (_lib.FPS_TREE_TIES if self.fps_ties == "tree" else 0))
         if not self.fps_prefix:
-            return check(L.tgn_furthestsampling_dense(self.B, lv["N"], lv["S"], ptr(cur_xyz), None, ptr(lv["fps_idx"]),
-                                                      ptr(lv["new_xyz"]), flags, st), "fps")
+            L.tgn_furthestsampling_dense(self.B, lv["N"], lv["S"], cur_xyz, None, lv["fps_idx"], lv["new_xyz"], flags, st)
+            return
         cert_in = levels[i - 1]["cert"] if i > 0 else None   # level i samples level i-1's new_xyz
-        return check(L.tgn_furthestsampling_dense_prefix(self.B, lv["N"], lv["S"], ptr(cur_xyz), None, 0, ptr(lv["fps_idx"]),
-                                                         ptr(lv["new_xyz"]), ptr(cert_in), None, ptr(lv["cert"]),
-                                                         flags, st), "fps")
+        L.tgn_furthestsampling_dense_prefix(self.B, lv["N"], lv["S"], cur_xyz, None, 0, lv["fps_idx"], lv["new_xyz"], cert_in, None, lv["cert"],
+                                            flags, st)
 
     def _run_pipelined(self, xyz, feats, inputs_on_current_stream=True, input_event=None, more=True):
         p = self.step_no & 1
@@ -457,7 +452,7 @@ class HotPath:
                 sg.wait_event(self.ev_ball[p][early - 1])
                 sg.wait_event(self.ev_fps[p][nl - 1])     # ... and by the last FPS level: the end of phase 2, whichever chain is longer
                 if self.plan.get("spacer_us"):
-                    check(self.L.tgn_stream_delay(int(self.plan["spacer_us"]), pg), "stream_delay")
+                    self.L.tgn_stream_delay(int(self.plan["spacer_us"]), pg)
                 for j in range(early, nl):
                     lj = levels[j]
                     self._timed(f"ball_l{j + 1}", lambda: [self._ball(lj, br, clouds[j], pg) for br in lj["branches"]], sg)

@@ -49,15 +49,13 @@ class _TgnOffsetLosses(Function):
     @_fwd
     def forward(ctx, pred_offset, sample_xyz, labels):
         B, _, N = pred_offset.shape
-        L, dev = _lib.lib(), pred_offset.device
+        L, dev = _lib.ops(), pred_offset.device
         counts, cent = crops.label_centroids(sample_xyz, labels, crops.NUM_LABELS)
         losses = torch.empty(3, dtype=torch.float32, device=dev)
         scales = torch.empty(B, _SCALES, dtype=torch.float32, device=dev)
         ws_bytes = L.tgn_offset_loss_workspace_bytes(B, N)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        _lib.check(L.tgn_offset_loss_forward(B, N, _lib.ptr(pred_offset), _lib.ptr(sample_xyz), _lib.ptr(labels), _lib.ptr(counts),
-                                             _lib.ptr(cent), _lib.ptr(losses), _lib.ptr(scales), _lib.ptr(ws), ws_bytes, _lib.stream()),
-                   "tgn_offset_loss_forward")
+        L.tgn_offset_loss_forward(B, N, pred_offset, sample_xyz, labels, counts, cent, losses, scales, ws, ws_bytes, _lib.stream())
         ctx.save_for_backward(pred_offset, sample_xyz, labels, counts, cent, scales)
         return losses[0], losses[1], losses[2]
 
@@ -68,9 +66,7 @@ class _TgnOffsetLosses(Function):
         B, _, N = pred_offset.shape
         g = _grads(g_off, g_dir, g_chamf)
         grad = torch.empty_like(pred_offset)
-        _lib.check(_lib.lib().tgn_offset_loss_backward(B, N, _lib.ptr(pred_offset), _lib.ptr(sample_xyz), _lib.ptr(labels),
-                                                       _lib.ptr(counts), _lib.ptr(cent), _lib.ptr(scales), _lib.ptr(g), _lib.ptr(grad),
-                                                       _lib.stream()), "tgn_offset_loss_backward")
+        _lib.ops().tgn_offset_loss_backward(B, N, pred_offset, sample_xyz, labels, counts, cent, scales, g, grad, _lib.stream())
         return grad, None, None
 
 
@@ -83,15 +79,14 @@ class _CentroidLoss(Function):
     def forward(ctx, pred_offset, sample_xyz, distance, centroid, exists):
         B, _, M = pred_offset.shape
         C = centroid.shape[2]
-        L, dev = _lib.lib(), pred_offset.device
+        L, dev = _lib.ops(), pred_offset.device
         losses = torch.empty(3, dtype=torch.float32, device=dev)
         scales = torch.empty(4, dtype=torch.float32, device=dev)
         rev_arg = torch.empty(B, MAX_CENTROIDS, dtype=torch.int32, device=dev)
         ws_bytes = L.tgn_centroid_loss_workspace_bytes(B)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        _lib.check(L.tgn_centroid_loss_forward(B, M, C, _lib.ptr(pred_offset), _lib.ptr(sample_xyz), _lib.ptr(distance), _lib.ptr(centroid),
-                                               _lib.ptr(exists), _lib.ptr(losses), _lib.ptr(scales), _lib.ptr(rev_arg), _lib.ptr(ws),
-                                               ws_bytes, _lib.stream()), "tgn_centroid_loss_forward")
+        L.tgn_centroid_loss_forward(B, M, C, pred_offset, sample_xyz, distance, centroid, exists, losses, scales, rev_arg, ws, ws_bytes,
+                                    _lib.stream())
         ctx.save_for_backward(pred_offset, sample_xyz, distance, centroid, exists, scales, rev_arg)
         return losses[0], losses[1], losses[2]
 
@@ -102,10 +97,8 @@ class _CentroidLoss(Function):
         B, _, M = pred_offset.shape
         g = _grads(g_dist, g_cent, g_chamf)
         grad_offset, grad_distance = torch.empty_like(pred_offset), torch.empty_like(distance)
-        _lib.check(_lib.lib().tgn_centroid_loss_backward(B, M, centroid.shape[2], _lib.ptr(pred_offset), _lib.ptr(sample_xyz),
-                                                         _lib.ptr(distance), _lib.ptr(centroid), _lib.ptr(exists), _lib.ptr(scales),
-                                                         _lib.ptr(rev_arg), _lib.ptr(g), _lib.ptr(grad_offset), _lib.ptr(grad_distance),
-                                                         _lib.stream()), "tgn_centroid_loss_backward")
+        _lib.ops().tgn_centroid_loss_backward(B, M, centroid.shape[2], pred_offset, sample_xyz, distance, centroid, exists, scales, rev_arg, g,
+                                              grad_offset, grad_distance, _lib.stream())
         return grad_offset, None, grad_distance, None, None
 
 

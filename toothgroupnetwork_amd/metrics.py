@@ -84,8 +84,7 @@ def confusion(gt, sem, ins=None, nlab=MAX_LABELS, offset=None):
     p = s if ins is None else _packed(ins).reshape(-1)
     ins_gt = torch.empty(b, nlab, nlab, dtype=torch.int32, device=dev)
     ins_sem = torch.empty(b, nlab, nlab, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().tgn_seg_confusion(b, n, _lib.ptr(off), _lib.ptr(g), _lib.ptr(s), _lib.ptr(p), nlab, _lib.ptr(ins_gt),
-                                            _lib.ptr(ins_sem), _lib.stream()), "tgn_seg_confusion")
+    _lib.ops().tgn_seg_confusion(b, n, off, g, s, p, nlab, ins_gt, ins_sem, _lib.stream())
     return ins_gt, ins_sem
 
 
@@ -109,8 +108,7 @@ def confusion_from_logits(logits, gt, gt_shift=1):
     x, g = logits.detach().to(torch.float32).contiguous(), _packed(gt)
     ins_gt = torch.empty(B, C, C, dtype=torch.int32, device=x.device)
     ins_sem = torch.empty(B, C, C, dtype=torch.int32, device=x.device)
-    _lib.check(_lib.lib().tgn_seg_confusion_logits(B, C, N, _lib.ptr(x), _lib.ptr(g), int(gt_shift), _lib.ptr(ins_gt), _lib.ptr(ins_sem),
-                                                   _lib.stream()), "tgn_seg_confusion_logits")
+    _lib.ops().tgn_seg_confusion_logits(B, C, N, x, g, int(gt_shift), ins_gt, ins_sem, _lib.stream())
     return ins_gt, ins_sem
 
 
@@ -127,8 +125,7 @@ def _scores_raw(ins_gt, ins_sem, is_half):
     inst = torch.empty(b, dtype=torch.int32, device=dev)
     iou_pi = torch.empty(b, nlab, dtype=torch.float64, device=dev)
     matched = torch.empty(b, nlab, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().tgn_seg_scores(b, nlab, _lib.ptr(a), _lib.ptr(s), 1 if is_half else 0, _lib.ptr(sc), _lib.ptr(inst),
-                                         _lib.ptr(iou_pi), _lib.ptr(matched), _lib.stream()), "tgn_seg_scores")
+    _lib.ops().tgn_seg_scores(b, nlab, a, s, 1 if is_half else 0, sc, inst, iou_pi, matched, _lib.stream())
     return sc, inst, iou_pi, matched
 
 

@@ -26,7 +26,7 @@ import torch.nn.functional as F
 from torch.autograd import Function
 
 from . import _derived, _lib, pointnet2_utils as _U, pointops
-from ._lib import check, lib, ptr, stream
+from ._lib import ops, stream
 from .sa_fused import bn_scale_shift as _bn_scale_shift, pack_first_layer
 
 _fwd = torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
@@ -46,8 +46,7 @@ class _SoftmaxAggregate(Function):
         g = logit.shape[2]
         sm = torch.empty(n, nsample, g, dtype=torch.float32, device=x_v.device)
         out = torch.empty(n, c, dtype=torch.float32, device=x_v.device)
-        check(lib().tgn_pt_softmax_aggregate_forward(n, nsample, c, g, ptr(x_v), ptr(p_r), ptr(logit), ptr(idx), ptr(sm), ptr(out),
-                                                     stream()), "pt_softmax_aggregate fwd")
+        ops().tgn_pt_softmax_aggregate_forward(n, nsample, c, g, x_v, p_r, logit, idx, sm, out, stream())
         ctx.save_for_backward(x_v, p_r, sm, idx)
         return out
 
@@ -61,8 +60,7 @@ class _SoftmaxAggregate(Function):
         g_xv = torch.zeros_like(x_v)
         g_pr = torch.empty_like(p_r)
         g_lg = torch.empty_like(sm)
-        check(lib().tgn_pt_softmax_aggregate_backward(n, nsample, c, g, ptr(x_v), ptr(p_r), ptr(sm), ptr(idx), ptr(grad_out),
-                                                      ptr(g_xv), ptr(g_pr), ptr(g_lg), stream()), "pt_softmax_aggregate bwd")
+        ops().tgn_pt_softmax_aggregate_backward(n, nsample, c, g, x_v, p_r, sm, idx, grad_out, g_xv, g_pr, g_lg, stream())
         return g_xv, g_pr, g_lg, None
 
 
@@ -115,12 +113,12 @@ class _LinearSplitK(Function):
                 # gradient comes out of the same pass
                 gyc, xc = gy2.contiguous(), x2.contiguous()
                 cout, cin = gyc.shape[1], xc.shape[1]
-                nbytes = int(lib().tgn_linear_wgrad_workspace_bytes(rows, cin, cout))
+                nbytes = int(ops().tgn_linear_wgrad_workspace_bytes(rows, cin, cout))
                 ws = torch.empty(nbytes, dtype=torch.uint8, device=gy2.device)
                 gw = torch.empty(cout, cin, dtype=torch.float32, device=gy2.device)
                 want_b = ctx.has_bias and ctx.needs_input_grad[2]
                 gb = torch.empty(cout, dtype=torch.float32, device=gy2.device) if want_b else None
-                check(lib().tgn_linear_wgrad(rows, cin, cout, ptr(xc), ptr(gyc), ptr(gw), ptr(gb), ptr(ws), nbytes, stream()), "linear_wgrad")
+                ops().tgn_linear_wgrad(rows, cin, cout, xc, gyc, gw, gb, ws, nbytes, stream())
                 gw = gw.to(weight.dtype)
                 if want_b:
                     gb = gb.to(weight.dtype)
@@ -158,12 +156,11 @@ class _BNRows(Function):
         wkey = (x.device.index, torch.cuda.current_stream().cuda_stream)
         ws = wss.get(wkey)
         if ws is None:
-            ws = wss[wkey] = torch.zeros(int(lib().tgn_bn_rows_workspace_bytes(C)), dtype=torch.uint8, device=x.device)
+            ws = wss[wkey] = torch.zeros(int(ops().tgn_bn_rows_workspace_bytes(C)), dtype=torch.uint8, device=x.device)
         track = bn.track_running_stats and bn.running_mean is not None
-        check(lib().tgn_bn_rows_forward(rows, C, ptr(x), ptr(weight), ptr(bias), float(bn.eps), float(bn.momentum),
-                                        ptr(bn.running_mean) if track else None, ptr(bn.running_var) if track else None,
-                                        ptr(bn.num_batches_tracked) if track and bn.num_batches_tracked is not None else None,
-                                        int(relu), ptr(y), ptr(mean), ptr(invstd), ptr(ws), stream()), "bn_rows_forward")
+        ops().tgn_bn_rows_forward(rows, C, x, weight, bias, float(bn.eps), float(bn.momentum),
+                                  bn.running_mean if track else None, bn.running_var if track else None,
+                                  bn.num_batches_tracked if track else None, int(relu), y, mean, invstd, ws, stream())
         if track:   # written through raw pointers: tell torch (the fold memo of the eval paths keys on these counters)
             for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked):
                 if t is not None:
@@ -180,8 +177,7 @@ class _BNRows(Function):
         dx = torch.empty_like(x)
         dwb = torch.empty(2, C, dtype=torch.float32, device=x.device)
         dgamma, dbeta = dwb[0], dwb[1]
-        check(lib().tgn_bn_rows_backward(rows, C, ptr(x), ptr(y), ptr(dy), ptr(weight), ptr(mean), ptr(invstd), int(ctx.relu),
-                                         ptr(dx), ptr(dgamma), ptr(dbeta), ptr(ctx.ws), stream()), "bn_rows_backward")
+        ops().tgn_bn_rows_backward(rows, C, x, y, dy, weight, mean, invstd, int(ctx.relu), dx, dgamma, dbeta, ctx.ws, stream())
         return dx, dgamma, dbeta, None, None
 
 
@@ -314,10 +310,8 @@ def pt_attention(p, x_q, x_k, x_v, idx, params, post=None):
     g = params["Ww2"].shape[0]
     out = torch.empty(n, c, dtype=torch.float32, device=x_q.device)
     P = params
-    check(lib().tgn_pt_attention_forward(n, nsample, c, g, ptr(p), ptr(x_q), ptr(x_k), ptr(x_v), ptr(idx), ptr(P["Wp1"]),
-                                         ptr(P["bp1"]), ptr(P["Wp2"]), ptr(P["bp2"]), ptr(P["a1"]), ptr(P["t1"]), ptr(P["Ww1"]),
-                                         ptr(P["bw1"]), ptr(P["Ww2"]), ptr(P["bw2"]), ptr(post[0]) if post else None,
-                                         ptr(post[1]) if post else None, ptr(out), stream()), "pt_attention")
+    ops().tgn_pt_attention_forward(n, nsample, c, g, p, x_q, x_k, x_v, idx, P["Wp1"], P["bp1"], P["Wp2"], P["bp2"], P["a1"], P["t1"], P["Ww1"],
+                                   P["bw1"], P["Ww2"], P["bw2"], post[0] if post else None, post[1] if post else None, out, stream())
     return out
 
 
@@ -428,12 +422,10 @@ class TransitionDown(nn.Module):
                 return f["Wt"], f["Wxs"], f["b"]
             Wt, Wxyz, t = _derived.cached(self, "down", _derived.sources(self.linear, self.bn), c, fold)
             A = torch.empty(n, C1, dtype=torch.float32, device=x.device)
-            L = lib()
-            check(L.tgn_sa_point_transform(n, c, C1, ptr(pointops._f32c(p, "p")), ptr(x.contiguous()), ptr(Wt), ptr(A), stream()),
-                  "sa_point_transform")
+            L = ops()
+            L.tgn_sa_point_transform(n, c, C1, pointops._f32c(p, "p"), x.contiguous(), Wt, A, stream())
             out = torch.empty(m, C1, dtype=torch.float32, device=x.device)
-            check(L.tgn_sa_gather_max(1, n, m, self.nsample, C1, ptr(A), ptr(n_p), ptr(Wxyz), ptr(t),
-                                      ptr(kidx), 0, 1, ptr(out), stream()), "sa_gather_max")
+            L.tgn_sa_gather_max(1, n, m, self.nsample, C1, A, n_p, Wxyz, t, kidx, 0, 1, out, stream())
             return [n_p, out, n_o]
         x = pointops.queryandgroup(self.nsample, p, n_p, x, None, o, n_o, use_xyz=True)  # (m, nsample, 3+c)
         m = x.shape[0]

@@ -27,7 +27,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _derived
-from ._lib import check, lib, ptr, require_cuda, stream
+from ._lib import ops, require_cuda, stream
 from .point_transformer import _bn_scale_shift, _frozen
 
 _ACTS = {"identity": 0, "relu": 1, "leaky_relu": 2}
@@ -89,10 +89,9 @@ def linear_act_max(x, conv, bn, act, slope=0.0):
     x = (x if x.dtype == torch.float32 else x.float()).contiguous()
     Wt, shift = _folded_t(conv, bn)
     out = torch.empty(B, C, dtype=torch.float32, device=x.device)
-    ws_bytes = lib().tgn_linear_act_max_workspace_bytes(B, N, K, C)
+    ws_bytes = ops().tgn_linear_act_max_workspace_bytes(B, N, K, C)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-    check(lib().tgn_linear_act_max(B, N, K, C, ptr(x), ptr(Wt), ptr(shift), _ACTS[act], float(slope), ptr(out), ptr(ws), ws_bytes,
-                                   stream()), "linear_act_max")
+    ops().tgn_linear_act_max(B, N, K, C, x, Wt, shift, _ACTS[act], float(slope), out, ws, ws_bytes, stream())
     return out
 
 

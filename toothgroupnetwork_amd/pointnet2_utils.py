@@ -29,7 +29,7 @@ from torch.autograd import Function
 from . import _derived, _lib, config
 from . import _fps_prefix
 from ._fps_prefix import PrefixBook
-from ._lib import as_int, check, lib, ptr, require_cuda, stream
+from ._lib import as_int, ops, require_cuda, stream
 from .sa_fused import (_f32c, bn_scale_shift, fold_first_layer, fold_second_layer, pad16, sa_all_mlp2_max,  # noqa: F401
                        sa_first_layer, sa_level_max, sa_level_mlp2_max, sa_point_transform, split_point_transform, split_second_layer)
 
@@ -66,7 +66,7 @@ class _SquareDistance3(Function):
             raise RuntimeError(f"square_distance: batch sizes differ ({B} vs {dst.shape[0]})")
         M = dst.shape[1]
         out = torch.empty(B, N, M, dtype=torch.float32, device=src.device)
-        check(lib().tgn_square_distance(B, N, M, ptr(src), ptr(dst), ptr(out), stream()), "square_distance")
+        ops().tgn_square_distance(B, N, M, src, dst, out, stream())
         ctx.save_for_backward(src, dst)
         return out
 
@@ -109,8 +109,7 @@ class _IndexPoints(Function):
         M = idx.numel() // B if B else 0
         out = torch.empty(tuple(idx.shape) + (C,), dtype=torch.float32, device=points.device)
         _lib.begin_index_check()
-        check(lib().tgn_gather_points(B, N, M, C, ptr(points), ptr(idx), int(idx.dtype == torch.int64), ptr(out),
-                                      stream()), "gather_points")
+        ops().tgn_gather_points(B, N, M, C, points, idx, int(idx.dtype == torch.int64), out, stream())
         _lib.raise_on_index_error("index_points")
         ctx.shape = (B, N, M, C)
         ctx.save_for_backward(idx)
@@ -123,8 +122,7 @@ class _IndexPoints(Function):
         B, N, M, C = ctx.shape
         g = g.contiguous().float()
         grad = torch.zeros(B, N, C, dtype=torch.float32, device=g.device)
-        check(lib().tgn_scatter_add_points(B, N, M, C, ptr(g), ptr(idx), int(idx.dtype == torch.int64), ptr(grad),
-                                           stream()), "scatter_add_points")
+        ops().tgn_scatter_add_points(B, N, M, C, g, idx, int(idx.dtype == torch.int64), grad, stream())
         return grad, None
 
 
@@ -182,7 +180,7 @@ def _fps_dense(xyz, npoint, want_coords=False, cuda_compat=False, prefix=False, 
     if nbytes == 0 and B >= 3 * torch.cuda.get_device_properties(xyz.device).multi_processor_count:
         # three or more clouds per CU: the L2-resident form shares a CU between four workgroups and finishes the BATCH sooner
         # (24 000 -> 4096: 10.9 against 12.7 us per scan at 768 scans, 9.7 at 1024; profiles/r06_fps_throughput.txt); same results
-        nbytes = int(lib().tgn_fps_throughput_workspace_bytes(B, N))
+        nbytes = int(ops().tgn_fps_throughput_workspace_bytes(B, N))
         if nbytes:
             ws = torch.empty(nbytes, dtype=torch.uint8, device=xyz.device)
             flags |= _lib.FPS_THROUGHPUT
@@ -190,9 +188,7 @@ def _fps_dense(xyz, npoint, want_coords=False, cuda_compat=False, prefix=False, 
     if use_prefix:
         cert_in, ref = _fps_book.offer((B, N, mode), xyz.device)
         cert_out = torch.empty(B, dtype=torch.int32, device=xyz.device)
-    check(lib().tgn_furthestsampling_dense_prefix(B, N, npoint, ptr(xyz), ptr(ws), nbytes, ptr(idx), ptr(new_xyz),
-                                                  ptr(cert_in), ptr(ref), ptr(cert_out), flags, stream()),
-          "tgn_furthestsampling_dense")
+    ops().tgn_furthestsampling_dense_prefix(B, N, npoint, xyz, ws, nbytes, idx, new_xyz, cert_in, ref, cert_out, flags, stream())
     if use_prefix:
         _fps_book.record((B, npoint, mode), xyz.device, new_xyz, cert_out, shared=want_coords)
     return idx, (new_xyz if want_coords else None)
@@ -262,10 +258,9 @@ def query_ball_point(radius, nsample, xyz, new_xyz):
     # `sqrdists > radius ** 2`: python evaluates radius**2 in double, torch compares in fp32
     r2 = float(torch.tensor(float(radius) ** 2, dtype=torch.float32).item())
     group_idx = torch.empty(B, S, nsample, dtype=torch.int64, device=xyz.device)
-    nbytes = int(lib().tgn_ball_query_workspace_bytes(B, N, S))
+    nbytes = int(ops().tgn_ball_query_workspace_bytes(B, N, S))
     ws = _workspace(nbytes, xyz.device)
-    check(lib().tgn_ball_query(B, N, S, nsample, r2, ptr(xyz), ptr(new_xyz), ptr(group_idx), 1, ptr(ws), nbytes,
-                               stream()), "tgn_ball_query")
+    ops().tgn_ball_query(B, N, S, nsample, r2, xyz, new_xyz, group_idx, 1, ws, nbytes, stream())
     return group_idx
 
 
@@ -281,9 +276,7 @@ class _GroupPoints(Function):
         D = 0 if points is None else points.shape[2]
         out = torch.empty(B, S, K, 3 + D, dtype=torch.float32, device=xyz.device)
         _lib.begin_index_check()
-        check(lib().tgn_group_points(B, N, S, K, D, ptr(xyz), ptr(new_xyz), ptr(points), ptr(idx),
-                                     int(idx.dtype == torch.int64), int(xyz_first), ptr(out), stream()),
-              "group_points")
+        ops().tgn_group_points(B, N, S, K, D, xyz, new_xyz, points, idx, int(idx.dtype == torch.int64), int(xyz_first), out, stream())
         _lib.raise_on_index_error("group_points")
         ctx.dims = (B, N, S, K, D, bool(xyz_first))
         ctx.save_for_backward(idx)
@@ -300,15 +293,13 @@ class _GroupPoints(Function):
         g_xyz = g_new = g_pts = None
         if ctx.needs_input_grad[0]:
             g_xyz = torch.zeros(B, N, 3, dtype=torch.float32, device=g.device)
-            check(lib().tgn_scatter_add_points(B, N, S * K, 3, ptr(g_rel), ptr(idx), is64, ptr(g_xyz), stream()),
-                  "scatter_add_points")
+            ops().tgn_scatter_add_points(B, N, S * K, 3, g_rel, idx, is64, g_xyz, stream())
         if ctx.needs_input_grad[1]:
             g_new = -g_rel.sum(2)
         if D and ctx.needs_input_grad[2]:
             g_f = (g[..., 3:] if xyz_first else g[..., :D]).contiguous()
             g_pts = torch.zeros(B, N, D, dtype=torch.float32, device=g.device)
-            check(lib().tgn_scatter_add_points(B, N, S * K, D, ptr(g_f), ptr(idx), is64, ptr(g_pts), stream()),
-                  "scatter_add_points")
+            ops().tgn_scatter_add_points(B, N, S * K, D, g_f, idx, is64, g_pts, stream())
         return g_xyz, g_new, g_pts, None, None
 
 
@@ -362,7 +353,7 @@ def three_nn(xyz1, xyz2):
     S = xyz2.shape[1]
     dist = torch.empty(B, N, 3, dtype=torch.float32, device=xyz1.device)
     idx = torch.empty(B, N, 3, dtype=torch.int64, device=xyz1.device)
-    check(lib().tgn_three_nn(B, N, S, ptr(xyz1), ptr(xyz2), ptr(dist), ptr(idx), 1, stream()), "three_nn")
+    ops().tgn_three_nn(B, N, S, xyz1, xyz2, dist, idx, 1, stream())
     return dist, idx
 
 
@@ -374,8 +365,7 @@ class _ThreeInterpolate(Function):
         N = dist.shape[1]
         out = torch.empty(B, N, C, dtype=torch.float32, device=points2.device)
         weight = torch.empty(B, N, 3, dtype=torch.float32, device=points2.device)
-        check(lib().tgn_three_interpolate(B, N, S, C, ptr(points2), ptr(dist), ptr(idx), int(idx.dtype == torch.int64),
-                                          ptr(out), ptr(weight), stream()), "three_interpolate")
+        ops().tgn_three_interpolate(B, N, S, C, points2, dist, idx, int(idx.dtype == torch.int64), out, weight, stream())
         ctx.dims = (B, N, S, C)
         ctx.save_for_backward(idx, weight)
         return out
@@ -389,8 +379,7 @@ class _ThreeInterpolate(Function):
         # global row indices into the flattened (B*S, C) support features
         gidx = (idx + (torch.arange(B, device=idx.device, dtype=idx.dtype) * S).view(B, 1, 1)).to(torch.int32)
         grad = torch.zeros(B * S, C, dtype=torch.float32, device=g.device)
-        check(lib().tgn_interpolation_backward(B * N, C, 3, ptr(g), ptr(gidx.contiguous()), ptr(weight), ptr(grad),
-                                               stream()), "interpolation bwd")
+        ops().tgn_interpolation_backward(B * N, C, 3, g, gidx.contiguous(), weight, grad, stream())
         return grad.view(B, S, C), None, None
 
 
@@ -420,8 +409,7 @@ def three_interpolate_add_relu(points2, dist, idx, add=None, relu=False):
         if tuple(add.shape) != (B, N, C):
             raise ValueError(f"three_interpolate_add_relu: add must be ({B}, {N}, {C}), got {tuple(add.shape)}")
     out = add if add is not None else torch.empty(B, N, C, dtype=torch.float32, device=points2.device)
-    check(lib().tgn_three_interpolate_ex(B, N, S, C, ptr(points2), ptr(dist), ptr(idx), int(idx.dtype == torch.int64), ptr(add),
-                                         int(bool(relu)), ptr(out), None, stream()), "three_interpolate_ex")
+    ops().tgn_three_interpolate_ex(B, N, S, C, points2, dist, idx, int(idx.dtype == torch.int64), add, int(bool(relu)), out, None, stream())
     return out
 
 

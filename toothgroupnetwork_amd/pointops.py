@@ -18,7 +18,7 @@ from torch.utils.weak import WeakTensorKeyDictionary
 from . import _lib, config
 from . import _fps_prefix
 from ._fps_prefix import PrefixBook
-from ._lib import as_int, check, lib, ptr, require_cuda, stream
+from ._lib import as_int, ops, require_cuda, stream
 
 _fwd = torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
 _bwd = torch.amp.custom_bwd(device_type="cuda")
@@ -115,9 +115,9 @@ def _max_segment(off_h):
 def fps_workspace(b, n_max, n_total, device):
     """Scratch for clouds that do not fit the register-resident FPS kernels (raw scans): the cell-sorted
     workspace of the large-cloud kernel, or -- above its 262 144-point limit -- the reference's tmp array."""
-    if n_max <= lib().tgn_fps_resident_capacity():
+    if n_max <= ops().tgn_fps_resident_capacity():
         return None, 0
-    nbytes = int(lib().tgn_fps_workspace_bytes(b, n_max))
+    nbytes = int(ops().tgn_fps_workspace_bytes(b, n_max))
     nbytes = max(nbytes, 4 * int(n_total))
     return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
 
@@ -164,9 +164,7 @@ def fps_with_coords(xyz, offset, new_offset, cuda_compat=False, prefix=False):
     if use_prefix:
         cert_in, ref = _fps_book.offer((tuple(off_h), xyz.shape[0], flags), xyz.device)
         cert_out = torch.empty(b, dtype=torch.int32, device=xyz.device)
-    check(lib().tgn_furthestsampling_prefix(b, n_max, ptr(xyz), ptr(offset), ptr(new_offset), ptr(ws), nbytes, ptr(idx),
-                                            ptr(new_xyz), ptr(cert_in), ptr(ref), ptr(cert_out), flags, stream()),
-          "tgn_furthestsampling")
+    ops().tgn_furthestsampling_prefix(b, n_max, xyz, offset, new_offset, ws, nbytes, idx, new_xyz, cert_in, ref, cert_out, flags, stream())
     if use_prefix:
         _fps_book.record((tuple(noff_h), m, flags), xyz.device, new_xyz, cert_out, shared=True)
     return idx, new_xyz
@@ -205,15 +203,13 @@ def _knn_raw(nsample, xyz, new_xyz, offset, new_offset):
     b, n = offset.shape[0], xyz.shape[0]
     if config.cfg.knn_grid and nsample <= 63 and b > 0 and n >= config.cfg.knn_grid_min_points * b:
         # big segments: per-segment grids, a query looks at the cells around it (same result)
-        nbytes = int(lib().tgn_knnquery_grid_workspace_bytes(b, n, m))
+        nbytes = int(ops().tgn_knnquery_grid_workspace_bytes(b, n, m))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=xyz.device) if nbytes else None
-        check(lib().tgn_knnquery_grid(b, n, m, nsample, ptr(xyz), ptr(new_xyz), ptr(offset), ptr(new_offset),
-                                      ptr(idx), ptr(dist2), ptr(ws), nbytes, stream()), "tgn_knnquery")
+        ops().tgn_knnquery_grid(b, n, m, nsample, xyz, new_xyz, offset, new_offset, idx, dist2, ws, nbytes, stream())
         return idx, dist2
-    nbytes = int(lib().tgn_knnquery_workspace_bytes(m))
+    nbytes = int(ops().tgn_knnquery_workspace_bytes(m))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=xyz.device) if nbytes else None
-    check(lib().tgn_knnquery_ws(b, m, nsample, ptr(xyz), ptr(new_xyz), ptr(offset), ptr(new_offset),
-                                ptr(idx), ptr(dist2), ptr(ws), nbytes, stream()), "tgn_knnquery")
+    ops().tgn_knnquery_ws(b, m, nsample, xyz, new_xyz, offset, new_offset, idx, dist2, ws, nbytes, stream())
     return idx, dist2
 
 
@@ -299,7 +295,7 @@ class Grouping(Function):
         _packed(input, "input"), _packed_idx(idx, "idx")
         m, nsample, n, c = idx.shape[0], idx.shape[1], input.shape[0], input.shape[1]
         output = torch.empty(m, nsample, c, dtype=torch.float32, device=input.device)
-        check(lib().tgn_grouping_forward(m, nsample, c, ptr(input), ptr(idx), ptr(output), stream()), "grouping fwd")
+        ops().tgn_grouping_forward(m, nsample, c, input, idx, output, stream())
         ctx.n = n
         ctx.save_for_backward(idx)
         return output
@@ -316,8 +312,7 @@ class Grouping(Function):
         grad_output = grad_output.contiguous().float()
         m, nsample, c = grad_output.shape
         grad_input = torch.zeros(n, c, dtype=torch.float32, device=grad_output.device)
-        check(lib().tgn_grouping_backward(m, nsample, c, ptr(grad_output), ptr(idx), ptr(grad_input), stream()),
-              "grouping bwd")
+        ops().tgn_grouping_backward(m, nsample, c, grad_output, idx, grad_input, stream())
         return grad_input, None
 
 
@@ -348,12 +343,11 @@ class _QueryGroup(Function):
         ctx.save_for_backward(idx)
         if not use_xyz:
             out = torch.empty(m, nsample, c, dtype=torch.float32, device=feat.device)
-            check(lib().tgn_grouping_forward(m, nsample, c, ptr(feat), ptr(idx), ptr(out), stream()), "grouping fwd")
+            ops().tgn_grouping_forward(m, nsample, c, feat, idx, out, stream())
             return out
         out = torch.empty(m, nsample, 3 + c, dtype=torch.float32, device=feat.device)
         # packed layout == dense layout with B=1: rows of new_xyz are the S "centres", K = nsample
-        check(lib().tgn_group_points(1, n, m, nsample, c, ptr(xyz), ptr(new_xyz), ptr(feat), ptr(idx), 0, 1,
-                                     ptr(out), stream()), "group_points")
+        ops().tgn_group_points(1, n, m, nsample, c, xyz, new_xyz, feat, idx, 0, 1, out, stream())
         return out
 
     @staticmethod
@@ -369,15 +363,14 @@ class _QueryGroup(Function):
             g_feat = grad_out[:, :, 3:].contiguous()
             if ctx.needs_input_grad[0]:
                 g_xyz = torch.zeros(n, 3, dtype=torch.float32, device=grad_out.device)
-                check(lib().tgn_grouping_backward(m, nsample, 3, ptr(g_rel), ptr(idx), ptr(g_xyz), stream()),
-                      "grouping bwd")
+                ops().tgn_grouping_backward(m, nsample, 3, g_rel, idx, g_xyz, stream())
             if ctx.needs_input_grad[1]:
                 g_new = -g_rel.sum(1)
         else:
             g_feat = grad_out
         c = g_feat.shape[2]
         g_in = torch.zeros(n, c, dtype=torch.float32, device=grad_out.device)
-        check(lib().tgn_grouping_backward(m, nsample, c, ptr(g_feat), ptr(idx), ptr(g_in), stream()), "grouping bwd")
+        ops().tgn_grouping_backward(m, nsample, c, g_feat, idx, g_in, stream())
         return g_xyz, g_new, g_in, None, None
 
 
@@ -421,8 +414,7 @@ class Subtraction(Function):
         n, c = input1.shape
         nsample = idx.shape[-1]
         output = torch.empty(n, nsample, c, dtype=torch.float32, device=input1.device)
-        check(lib().tgn_subtraction_forward(n, nsample, c, ptr(input1), ptr(input2), ptr(idx), ptr(output), stream()),
-              "subtraction fwd")
+        ops().tgn_subtraction_forward(n, nsample, c, input1, input2, idx, output, stream())
         ctx.n2 = input2.shape[0]
         ctx.save_for_backward(idx)
         return output
@@ -439,8 +431,7 @@ class Subtraction(Function):
         n, nsample, c = grad_output.shape
         grad_input1 = torch.zeros(n, c, dtype=torch.float32, device=grad_output.device)
         grad_input2 = torch.zeros(ctx.n2, c, dtype=torch.float32, device=grad_output.device)
-        check(lib().tgn_subtraction_backward(n, nsample, c, ptr(idx), ptr(grad_output), ptr(grad_input1),
-                                             ptr(grad_input2), stream()), "subtraction bwd")
+        ops().tgn_subtraction_backward(n, nsample, c, idx, grad_output, grad_input1, grad_input2, stream())
         return grad_input1, grad_input2, None
 
 
@@ -465,8 +456,7 @@ class Aggregation(Function):
         n, nsample, c = position.shape
         w_c = weight.shape[-1]
         output = torch.zeros(n, c, dtype=torch.float32, device=input.device)
-        check(lib().tgn_aggregation_forward(n, nsample, c, w_c, ptr(input), ptr(position), ptr(weight), ptr(idx),
-                                            ptr(output), stream()), "aggregation fwd")
+        ops().tgn_aggregation_forward(n, nsample, c, w_c, input, position, weight, idx, output, stream())
         ctx.save_for_backward(input, position, weight, idx)
         return output
 
@@ -484,9 +474,8 @@ class Aggregation(Function):
         grad_input = torch.zeros(input.shape[0], c, dtype=torch.float32, device=grad_output.device)
         grad_position = torch.zeros(n, nsample, c, dtype=torch.float32, device=grad_output.device)
         grad_weight = torch.zeros(n, nsample, w_c, dtype=torch.float32, device=grad_output.device)
-        check(lib().tgn_aggregation_backward(n, nsample, c, w_c, ptr(input), ptr(position), ptr(weight), ptr(idx),
-                                             ptr(grad_output), ptr(grad_input), ptr(grad_position),
-                                             ptr(grad_weight), stream()), "aggregation bwd")
+        ops().tgn_aggregation_backward(n, nsample, c, w_c, input, position, weight, idx, grad_output, grad_input, grad_position, grad_weight,
+                                       stream())
         return grad_input, grad_position, grad_weight, None
 
 
@@ -514,8 +503,7 @@ class _WeightedGather(Function):
         n, k = idx.shape
         m, c = feat.shape
         output = torch.zeros(n, c, dtype=torch.float32, device=feat.device)
-        check(lib().tgn_interpolation_forward(n, c, k, ptr(feat), ptr(idx), ptr(weight), ptr(output), stream()),
-              "interpolation fwd")
+        ops().tgn_interpolation_forward(n, c, k, feat, idx, weight, output, stream())
         ctx.m = m
         ctx.save_for_backward(idx, weight)
         return output
@@ -528,8 +516,7 @@ class _WeightedGather(Function):
         n, c = grad_output.shape
         k = idx.shape[1]
         grad_input = torch.zeros(ctx.m, c, dtype=torch.float32, device=grad_output.device)
-        check(lib().tgn_interpolation_backward(n, c, k, ptr(grad_output), ptr(idx), ptr(weight), ptr(grad_input),
-                                               stream()), "interpolation bwd")
+        ops().tgn_interpolation_backward(n, c, k, grad_output, idx, weight, grad_input, stream())
         return grad_input, None, None
 
 
@@ -560,8 +547,7 @@ class Interpolation(Function):
         weight = _inverse_distance_weights(torch.sqrt(dist2)).contiguous()
         n, c, m = new_xyz.shape[0], input.shape[1], input.shape[0]
         output = torch.zeros(n, c, dtype=torch.float32, device=input.device)
-        check(lib().tgn_interpolation_forward(n, c, k, ptr(input), ptr(idx), ptr(weight), ptr(output), stream()),
-              "interpolation fwd")
+        ops().tgn_interpolation_forward(n, c, k, input, idx, weight, output, stream())
         ctx.m, ctx.k = m, k
         ctx.save_for_backward(idx, weight)
         return output
@@ -576,8 +562,7 @@ class Interpolation(Function):
         grad_output = grad_output.contiguous().float()
         n, c = grad_output.shape
         grad_input = torch.zeros(m, c, dtype=torch.float32, device=grad_output.device)
-        check(lib().tgn_interpolation_backward(n, c, k, ptr(grad_output), ptr(idx), ptr(weight), ptr(grad_input),
-                                               stream()), "interpolation bwd")
+        ops().tgn_interpolation_backward(n, c, k, grad_output, idx, weight, grad_input, stream())
         return None, None, grad_input, None, None, None
 
 

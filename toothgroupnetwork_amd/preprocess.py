@@ -78,7 +78,7 @@ def subdivide_midpoint_device(vertices, normals, triangles, number_of_iterations
     -> the same three for the subdivided mesh, on the current stream.  One host synchronisation per iteration: the number of new
     vertices.  The triangle indices are checked on the device; a bad one raises ValueError after the pass."""
     import torch
-    L = _lib.lib()
+    L = _lib.ops()
     _lib.require_cuda(vertices, normals, triangles)
     v, n, t = vertices.contiguous(), (None if normals is None else normals.contiguous()), triangles.contiguous()
     if v.dtype != torch.float64 or t.dtype != torch.int64 or (n is not None and n.dtype != torch.float64):
@@ -93,8 +93,7 @@ def subdivide_midpoint_device(vertices, normals, triangles, number_of_iterations
         out_n = torch.empty_like(out_v) if n is not None else None
         out_t = torch.empty((4 * nf, 3), dtype=torch.int64, device=v.device)
         count = torch.empty(1, dtype=torch.int32, device=v.device)
-        _lib.check(L.tgn_subdivide_midpoint(nv, nf, _lib.ptr(v), _lib.ptr(n), _lib.ptr(t), _lib.ptr(out_v), _lib.ptr(out_n), _lib.ptr(out_t),
-                                            _lib.ptr(count), _lib.ptr(ws), need, _lib.stream()), "tgn_subdivide_midpoint")
+        L.tgn_subdivide_midpoint(nv, nf, v, n, t, out_v, out_n, out_t, count, ws, need, _lib.stream())
         new = int(count.item())                                  # the one synchronisation of the pass
         if new < 0:
             if -new & 1:
@@ -228,9 +227,9 @@ def load_scan_native(obj_path, json_path, with_xyz32=False, pools=None):
             lv = np.empty((nv.value, 7), dtype=np.float64)
             x32 = np.empty((nv.value, 3), dtype=np.float32) if want32 else None
     except BaseException:
-        L.tgn_scan_take(handle, None, None)
+        L.tgn_scan_take(handle, None, None)     # raw on purpose: a failed release must not mask the exception re-raised here
         raise
-    L.tgn_scan_take(handle, lv.ctypes.data_as(ctypes.c_void_p), x32.ctypes.data_as(ctypes.c_void_p) if x32 is not None else None)
+    _lib.ops().tgn_scan_take(handle, lv.ctypes.data_as(ctypes.c_void_p), x32.ctypes.data_as(ctypes.c_void_p) if x32 is not None else None)
     return lv, str(os.path.basename(obj_path).split(".")[0]), jaw.value.decode("ascii"), x32
 
 

@@ -18,7 +18,7 @@ modules of pointnet2_utils, by HotPath (what bench.py --fused measures), by Tran
 import torch
 
 from . import _derived, _lib, config
-from ._lib import check, lib, ptr, require_cuda, stream
+from ._lib import ops, require_cuda, stream
 
 
 def _f32c(t):
@@ -116,8 +116,8 @@ def fold_second_layer(conv, bn, C1p):
 def split_second_layer(W2f):
     """The bf16 x 3 image of a folded second-layer weight matrix W2f (C1p/8, C2, 8) for tgn_sa_mlp2_max_bf16x3."""
     C1p, C2 = W2f.shape[0] * 8, W2f.shape[1]
-    img = torch.empty(int(lib().tgn_sa_mlp2_split_bytes(C1p, C2)), dtype=torch.uint8, device=W2f.device)
-    check(lib().tgn_sa_mlp2_split_weights(C1p, C2, ptr(W2f), ptr(img), stream()), "sa_mlp2_split_weights")
+    img = torch.empty(int(ops().tgn_sa_mlp2_split_bytes(C1p, C2)), dtype=torch.uint8, device=W2f.device)
+    ops().tgn_sa_mlp2_split_weights(C1p, C2, W2f, img, stream())
     return img
 
 
@@ -144,14 +144,14 @@ def plan_branch(first, second, K, D, *, bf16x3):
                three-way split of both operands, six products; an infinite activation or weight turns into NaN there)."""
     C1 = first["C1"]
     if second is None:
-        direct = bool(lib().tgn_sa_direct_supported(K, D, C1))
+        direct = bool(ops().tgn_sa_direct_supported(K, D, C1))
         return dict(nlayers=1, K=K, D=D, direct=direct, C1p=C1, C_out=C1, W1=first["Wd"] if direct else first["Wxs"], b1=first["b"],
                     Wt=None if direct else first["Wt"], Wts=None)
     W2f, b2 = second
     C1p = pad16(C1)
     if W2f.shape[0] * 8 != C1p:
         raise ValueError(f"plan_branch: second layer packed for {W2f.shape[0] * 8} input channels, the first layer has {C1p}")
-    direct = bool(lib().tgn_sa_mlp2_direct_supported(K, D))
+    direct = bool(ops().tgn_sa_mlp2_direct_supported(K, D))
     Wt = None if direct else _pad_cols(first["Wt"], C1p)
     return dict(nlayers=2, K=K, D=D, direct=direct, C1p=C1p, C_out=b2.shape[0], W1=_pad_cols(first["Wd"] if direct else first["Wxs"], C1p),
                 b1=_pad_cols(first["b"], C1p), Wt=Wt, Wts=split_point_transform(Wt) if (bf16x3 and not direct) else None,
@@ -171,30 +171,28 @@ def _module_plan(convs, bns, K, D, xyz_first, bf16x3):
 def _launch_point_transform(M, D, C1, xyz, points, Wt, Wts, A, st):
     if Wts is not None and M <= 65535 * 128:        # (the bf16 x 3 kernel's grid: one block per 128 rows)
         img, Kp = Wts
-        check(lib().tgn_sa_point_transform_bf16x3(M, D, Kp, C1, ptr(xyz), ptr(points), ptr(img), ptr(A), st), "sa_point_transform_bf16x3")
+        ops().tgn_sa_point_transform_bf16x3(M, D, Kp, C1, xyz, points, img, A, st)
     else:
-        check(lib().tgn_sa_point_transform(M, D, C1, ptr(xyz), ptr(points), ptr(Wt), ptr(A), st), "sa_point_transform")
+        ops().tgn_sa_point_transform(M, D, C1, xyz, points, Wt, A, st)
 
 
 def launch_branch(plan, B, N, S, xyz, new_xyz, points, idx, idx64, out, A, st):
     """One branch of a fused level on stream st: xyz (B,N,3), new_xyz (B,S,3), points (B,N,D) or None, idx (B,S,K) -> out (B,S,C_out)
     (two layers: any row stride).  A: the caller's (B,N,C1p) buffer for the per-point transform, None for a direct plan.  Packed
     fp32 / int32 or int64 (idx64) operands; nothing is allocated, synchronised or checked here."""
-    L, K, D, C1p, W1, b1 = lib(), plan["K"], plan["D"], plan["C1p"], plan["W1"], plan["b1"]
+    L, K, D, C1p, W1, b1 = ops(), plan["K"], plan["D"], plan["C1p"], plan["W1"], plan["b1"]
     if not plan["direct"]:
         _launch_point_transform(B * N, D, C1p, xyz, points, plan["Wt"], plan["Wts"], A, st)
     if plan["nlayers"] == 2 and plan["W2s"] is not None:
-        check(L.tgn_sa_mlp2_max_bf16x3(B, N, S, K, D, C1p, plan["C_out"], ptr(A), ptr(xyz), ptr(points), ptr(new_xyz), ptr(W1), ptr(b1),
-                                       ptr(idx), int(idx64), ptr(plan["W2s"]), ptr(plan["b2"]), ptr(out), out.stride(1), st), "sa_mlp2_max_bf16x3")
+        L.tgn_sa_mlp2_max_bf16x3(B, N, S, K, D, C1p, plan["C_out"], A, xyz, points, new_xyz, W1, b1, idx, int(idx64), plan["W2s"], plan["b2"],
+                                 out, out.stride(1), st)
     elif plan["nlayers"] == 2:
-        check(L.tgn_sa_mlp2_max(B, N, S, K, D, C1p, plan["C_out"], ptr(A), ptr(xyz), ptr(points), ptr(new_xyz), ptr(W1), ptr(b1),
-                                ptr(idx), int(idx64), ptr(plan["W2f"]), ptr(plan["b2"]), ptr(out), out.stride(1), st), "sa_mlp2_max")
+        L.tgn_sa_mlp2_max(B, N, S, K, D, C1p, plan["C_out"], A, xyz, points, new_xyz, W1, b1, idx, int(idx64), plan["W2f"], plan["b2"], out,
+                          out.stride(1), st)
     elif plan["direct"]:
-        check(L.tgn_sa_direct_max(B, N, S, K, D, C1p, ptr(xyz), ptr(new_xyz), ptr(points), ptr(W1), ptr(b1), ptr(idx), int(idx64), 1,
-                                  ptr(out), st), "sa_direct_max")
+        L.tgn_sa_direct_max(B, N, S, K, D, C1p, xyz, new_xyz, points, W1, b1, idx, int(idx64), 1, out, st)
     else:
-        check(L.tgn_sa_gather_max(B, N, S, K, C1p, ptr(A), ptr(new_xyz), ptr(W1), ptr(b1), ptr(idx), int(idx64), 1, ptr(out), st),
-              "sa_gather_max")
+        L.tgn_sa_gather_max(B, N, S, K, C1p, A, new_xyz, W1, b1, idx, int(idx64), 1, out, st)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -269,8 +267,7 @@ def sa_first_layer(xyz, new_xyz, points, idx, conv, bn, xyz_first, reduce_max=Fa
     A = sa_point_transform(xyz, points, f["Wt"])
     out = torch.empty(B, S, K, f["C1"], dtype=torch.float32, device=xyz.device)
     _lib.begin_index_check()
-    check(lib().tgn_sa_gather_act(B, N, S, K, f["C1"], ptr(A), ptr(new_xyz), ptr(f["Wxs"]), ptr(f["b"]), ptr(idx),
-                                  int(idx.dtype == torch.int64), 1, ptr(out), stream()), "sa_gather_act")
+    ops().tgn_sa_gather_act(B, N, S, K, f["C1"], A, new_xyz, f["Wxs"], f["b"], idx, int(idx.dtype == torch.int64), 1, out, stream())
     _lib.raise_on_index_error("set abstraction (grouping)")
     return out
 
@@ -284,13 +281,13 @@ def sa_all_mlp2_max(xyz, points, convs, bns):
     xyz, _, points, _ = _sa_operands(xyz, None, points, None)
     B, N, _ = xyz.shape
     D = 0 if points is None else points.shape[2]
-    L = lib()
+    L = ops()
     plan = _module_plan(list(convs[:2]), list(bns[:2]), 64, D, True, False)     # (its "groups" are chunks of at most 64 points)
     C1p, C2 = plan["C1p"], plan["C_out"]
     out = torch.empty(B, C2, dtype=torch.float32, device=xyz.device)
     chunks = int(L.tgn_sa_all_chunks(N))
     part = torch.empty(B, chunks, C2, dtype=torch.float32, device=xyz.device) if chunks > 1 else None
     A1 = None if plan["direct"] else sa_point_transform(xyz, points, plan["Wt"])
-    check(L.tgn_sa_all_mlp2_max(B, N, D, C1p, C2, ptr(A1), ptr(xyz), ptr(points), ptr(plan["W1"] if plan["direct"] else None), ptr(plan["b1"]),
-                                ptr(plan["W2f"]), ptr(plan["b2"]), ptr(part), ptr(out), C2, stream()), "sa_all_mlp2_max")
+    L.tgn_sa_all_mlp2_max(B, N, D, C1p, C2, A1, xyz, points, plan["W1"] if plan["direct"] else None, plan["b1"], plan["W2f"], plan["b2"], part,
+                          out, C2, stream())
     return out

@@ -51,8 +51,7 @@ def centroid_proposals(l3_xyz, offset, dist, threshold=THRESHOLD):
     dev = l3_xyz.device
     moved = torch.empty(B * M, 3, dtype=torch.float32, device=dev)
     counts = torch.empty(B, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().tgn_tsg_proposals(B, M, _lib.ptr(l3_xyz), _lib.ptr(offset), _lib.ptr(dist), threshold, _lib.ptr(moved),
-                                            _lib.ptr(counts), _lib.stream()), "tgn_tsg_proposals")
+    _lib.ops().tgn_tsg_proposals(B, M, l3_xyz, offset, dist, threshold, moved, counts, _lib.stream())
     counts = counts.cpu().tolist()                                                            # the synchronisation
     return moved[:sum(counts)], counts
 
@@ -131,9 +130,7 @@ def crop_features(feats, l0_points, centres, k=CROP_K, labels=None):
     idx = _crops.crop_knn(x, scan, cent, k)
     out = torch.empty(T, 3 + Cf + 1, k, dtype=torch.float32, device=dev)
     crop_lab = torch.empty(T, 1, k, dtype=torch.int64, device=dev) if lab is not None else None
-    _lib.check(_lib.lib().tgn_tsg_crop_features(B, N, C, Cf, T, k, _lib.ptr(x), _lib.ptr(f) if Cf else None, _lib.ptr(scan),
-                                                _lib.ptr(cent), _lib.ptr(idx), _lib.ptr(lab), _lib.ptr(out), _lib.ptr(crop_lab),
-                                                _lib.stream()), "tgn_tsg_crop_features")
+    _lib.ops().tgn_tsg_crop_features(B, N, C, Cf, T, k, x, f if Cf else None, scan, cent, idx, lab, out, crop_lab, _lib.stream())
     if differentiable:
         flat = (scan.to(torch.int64)[:, None] * N + idx).reshape(-1)                           # rows of the (B * N, Cf) features
         rows = l0_points.permute(0, 2, 1).reshape(B * N, -1).index_select(0, flat)
@@ -175,10 +172,9 @@ def paint_labels(nn_crop_indexes, pd_2, id_pred, n_points):
     ids = id_pred.detach().argmax(dim=1).to(torch.int64).contiguous()
     scan = _crops.scan_ids(per_scan, dev)
     out = torch.empty(B, n_points, dtype=torch.int64, device=dev)
-    L, st = _lib.lib(), _lib.stream()
-    _lib.check(L.tgn_clear_index_error(st), "tgn_clear_index_error")
-    _lib.check(L.tgn_tsg_paint(B, n_points, T, k, _lib.ptr(scan), _lib.ptr(idx), _lib.ptr(mask), _lib.ptr(ids), _lib.ptr(out), st),
-               "tgn_tsg_paint")
+    L, st = _lib.ops(), _lib.stream()
+    L.tgn_clear_index_error(st)
+    L.tgn_tsg_paint(B, n_points, T, k, scan, idx, mask, ids, out, st)
     if L.tgn_take_index_error(st) & _lib.INDEX_ERROR_CROP:
         raise IndexError(f"paint_labels: a crop index outside [0, {n_points})")
     return out
