@@ -91,7 +91,7 @@ void furthestsampling_cuda_launcher(int b, int n, const float *xyz, const int *o
 /* knnquery/knnquery_cuda_kernel.h:13 ; dist2 = squared distances, ascending */
 void knnquery_cuda_launcher(int m, int nsample, const float *xyz, const float *new_xyz, const int *offset,
                             const int *new_offset, int *idx, float *dist2);
-/* grouping/grouping_cuda_kernel.h:14-15 */
+/* grouping/grouping_cuda_kernel.h:14-15 ; grad_input (n,c) pre-zeroed, accumulated into */
 void grouping_forward_cuda_launcher(int m, int nsample, int c, const float *input, const int *idx, float *output);
 void grouping_backward_cuda_launcher(int m, int nsample, int c, const float *grad_output, const int *idx,
                                      float *grad_input);
@@ -100,12 +100,13 @@ void interpolation_forward_cuda_launcher(int n, int c, int k, const float *input
                                          const float *weight, float *output);
 void interpolation_backward_cuda_launcher(int n, int c, int k, const float *grad_output, const int *idx,
                                           const float *weight, float *grad_input);
-/* subtraction/subtraction_cuda_kernel.h:14-15 */
+/* subtraction/subtraction_cuda_kernel.h:14-15 ; grad_input1 / grad_input2 (n,c) pre-zeroed, accumulated into */
 void subtraction_forward_cuda_launcher(int n, int nsample, int c, const float *input1, const float *input2,
                                        const int *idx, float *output);
 void subtraction_backward_cuda_launcher(int n, int nsample, int c, const int *idx, const float *grad_output,
                                         float *grad_input1, float *grad_input2);
-/* aggregation/aggregation_cuda_kernel.h:14-15 */
+/* aggregation/aggregation_cuda_kernel.h:14-15 ; output (n,c) and the three gradients pre-zeroed: the kernels add to what they
+ * find there, as the reference's do (aggregation_cuda_kernel.cu:18,35-37) */
 void aggregation_forward_cuda_launcher(int n, int nsample, int c, int w_c, const float *input,
                                        const float *position, const float *weight, const int *idx, float *output);
 void aggregation_backward_cuda_launcher(int n, int nsample, int c, int w_c, const float *input,
@@ -119,7 +120,7 @@ void aggregation_backward_cuda_launcher(int n, int nsample, int c, int w_c, cons
 /*
  * Farthest point sampling over b packed clouds (pointops.py:10-27).  n_max = largest cloud.
  * tmp may be NULL unless a cloud exceeds tgn_fps_resident_capacity() points (then it must hold
- * offset[b-1] floats; contents on entry are ignored).  new_xyz (m,3) is optional (NULL to skip): the
+ * offset[b-1] floats; contents on entry are ignored; the dense form: B * N floats).  new_xyz (m,3) is optional (NULL to skip): the
  * sampled coordinates, i.e. xyz[idx] (pointnet2_utils.py:276 / blocks.py:70).
  */
 int tgn_furthestsampling(int b, int n_max, const float *xyz, const int *offset, const int *new_offset,
@@ -592,7 +593,8 @@ int tgn_centroid_loss_backward(int b, int m, int c, const float *offset, const f
  *     point-major, idx (B, N, K) int64, W2 (64, 64) float32 (out, in) row-major, b2 (64), lrelu = LeakyReLU(0.2).  The second layer
  *     runs on fp32 MFMA (exact fp32 products, fp32 accumulation).
  *   tgn_edgeconv1_max: out[b, coff + c, i] = max_{r < K} lrelu(P[b, idx[b,i,r], c] + Q[b, i, c]), the one-layer level.
- *   Both: out (B, *, N) float32 channel-first with batch stride ostride >= (coff + 64) * N floats; 1 <= K <= 32.  An index outside
+ *   Both: out (B, *, N) float32 channel-first with batch stride ostride >= (coff + 64) * N floats, a buffer of at least
+ *   (B - 1) * ostride + (coff + 64) * N floats; only channels coff .. coff + 63 of every scan are written; 1 <= K <= 32.  An index outside
  *   [0, N) reads point 0 and latches bit 1 of the stream's error word (tgn_take_index_error).
  */
 size_t tgn_feature_knn_workspace_bytes(int B, int N, int k);

@@ -20,10 +20,10 @@ import numpy as np
 import pytest
 import torch
 
+from arena import CANARY, CANARY_B, GUARD, Arena  # noqa: F401  (tests/arena.py)
+
 pytestmark = pytest.mark.gpu
 
-CANARY = 0xA5
-GUARD = 64 * 1024
 T_STEPS = 6        # steps issued back to back per round (both parity sets are inspected: steps T-2 and T-1)
 ROUNDS = 5         # fresh HotPath objects per case: fixed, never "until it fails"
 SEEDS = (5, 105)   # synth.scan_batch seeds scan i with seed + i: two disjoint batches of 8
@@ -34,65 +34,6 @@ PAIRS = 4          # (FPS, set-abstraction) launch pairs per case of group b, ev
 
 def T(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-# ---------------------------------------------------------------------------------------------------------------------------
-# the arena
-# ---------------------------------------------------------------------------------------------------------------------------
-class Arena:
-    """One uint8 allocation filled with CANARY; every buffer a kernel sees is a view into it, with GUARD bytes of canary in front
-    of the first, between any two and behind the last.  add() before build(); check() after the launches."""
-
-    def __init__(self):
-        self.specs, self.total, self.buf, self.snap = [], GUARD, None, None
-
-    def add(self, name, like=None, shape=None, dtype=None, out=False):
-        """like: a tensor whose contents the buffer starts with (an input, or an output the caller wants pre-filled);
-        shape/dtype: a buffer left full of canary bytes.  out=True: the launches may write it."""
-        shape = tuple(like.shape) if like is not None else tuple(shape)
-        dtype = like.dtype if like is not None else dtype
-        nbytes = int(np.prod(shape, dtype=np.int64)) * torch.empty((), dtype=dtype).element_size()
-        spec = dict(name=name, off=self.total, nbytes=nbytes, shape=shape, dtype=dtype, like=like, out=out)
-        self.specs.append(spec)
-        self.total += (nbytes + 255) // 256 * 256 + GUARD     # 256-byte aligned starts (the kernels want 16)
-        return len(self.specs) - 1
-
-    def build(self, dev):
-        self.buf = torch.full((self.total,), CANARY, dtype=torch.uint8, device=dev)
-        views = []
-        for s in self.specs:
-            v = self.buf[s["off"]:s["off"] + s["nbytes"]].view(s["dtype"]).view(s["shape"])
-            if s["like"] is not None:
-                v.copy_(s["like"])
-            s["view"] = v
-            views.append(v)
-        self.snap = self.buf.clone()
-        return views
-
-    def reset_outputs(self):
-        """refill every output with the bytes it had after build()"""
-        for s in self.specs:
-            if s["out"]:
-                self.buf[s["off"]:s["off"] + s["nbytes"]].copy_(self.snap[s["off"]:s["off"] + s["nbytes"]])
-
-    def check(self, what):
-        """every byte that is not inside a declared output -- guard bands, inputs, weights -- is what it was after build()"""
-        changed = self.buf != self.snap
-        for s in self.specs:
-            if s["out"]:
-                changed[s["off"]:s["off"] + s["nbytes"]] = False
-        n = int(changed.sum())
-        if n == 0:
-            return
-        first = int(torch.nonzero(changed)[0])
-        last = int(torch.nonzero(changed)[-1])
-        where = "the leading guard band"
-        for s in self.specs:
-            if first >= s["off"]:
-                where = (f"{s['name']} at byte {first - s['off']} of {s['nbytes']}" if first < s["off"] + s["nbytes"]
-                         else f"the guard band {first - s['off'] - s['nbytes']} bytes behind {s['name']}")
-        raise AssertionError(f"{what}: {n} bytes outside the outputs changed, arena offsets {first}..{last}; the first is in {where} "
-                             f"(now {int(self.buf[first]):#x}, was {int(self.snap[first]):#x})")
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -312,18 +253,29 @@ ALONE_SHAPES = [(700, 50, 7, 13, [20, 36]), (640, 33, 36, 200, [72, 100]), (300,
                 (900, 100, 16, 6, [64]), (700, 50, 64, 13, [256]), (500, 60, 7, 61, [100]), (4099, 129, 32, 125, [208])]
 
 
+def _same_bytes(got, want, what):
+    """a run under CANARY against the same run under CANARY_B: a guard value that reached an output, or an element nobody wrote,
+    differs between the two"""
+    for name in got:
+        assert torch.equal(got[name], want[name]), f"{what}: {name} differs between the arena fills {CANARY:#x} and {CANARY_B:#x}"
+
+
 def _run_alone_in_arena(dev, ops, what):
-    ar = Arena()
-    h = _branch_into_arena(ar, ops)
-    views = ar.build(dev)
-    launch, v = _arena_launcher(ops, h, views)
-    from toothgroupnetwork_amd import _lib
-    launch(_lib.stream())
-    torch.cuda.synchronize()
-    ar.check(what)
-    out, A = _unguarded(ops)
-    assert torch.equal(v["out"], out), what + ": out differs from the unguarded call"
-    assert A is None or torch.equal(v["A"], A), what + ": A differs from the unguarded call"
+    by_fill = {}
+    for fill in (CANARY, CANARY_B):
+        ar = Arena(fill)
+        h = _branch_into_arena(ar, ops)
+        views = ar.build(dev)
+        launch, v = _arena_launcher(ops, h, views)
+        from toothgroupnetwork_amd import _lib
+        launch(_lib.stream())
+        torch.cuda.synchronize()
+        ar.check(what)
+        out, A = _unguarded(ops)
+        assert torch.equal(v["out"], out), what + ": out differs from the unguarded call"
+        assert A is None or torch.equal(v["A"], A), what + ": A differs from the unguarded call"
+        by_fill[fill] = ar.out_bytes()
+    _same_bytes(by_fill[CANARY], by_fill[CANARY_B], what)
 
 
 # (one-layer plans have no bf16x3 form)
@@ -363,17 +315,21 @@ def test_point_transform_writes_only_A(dev, M, D, C1, bf16x3):
     pts = torch.randn(1, M, D, generator=g).to(dev) if D else None
     Wt = (torch.randn(D + 3, C1, generator=g) / (D + 3) ** 0.5).to(dev)
     Wts = F.split_point_transform(Wt) if bf16x3 else None
-    ar = Arena()
-    hA = ar.add("A", shape=(1, M, C1), dtype=torch.float32, out=True)
-    hx, hW = ar.add("xyz", like=xyz), ar.add("Wt", like=Wt)
-    hp = ar.add("points", like=pts) if D else None
-    hs = ar.add("Wts", like=Wts[0]) if bf16x3 else None
-    views = ar.build(dev)
-    F._launch_point_transform(M, D, C1, views[hx], views[hp] if D else None, views[hW], (views[hs], Wts[1]) if bf16x3 else None, views[hA],
-                              _lib.stream())
-    torch.cuda.synchronize()
-    ar.check(f"point transform ({M},{D},{C1}) bf16x3={bf16x3}")
-    assert torch.equal(views[hA], F.sa_point_transform(xyz, pts, Wt, Wts))
+    by_fill = {}
+    for fill in (CANARY, CANARY_B):
+        ar = Arena(fill)
+        hA = ar.add("A", shape=(1, M, C1), dtype=torch.float32, out=True)
+        hx, hW = ar.add("xyz", like=xyz), ar.add("Wt", like=Wt)
+        hp = ar.add("points", like=pts) if D else None
+        hs = ar.add("Wts", like=Wts[0]) if bf16x3 else None
+        views = ar.build(dev)
+        F._launch_point_transform(M, D, C1, views[hx], views[hp] if D else None, views[hW], (views[hs], Wts[1]) if bf16x3 else None,
+                                  views[hA], _lib.stream())
+        torch.cuda.synchronize()
+        ar.check(f"point transform ({M},{D},{C1}) bf16x3={bf16x3}")
+        assert torch.equal(views[hA], F.sa_point_transform(xyz, pts, Wt, Wts))
+        by_fill[fill] = ar.out_bytes()
+    _same_bytes(by_fill[CANARY], by_fill[CANARY_B], f"point transform ({M},{D},{C1}) bf16x3={bf16x3}")
 
 
 @pytest.mark.parametrize("N", [33, 65, 257, 1000])
@@ -394,16 +350,21 @@ def test_group_all_writes_only_its_outputs(dev, N, D, C1, C2):
         L = _lib.lib()
         chunks = int(L.tgn_sa_all_chunks(N))
         A1 = None if plan["direct"] else F.sa_point_transform(xyz, pts, plan["Wt"])
-        ar = Arena()
-        h_out = ar.add("out", shape=(B, C2), dtype=torch.float32, out=True)
-        h_in = {k: ar.add(k, like=t) for k, t in (("xyz", xyz), ("points", pts), ("b1", plan["b1"]), ("W2f", plan["W2f"]), ("b2", plan["b2"]))}
-        h_w = ar.add("A1", like=A1) if A1 is not None else ar.add("Wd", like=plan["W1"])
-        h_part = ar.add("part", shape=(B, chunks, C2), dtype=torch.float32, out=True) if chunks > 1 else None
-        v = ar.build(dev)
-        _lib.check(L.tgn_sa_all_mlp2_max(B, N, D, plan["C1p"], C2, ptr(v[h_w]) if A1 is not None else None, ptr(v[h_in["xyz"]]),
-                                         ptr(v[h_in["points"]]), None if A1 is not None else ptr(v[h_w]), ptr(v[h_in["b1"]]),
-                                         ptr(v[h_in["W2f"]]), ptr(v[h_in["b2"]]), ptr(v[h_part]) if chunks > 1 else None, ptr(v[h_out]), C2,
-                                         _lib.stream()), "sa_all_mlp2_max")
-        torch.cuda.synchronize()
-    ar.check(f"group_all N={N} D={D} [{C1}, {C2}]")
-    assert torch.equal(v[h_out], want)
+        by_fill = {}
+        for fill in (CANARY, CANARY_B):
+            ar = Arena(fill)
+            h_out = ar.add("out", shape=(B, C2), dtype=torch.float32, out=True)
+            h_in = {k: ar.add(k, like=t) for k, t in (("xyz", xyz), ("points", pts), ("b1", plan["b1"]), ("W2f", plan["W2f"]),
+                                                      ("b2", plan["b2"]))}
+            h_w = ar.add("A1", like=A1) if A1 is not None else ar.add("Wd", like=plan["W1"])
+            h_part = ar.add("part", shape=(B, chunks, C2), dtype=torch.float32, out=True) if chunks > 1 else None
+            v = ar.build(dev)
+            _lib.check(L.tgn_sa_all_mlp2_max(B, N, D, plan["C1p"], C2, ptr(v[h_w]) if A1 is not None else None, ptr(v[h_in["xyz"]]),
+                                             ptr(v[h_in["points"]]), None if A1 is not None else ptr(v[h_w]), ptr(v[h_in["b1"]]),
+                                             ptr(v[h_in["W2f"]]), ptr(v[h_in["b2"]]), ptr(v[h_part]) if chunks > 1 else None,
+                                             ptr(v[h_out]), C2, _lib.stream()), "sa_all_mlp2_max")
+            torch.cuda.synchronize()
+            ar.check(f"group_all N={N} D={D} [{C1}, {C2}]")
+            assert torch.equal(v[h_out], want)
+            by_fill[fill] = ar.out_bytes()
+    _same_bytes(by_fill[CANARY], by_fill[CANARY_B], f"group_all N={N} D={D} [{C1}, {C2}]")
