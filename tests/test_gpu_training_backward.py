@@ -356,7 +356,7 @@ def test_block_without_parameter_gradients_takes_the_branch_frozen_selects(dev, 
     layer takes the fused eval kernel (tgn_pt_attention_forward) unless the stage is one of the deep ones, where it keeps the
     composition. Either way the output equals the same block's training composition (parameters requiring grad, BN in eval) to
     fp32 rounding."""
-    from toothgroupnetwork_amd import point_transformer as PT
+    from toothgroupnetwork_amd import fold, point_transformer as PT
     layer, bn2, p, x = _stage(dev, n, c, ns, seed=n % 53 + c)
     torch.manual_seed(n)
     blk = PT.PointTransformerBlock(c, c, 8, ns)
@@ -381,7 +381,7 @@ def test_block_without_parameter_gradients_takes_the_branch_frozen_selects(dev, 
         assert calls == {"fused": 0, "tail": 1} and y_train.requires_grad
         for q in blk.parameters():
             q.requires_grad_(False)
-        assert PT._frozen(blk.transformer2, p, x)
+        assert fold.frozen(blk.transformer2, p, x)
         y_frozen = blk([p, x, o])[1]
     assert not y_frozen.requires_grad
     assert calls == ({"fused": 1, "tail": 1} if fused else {"fused": 0, "tail": 2}), calls

@@ -226,7 +226,7 @@ def test_derived_operand_memo_follows_the_parameters():
     (optimiser step, load_state_dict, BatchNorm statistics), replaced, or the shape parameters of the derivation change."""
     import torch
     import torch.nn as nn
-    from toothgroupnetwork_amd import _derived, point_transformer as PT
+    from toothgroupnetwork_amd import _derived, fold, point_transformer as PT, pointnet
     lin, bn = nn.Linear(8, 5, bias=False), nn.BatchNorm1d(5).eval()
     with torch.no_grad():
         bn.running_mean.normal_()
@@ -234,18 +234,37 @@ def test_derived_operand_memo_follows_the_parameters():
         bn.weight.normal_()
         bn.bias.normal_()
         x = torch.randn(11, 8)
-        W, b = PT.folded_linear(lin, bn)
+        W, b = fold.affine(lin, bn)
         assert torch.allclose(torch.nn.functional.linear(x, W, b), bn(lin(x)), atol=1e-6)
-        assert PT.folded_linear(lin, bn)[0] is W                               # hit
+        assert fold.affine(lin, bn)[0] is W                               # hit
         bn.running_mean.add_(1.0)                                              # in-place write: version counter
-        W2, b2 = PT.folded_linear(lin, bn)
+        W2, b2 = fold.affine(lin, bn)
         assert W2 is not W and torch.allclose(torch.nn.functional.linear(x, W2, b2), bn(lin(x)), atol=1e-6)
         lin.load_state_dict({"weight": torch.randn(5, 8)})                     # copy_ into the parameter
-        W3, b3 = PT.folded_linear(lin, bn)
+        W3, b3 = fold.affine(lin, bn)
         assert W3 is not W2 and torch.allclose(torch.nn.functional.linear(x, W3, b3), bn(lin(x)), atol=1e-6)
         lin.weight = nn.Parameter(lin.weight.detach().clone() * 2)             # replaced: identity
-        W4, b4 = PT.folded_linear(lin, bn)
+        W4, b4 = fold.affine(lin, bn)
         assert W4 is not W3 and torch.allclose(torch.nn.functional.linear(x, W4, b4), bn(lin(x)), atol=1e-5)
+        s, t = fold.scale_shift(bn)
+        assert torch.allclose(x[:, :5] * s + t, bn(x[:, :5]), atol=1e-5)
+        assert fold.scale_shift(bn)[0] is s and fold.affine(lin, bn)[0] is W4  # hits; a write to the weight leaves scale_shift alone
+        lin.weight.mul_(0.5)
+        assert fold.scale_shift(bn)[0] is s and fold.affine(lin, bn)[0] is not W4
+        bn.running_var.mul_(2.0)
+        s2, t2 = fold.scale_shift(bn)
+        assert s2 is not s and torch.allclose(x[:, :5] * s2 + t2, bn(x[:, :5]), atol=1e-5)
+        # a layout memo on top of fold.affine has its own sources: a write to the statistics underneath rebuilds it
+        conv, cbn = nn.Conv1d(8, 5, 1), nn.BatchNorm1d(5).eval()
+        xc = x.t()[None]                                                       # (1, 8, 11)
+        Wt, ct = pointnet._folded_t(conv, cbn)
+        assert pointnet._folded_t(conv, cbn)[0] is Wt
+        assert torch.allclose((Wt.t() @ xc[0] + ct[:, None])[None], cbn(conv(xc)), atol=1e-5)
+        cbn.running_mean.add_(1.0)
+        cbn.running_var.mul_(3.0)
+        Wt2, ct2 = pointnet._folded_t(conv, cbn)
+        assert Wt2 is not Wt and pointnet._folded_t(conv, cbn)[0] is Wt2
+        assert torch.allclose((Wt2.t() @ xc[0] + ct2[:, None])[None], cbn(conv(xc)), atol=1e-5)
     calls = []
     build = lambda: calls.append(1) or len(calls)
     assert _derived.cached(bn, "t", [bn.weight], 3, build) == 1 and _derived.cached(bn, "t", [bn.weight], 3, build) == 1

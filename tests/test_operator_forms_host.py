@@ -107,19 +107,19 @@ def test_form_builders():
 
 
 def test_normalisers_of_the_packed_operators():
-    """pointops._f32c / _idx32c on the CPU: what they return, and that a non-floating feature tensor is a TypeError"""
-    from toothgroupnetwork_amd import pointops as P
+    """_lib.f32c / idx32c on the CPU: what they return, and that a non-floating feature tensor is a TypeError"""
+    from toothgroupnetwork_amd import _lib as L, pointops as P
     t = T.q16(T.gen_for("norm"), 6, 4)
-    assert P._f32c(t, "x") is t
+    assert L.f32c(t, "x") is t
     for form in ("offset", "strided_t", "strided_col", "f64", "f16", "bf16"):
-        v = P._f32c(T.float_form(t, form), "x")
+        v = L.f32c(T.float_form(t, form), "x")
         assert v.dtype == torch.float32 and v.is_contiguous() and torch.equal(v, t)
     with pytest.raises(TypeError, match="feat"):
-        P._f32c(torch.zeros(3, 2, dtype=torch.int64), "feat")
+        L.f32c(torch.zeros(3, 2, dtype=torch.int64), "feat")
     with pytest.raises(TypeError, match="idx"):
-        P._idx32c(torch.zeros(3, 2), "idx")
+        L.idx32c(torch.zeros(3, 2), "idx")
     i = torch.arange(6).view(3, 2)
-    assert P._idx32c(i, "idx").dtype == torch.int32 and P._idx32c(T.index_form(i, "strided"), "idx").is_contiguous()
+    assert L.idx32c(i, "idx").dtype == torch.int32 and L.idx32c(T.index_form(i, "strided"), "idx").is_contiguous()
     with pytest.raises(ValueError, match="input"):
         P._packed(t.double(), "input")
     with pytest.raises(ValueError, match="input"):

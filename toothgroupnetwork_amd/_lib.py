@@ -310,6 +310,31 @@ def require_cuda(*tensors):
                 "there is deliberately no CPU fallback -- the CPU restatement lives in oracle/ and is test-only.")
 
 
+def f32c(t, what="tensor"):
+    """What every float tensor argument goes through on its way to a kernel (the kernels read packed fp32 rows): any floating dtype,
+    any strides, any storage offset in; float32 and contiguous out -- the same tensor when it already is.  Differentiable; applied in
+    the public functions, outside the autograd Functions, so that gradients come back in the caller's dtype and layout."""
+    if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+        raise TypeError(f"{what} must be a floating-point tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    t = t if t.dtype == torch.float32 else t.float()
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def idx32c(t, what):
+    """An index argument of the packed-batch operators, which read int32: any integer width and strides in, packed int32 out."""
+    if not isinstance(t, torch.Tensor) or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+        raise TypeError(f"{what} must be an integer tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    return (t if t.dtype == torch.int32 else t.to(torch.int32)).contiguous()
+
+
+def idx_packed(idx):
+    """Index tensors reach the set-abstraction kernels as packed int64 or int32 (a flag tells which); any other integer width is
+    widened."""
+    if idx.dtype not in (torch.int64, torch.int32):
+        idx = idx.long()
+    return idx if idx.is_contiguous() else idx.contiguous()
+
+
 class _Pointer:
     """What ops() takes where the C function takes a pointer or a stream: a CUDA tensor (its data_ptr(); strided views are
     meant to pass, their stride is an argument of its own), None (NULL) or a c_void_p (a stream, a host array's

@@ -13,9 +13,9 @@ a state_dict-compatible mirror of DGCnnModule.
 import torch
 import torch.nn as nn
 
-from . import _derived, _lib
-from ._lib import ops, require_cuda, stream
-from .point_transformer import _bn_scale_shift, _frozen
+from . import _derived, _lib, fold
+from ._lib import f32c, ops, require_cuda, stream
+
 
 def feature_knn(x, k):
     """x (B, D, N) float32 on the GPU -> (idx (B, N, k) int64, dist2 (B, N, k) float32): per point the k nearest points of its scan
@@ -61,16 +61,14 @@ def get_graph_feature(x, k=20, idx=None, dim9=False):
 def _edge_first_layer(conv, bn):
     """Eval-mode BatchNorm folded into an edge layer's first 1x1 convolution, split for the commuted form
     W' [x_j - x_i ; x_i] + t = Wa' x_j + (Wb' - Wa') x_i + t: returns (Wa'^T, (Wb' - Wa')^T, t), the matrices (C, 64)."""
-    s, t = _bn_scale_shift(bn)
-    W = conv.weight.detach().reshape(conv.out_channels, -1).float() * s[:, None]
+    W, t = fold.affine(conv, bn)
     C = W.shape[1] // 2
     Wa, Wb = W[:, :C], W[:, C:]
-    return Wa.t().contiguous(), (Wb - Wa).t().contiguous(), t.contiguous()
+    return Wa.t().contiguous(), (Wb - Wa).t().contiguous(), t
 
 
 def _second_layer(conv, bn):
-    s, t = _bn_scale_shift(bn)
-    return (conv.weight.detach().reshape(conv.out_channels, -1).float() * s[:, None]).contiguous(), t.contiguous()
+    return fold.affine(conv, bn)
 
 
 def edgeconv_max(x, idx, first, second=None, out=None, coff=0):
@@ -92,7 +90,7 @@ def edgeconv_max(x, idx, first, second=None, out=None, coff=0):
             raise ValueError(f"edgeconv_max: out must be ({B}, Ctot, {N}) with 0 <= coff <= Ctot - 64, got {tuple(out.shape)}, coff {coff}")
         if out.stride(2) != 1 or out.stride(1) != N:
             raise ValueError("edgeconv_max: out must be (B, Ctot, N) with rows of N contiguous floats")
-    x = (x if x.dtype == torch.float32 else x.float()).contiguous()   # one layout: the GEMMs below round by the layout they read
+    x = f32c(x, "edgeconv_max: x")                                    # one layout: the GEMMs below round by the layout they read
     xt = x.transpose(1, 2)                              # (B, N, C) view; the GEMMs read it in place
     P = torch.matmul(xt, WaT)                           # (B, N, 64), contiguous
     Q = torch.matmul(xt, WdT).add_(t1)
@@ -169,7 +167,7 @@ class DGCnnModule(nn.Module):
 
     def forward(self, x_in):
         x = x_in[0]
-        if _frozen(self, x) and x.dtype == torch.float32:
+        if fold.frozen(self, x) and x.dtype == torch.float32:
             return {"cls_pred": self._forward_eval(x)}
         return {"cls_pred": self._forward_train(x)}
 

@@ -113,12 +113,6 @@ def _channel_first(t, what, B=None, N=None):
     return t.shape[0], t.shape[2]
 
 
-def _f32c(t):
-    """float32 and contiguous by differentiable operations (the same tensor when it already is)."""
-    t = t if t.dtype == torch.float32 else t.to(torch.float32)
-    return t if t.is_contiguous() else t.contiguous()
-
-
 def _tgn_operands(pred_offset, sample_xyz, gt_seg_label):
     B, N = _channel_first(pred_offset, "pred_offset")
     _channel_first(sample_xyz, "sample_xyz", B, N)
@@ -127,7 +121,7 @@ def _tgn_operands(pred_offset, sample_xyz, gt_seg_label):
     except (TypeError, ValueError) as e:
         raise type(e)(f"gt_seg_label: {e}") from None
     _lib.require_cuda(pred_offset, sample_xyz, labels)
-    return _f32c(pred_offset), _f32c(sample_xyz.detach()), labels
+    return _lib.f32c(pred_offset), _lib.f32c(sample_xyz.detach()), labels
 
 
 def tgn_offset_losses(pred_offset, sample_xyz, gt_seg_label):
@@ -168,7 +162,7 @@ def centroid_loss(pred_offset, sample_xyz, distance, centroid, exists=None):
             raise ValueError(f"exists must be (B, C) = ({B}, {centroid.shape[2]}), got {tuple(exists.shape)}")
     _lib.require_cuda(pred_offset, sample_xyz, distance, centroid, exists)
     mask = None if exists is None else exists.to(torch.uint8).contiguous()
-    return _CentroidLoss.apply(_f32c(pred_offset), _f32c(sample_xyz.detach()), _f32c(distance.reshape(B, M)), _f32c(centroid.detach()), mask)
+    return _CentroidLoss.apply(_lib.f32c(pred_offset), _lib.f32c(sample_xyz.detach()), _lib.f32c(distance.reshape(B, M)), _lib.f32c(centroid.detach()), mask)
 
 
 def grouping_loss_terms(output, gt_seg_label, input_coords):

@@ -37,7 +37,7 @@ import functools
 
 import numpy as np
 
-from . import _derived, _lib, cluster as _cluster, crops as _crops, point_transformer as PT, pointops, tsegnet as _tsg
+from . import _lib, cluster as _cluster, crops as _crops, fold, point_transformer as PT, pointops, tsegnet as _tsg
 from .dgcnn import DGCnnModule  # noqa: F401
 from .pointnet import PointFirstModule  # noqa: F401
 from .pointnet2_utils import PointNetFeaturePropagation, PointNetSetAbstraction, PointNetSetAbstractionMsg, linear_relu, square_distance
@@ -54,6 +54,11 @@ def _one_index_check(forward):
         with _lib.deferred_index_check(type(self).__name__ + " forward"):
             return forward(self, *args, **kwargs)
     return wrapped
+
+
+def fold_head(conv1, bn1, conv2):
+    """(W1', b1', W2, b2) of a prediction head Conv1d(1x1) + eval-mode BatchNorm1d + ReLU + Conv1d(1x1)."""
+    return fold.affine(conv1, bn1) + fold.affine(conv2)
 
 
 class PointNetPPSeg(nn.Module):
@@ -78,15 +83,10 @@ class PointNetPPSeg(nn.Module):
 
     def _head(self, name, x):
         conv1, bn1, conv2 = getattr(self, f"{name}_conv_1"), getattr(self, f"{name}_bn_1"), getattr(self, f"{name}_conv_2")
-        if PT._frozen(self, x) and x.dtype == torch.float32:
+        if fold.frozen(self, x) and x.dtype == torch.float32:
             # eval: on channel-last rows (x arrives as the channel-first view of a channel-last tensor, so the permute is free), the
             # BatchNorm folded into the first 1x1 convolution (memoised): two GEMMs with bias, no layout copies of the (B, C, N) features
-            def fold():
-                s, t = PT._bn_scale_shift(bn1)
-                W1 = (conv1.weight.detach().squeeze(-1).float() * s[:, None]).contiguous()
-                b1 = (conv1.bias.detach().float() * s + t).contiguous()
-                return W1, b1, conv2.weight.detach().squeeze(-1).float().contiguous(), conv2.bias.detach().float().contiguous()
-            W1, b1, W2, b2 = _derived.cached(bn1, "head_eval", _derived.sources(conv1, bn1, conv2), None, fold)
+            W1, b1, W2, b2 = fold_head(conv1, bn1, conv2)
             y = linear_relu(x.permute(0, 2, 1), W1, b1)       # (ReLU in the GEMM's epilogue where the rows are contiguous)
             return F.linear(y, W2, b2).permute(0, 2, 1)
         return conv2(F.relu(bn1(conv1(x))))
@@ -199,7 +199,7 @@ class _LatentMLP(nn.Module):
         self.infer = nn.Sequential(nn.Linear(fdim, d_out), nn.BatchNorm1d(d_out), nn.ReLU(inplace=True))
 
     def forward(self, x):
-        if PT._frozen(self, x) and x.dtype == torch.float32:
+        if fold.frozen(self, x) and x.dtype == torch.float32:
             return PT.mlp_eval(self.infer, x)
         return PT.mlp_train(self.infer, x)
 

@@ -25,9 +25,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd import Function
 
-from . import _derived, _lib, pointnet2_utils as _U, pointops
-from ._lib import ops, stream
-from .sa_fused import bn_scale_shift as _bn_scale_shift, pack_first_layer
+from . import _derived, _lib, fold, pointnet2_utils as _U, pointops
+from ._lib import f32c, idx32c, ops, stream
+from .sa_fused import pack_first_layer
 
 _fwd = torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
 _bwd = torch.amp.custom_bwd(device_type="cuda")
@@ -68,8 +68,8 @@ def pt_softmax_aggregate(x_v, p_r, logit, idx):
     """x_v (n_v, c) value rows, p_r (n, nsample, c) position encodings, logit (n, nsample, c // share_planes) attention
     logits, idx (n, nsample) int32 neighbour rows -> (n, c).  Differentiable w.r.t. x_v, p_r and logit."""
     _lib.require_cuda(x_v, p_r, logit, idx)
-    x_v, p_r, logit = pointops._f32c(x_v, "x_v"), pointops._f32c(p_r, "p_r"), pointops._f32c(logit, "logit")
-    idx = pointops._idx32c(idx, "idx")
+    x_v, p_r, logit = f32c(x_v, "x_v"), f32c(p_r, "p_r"), f32c(logit, "logit")
+    idx = idx32c(idx, "idx")
     if idx.dim() != 2:
         raise ValueError(f"idx must be (n, nsample), got {tuple(idx.shape)}")
     n, nsample = idx.shape
@@ -198,7 +198,7 @@ def bn_rows(bn, x, relu=False):
             and x.shape[1] <= 1024 and bn.affine and bn.momentum is not None and bn.weight.dtype == torch.float32
             and not torch.is_autocast_enabled()):
         # any floating dtype and layout of x: cast and packed out here, so that autograd hands back x's own dtype (an fp32 module: fp32 out)
-        return _BNRows.apply(pointops._f32c(x, "x"), bn.weight, bn.bias, bn, relu)
+        return _BNRows.apply(f32c(x, "x"), bn.weight, bn.bias, bn, relu)
     y = bn(x)
     return F.relu(y) if relu else y
 
@@ -238,16 +238,6 @@ def mlp_train(seq, t):
     return t
 
 
-def folded_linear(lin, bn):
-    """(W', b') with eval-mode `bn` folded into `lin`: bn(lin(x)) == x @ W'.T + b'; memoised on `bn`."""
-    def fold():
-        s, t = _bn_scale_shift(bn)
-        W = (lin.weight.detach().float() * s[:, None]).contiguous()
-        b = t if lin.bias is None else lin.bias.detach().float() * s + t
-        return W, b.contiguous()
-    return _derived.cached(bn, "folded_linear", _derived.sources(lin, bn), None, fold)
-
-
 def mlp_eval(seq, x):
     """nn.Sequential of Linear / BatchNorm1d / ReLU in eval mode with every BatchNorm that follows a Linear folded into it (one GEMM
     with bias instead of GEMM + normalisation) and the ReLUs in place."""
@@ -257,10 +247,10 @@ def mlp_eval(seq, x):
         m = layers[i]
         if isinstance(m, nn.Linear) and i + 1 < len(layers) and isinstance(layers[i + 1], nn.BatchNorm1d):
             if i + 2 < len(layers) and isinstance(layers[i + 2], nn.ReLU) and not x.requires_grad:
-                x = _U.linear_relu(x, *folded_linear(m, layers[i + 1]))      # the ReLU in the GEMM's epilogue: one launch
+                x = _U.linear_relu(x, *fold.affine(m, layers[i + 1]))      # the ReLU in the GEMM's epilogue: one launch
                 i += 3
                 continue
-            x = F.linear(x, *folded_linear(m, layers[i + 1]))
+            x = F.linear(x, *fold.affine(m, layers[i + 1]))
             i += 2
         elif isinstance(m, nn.ReLU):
             x = torch.relu_(x) if not x.requires_grad else torch.relu(x)
@@ -281,23 +271,31 @@ def fold_pt_layer(layer):
 
 
 def _fold_pt_layer(lp0, bnp, lp3, bnw0, lw2, bnw3, lw5):
-    sp, tp = _bn_scale_shift(bnp)
-    a1, t1 = _bn_scale_shift(bnw0)
-    s3, t3 = _bn_scale_shift(bnw3)
-    f = lambda t: t.detach().float().contiguous()
-    return dict(Wp1=f(lp0.weight * sp[:, None]), bp1=f(lp0.bias * sp + tp), Wp2=f(lp3.weight), bp2=f(lp3.bias),
-                a1=f(a1), t1=f(t1), Ww1=f(lw2.weight * s3[:, None]), bw1=f(lw2.bias * s3 + t3), Ww2=f(lw5.weight), bw2=f(lw5.bias))
+    (Wp1, bp1), (Wp2, bp2) = fold.affine(lp0, bnp), fold.affine(lp3)
+    (Ww1, bw1), (Ww2, bw2) = fold.affine(lw2, bnw3), fold.affine(lw5)
+    a1, t1 = fold.scale_shift(bnw0)
+    return dict(Wp1=Wp1, bp1=bp1, Wp2=Wp2, bp2=bp2, a1=a1, t1=t1, Ww1=Ww1, bw1=bw1, Ww2=Ww2, bw2=bw2)
+
+
+def fold_transition_down(td, c):
+    """Operands (Wt, Wxs, b) of the fused down-sampling step of a TransitionDown with stride > 1 over c feature channels: its linear
+    layer (no bias) + eval-mode BatchNorm packed as a set-abstraction first layer with the columns [xyz, features] (use_xyz=True);
+    memoised on the module."""
+    def build():
+        f = pack_first_layer(td.linear.weight.detach().float(), None, *fold.scale_shift(td.bn), c, True)
+        return f["Wt"], f["Wxs"], f["b"]
+    return _derived.cached(td, "down", _derived.sources(td.linear, td.bn), c, build)
 
 
 def pt_attention(p, x_q, x_k, x_v, idx, params, post=None):
     """The fused eval-mode layer: p (n,3), x_q/x_k/x_v (n,c), idx (n,nsample) int32 -> (n,c).
     post = (scale, shift): relu(out * scale + shift) on the way out (the block's bn2 + ReLU, folded)."""
     _lib.require_cuda(p, x_q, x_k, x_v, idx)
-    p, x_q, x_k, x_v = (pointops._f32c(t.detach(), what) for t, what in ((p, "p"), (x_q, "x_q"), (x_k, "x_k"), (x_v, "x_v")))
+    p, x_q, x_k, x_v = (f32c(t.detach(), what) for t, what in ((p, "p"), (x_q, "x_q"), (x_k, "x_k"), (x_v, "x_v")))
     # the kernel takes 16-byte vector loads of the key and value rows and its launcher refuses other pointers: a packed view that
     # starts off that grid (buf[1:], a row slice of a wider batch) is copied to a fresh allocation
     x_k, x_v = (t if t.data_ptr() % 16 == 0 else t.clone() for t in (x_k, x_v))
-    idx = pointops._idx32c(idx, "idx")
+    idx = idx32c(idx, "idx")
     if x_q.dim() != 2 or idx.dim() != 2 or idx.shape[0] != x_q.shape[0]:
         raise ValueError(f"x_q must be (n, c) and idx (n, nsample), got {tuple(x_q.shape)} and {tuple(idx.shape)}")
     n, c = x_q.shape
@@ -313,11 +311,6 @@ def pt_attention(p, x_q, x_k, x_v, idx, params, post=None):
     ops().tgn_pt_attention_forward(n, nsample, c, g, p, x_q, x_k, x_v, idx, P["Wp1"], P["bp1"], P["Wp2"], P["bp2"], P["a1"], P["t1"], P["Ww1"],
                                    P["bw1"], P["Ww2"], P["bw2"], post[0] if post else None, post[1] if post else None, out, stream())
     return out
-
-
-def _frozen(module, *tensors):
-    return (not module.training) and not (torch.is_grad_enabled() and (
-        any(t is not None and t.requires_grad for t in tensors) or any(q.requires_grad for q in module.parameters())))
 
 
 class PointTransformerLayer(nn.Module):
@@ -348,12 +341,9 @@ class PointTransformerLayer(nn.Module):
         # stages (24 000 points x 32 channels: 0.09 ms), wrong for the deep ones -- 93 points x 512 channels keep 93 lone waves busy
         # for 0.94 ms where the composition below needs 0.15 (profiled: 4.3 of the forward's 13 ms went there)
         deep = self.out_planes * g >= 8192 and p.shape[0] < 4096
-        if (_frozen(self, p, x) and not deep and self.nsample <= 64 and self.out_planes % 4 == 0 and g in (4, 8, 16, 32, 64)
+        if (fold.frozen(self, p, x) and not deep and self.nsample <= 64 and self.out_planes % 4 == 0 and g in (4, 8, 16, 32, 64)
                 and x_q.dtype == torch.float32):
-            post = None
-            if post_bn is not None:
-                post = _derived.cached(post_bn, "scale_shift", _derived.sources(post_bn), None,
-                                       lambda: tuple(t.contiguous() for t in _bn_scale_shift(post_bn)))
+            post = None if post_bn is None else fold.scale_shift(post_bn)
             return pt_attention(p, x_q, x_k, x_v, idx, fold_pt_layer(self), post)
         # training: the reference's composition with the softmax + weighted sum as one differentiable kernel pair.
         # Under autocast this section stays in fp32: it is bandwidth-bound over (n, nsample, c) tensors that the gather
@@ -362,7 +352,7 @@ class PointTransformerLayer(nn.Module):
         with torch.autocast("cuda", enabled=False):
             x_q, x_k, x_v = x_q.float(), x_k.float(), x_v.float()
             # (idx comes from this package's kNN: no index check, i.e. no host round trip per layer)
-            pc = pointops._f32c(p, "p")
+            pc = f32c(p, "p")
             x_kg = pointops._QueryGroup.apply(pc, pc, x_k.contiguous(), idx, True)                            # (n, nsample, 3+c)
             p_r, x_kg = x_kg[:, :, 0:3], x_kg[:, :, 3:]
             p_r = _mlp_rows(self.linear_p, p_r)
@@ -398,8 +388,8 @@ class TransitionDown(nn.Module):
     def forward(self, pxo):
         p, x, o = pxo  # (n, 3), (n, c), (b)
         if self.stride == 1:
-            if _frozen(self, x) and x.dtype == torch.float32:
-                return [p, _U.linear_relu(x, *folded_linear(self.linear, self.bn)), o]
+            if fold.frozen(self, x) and x.dtype == torch.float32:
+                return [p, _U.linear_relu(x, *fold.affine(self.linear, self.bn)), o]
             return [p, bn_rows(self.bn, _lin(self.linear, x), relu=True), o]
         pre, self._presampled = getattr(self, "_presampled", None), None
         if pre is not None and pre[0] is p and pre[1] is o:
@@ -410,20 +400,15 @@ class TransitionDown(nn.Module):
             n_o = self.sample_offsets(o)
             idx, n_p = pointops.fps_with_coords(p, o, n_o, prefix=True)                 # blocks.py:69-70: indices and p[idx] from one kernel
         C1 = self.linear.out_features
-        if _frozen(self, p, x) and self.nsample <= 64 and C1 % 4 == 0 and x.dtype == torch.float32:
+        if fold.frozen(self, p, x) and self.nsample <= 64 and C1 % 4 == 0 and x.dtype == torch.float32:
             # the whole down-sampling step fused: (m, nsample, 3+c) is never built (blocks.py:71-73)
             kidx = pointops.knn_indices(self.nsample, p, n_p, o, n_o)
             n, c = x.shape
             m = n_p.shape[0]
-
-            def fold():
-                s, t = _bn_scale_shift(self.bn)                            # (the linear layer has no bias)
-                f = pack_first_layer(self.linear.weight.detach().float(), None, s, t, c, True)   # columns [xyz, features] (use_xyz=True)
-                return f["Wt"], f["Wxs"], f["b"]
-            Wt, Wxyz, t = _derived.cached(self, "down", _derived.sources(self.linear, self.bn), c, fold)
+            Wt, Wxyz, t = fold_transition_down(self, c)
             A = torch.empty(n, C1, dtype=torch.float32, device=x.device)
             L = ops()
-            L.tgn_sa_point_transform(n, c, C1, pointops._f32c(p, "p"), x.contiguous(), Wt, A, stream())
+            L.tgn_sa_point_transform(n, c, C1, f32c(p, "p"), x.contiguous(), Wt, A, stream())
             out = torch.empty(m, C1, dtype=torch.float32, device=x.device)
             L.tgn_sa_gather_max(1, n, m, self.nsample, C1, A, n_p, Wxyz, t, kidx, 0, 1, out, stream())
             return [n_p, out, n_o]
@@ -452,12 +437,12 @@ class TransitionUp(nn.Module):
                                           output_size=x.shape[0])   # (the size is known: no device->host round trip)
             cnt = torch.diff(o, prepend=o.new_zeros(1)).to(x.dtype).unsqueeze(1)
             mean = torch.zeros(o.shape[0], x.shape[1], dtype=x.dtype, device=x.device).index_add_(0, seg, x) / cnt
-            if _frozen(self, x) and x.dtype == torch.float32:
+            if fold.frozen(self, x) and x.dtype == torch.float32:
                 return mlp_eval(self.linear1, torch.cat((x, mlp_eval(self.linear2, mean)[seg]), 1))
             return mlp_train(self.linear1, torch.cat((x, mlp_train(self.linear2, mean)[seg]), 1))
         p1, x1, o1 = pxo1
         p2, x2, o2 = pxo2
-        if _frozen(self, x1, x2) and x1.dtype == torch.float32 and x2.dtype == torch.float32:
+        if fold.frozen(self, x1, x2) and x1.dtype == torch.float32 and x2.dtype == torch.float32:
             return mlp_eval(self.linear1, x1).add_(pointops.interpolation(p2, p1, mlp_eval(self.linear2, x2).contiguous(), o2, o1))
         return mlp_train(self.linear1, x1) + pointops.interpolation(p2, p1, mlp_train(self.linear2, x2).contiguous(), o2, o1)
 
@@ -478,11 +463,11 @@ class PointTransformerBlock(nn.Module):
     def forward(self, pxo):
         p, x, o = pxo
         identity = x
-        if _frozen(self, x) and x.dtype == torch.float32:
+        if fold.frozen(self, x) and x.dtype == torch.float32:
             # eval: bn1 / bn3 folded into their linears (a GEMM with bias each), bn2 one fused normalisation kernel
-            x = _U.linear_relu(x, *folded_linear(self.linear1, self.bn1))
+            x = _U.linear_relu(x, *fold.affine(self.linear1, self.bn1))
             x = self.transformer2([p, x, o], post_bn=self.bn2)
-            x = F.linear(x, *folded_linear(self.linear3, self.bn3)).add_(identity)
+            x = F.linear(x, *fold.affine(self.linear3, self.bn3)).add_(identity)
             return [p, torch.relu_(x), o]
         x = bn_rows(self.bn1, _lin(self.linear1, x), relu=True)
         x = self.transformer2([p, x, o], post_bn=self.bn2)

@@ -26,31 +26,16 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _derived
-from ._lib import ops, require_cuda, stream
-from .point_transformer import _bn_scale_shift, _frozen
+from . import _derived, fold
+from ._lib import f32c, ops, require_cuda, stream
 
 _ACTS = {"identity": 0, "relu": 1, "leaky_relu": 2}
 
 
-def _folded(conv, bn):
-    """Eval-mode BatchNorm folded into a 1x1 convolution: (W' (C, K) = scale * W, shift (C) = scale * bias + bn shift);
-    bn None: the convolution alone.  Memoised on the convolution (_derived.cached, as dgcnn._folded)."""
-    def build():
-        W = conv.weight.detach().reshape(conv.out_channels, -1).float()
-        b = conv.bias.detach().float() if conv.bias is not None else torch.zeros(conv.out_channels, device=W.device)
-        if bn is None:
-            return W.contiguous(), b.contiguous()
-        s, t = _bn_scale_shift(bn)
-        return (W * s[:, None]).contiguous(), (b * s + t).contiguous()
-    src = _derived.sources(conv) + (_derived.sources(bn) if bn is not None else [])
-    return _derived.cached(conv, "pointnet_folded", src, None, build)
-
-
 def _folded_t(conv, bn):
-    """The same with the weight as the kernel reads it: (K, C) row-major."""
+    """fold.affine(conv, bn) with the weight as tgn_linear_act_max reads it: (K, C) row-major.  Memoised on the convolution."""
     def build():
-        W, t = _folded(conv, bn)
+        W, t = fold.affine(conv, bn)
         return W.t().contiguous(), t
     src = _derived.sources(conv) + (_derived.sources(bn) if bn is not None else [])
     return _derived.cached(conv, "pointnet_folded_t", src, None, build)
@@ -86,7 +71,7 @@ def linear_act_max(x, conv, bn, act, slope=0.0):
         raise ValueError(f"linear_act_max: x must have 1 .. 512 channels, got {K}")
     if conv.weight.device != x.device:
         raise ValueError(f"linear_act_max: conv lives on {conv.weight.device}, x on {x.device}")
-    x = (x if x.dtype == torch.float32 else x.float()).contiguous()
+    x = f32c(x, "linear_act_max: x")
     Wt, shift = _folded_t(conv, bn)
     out = torch.empty(B, C, dtype=torch.float32, device=x.device)
     ws_bytes = ops().tgn_linear_act_max_workspace_bytes(B, N, K, C)
@@ -98,7 +83,7 @@ def linear_act_max(x, conv, bn, act, slope=0.0):
 def _pointwise(x, conv, bn, relu):
     """A narrow 1x1 convolution in eval mode with the BatchNorm folded, (B, K, N) -> (B, C, N): one GEMM per scan, so that a
     scan's bits do not depend on the batch."""
-    W, t = _folded(conv, bn)
+    W, t = fold.affine(conv, bn)
     y = torch.empty(x.shape[0], W.shape[0], x.shape[2], dtype=torch.float32, device=x.device)
     for b in range(x.shape[0]):
         torch.matmul(W, x[b], out=y[b])
@@ -157,7 +142,7 @@ class _STN(nn.Module):
         return torch.cat(rows).float().view(-1, k, k)
 
     def forward(self, x):
-        if _frozen(self, x) and x.dtype == torch.float32:
+        if fold.frozen(self, x) and x.dtype == torch.float32:
             return self._forward_eval(x)
         return self._forward_train(x)
 
@@ -210,7 +195,7 @@ class PointNetEncoder(nn.Module):
         return torch.cat([rep, pointfeat], 1), trans, trans_feat
 
     def forward(self, x):
-        if _frozen(self, x) and x.dtype == torch.float32:
+        if fold.frozen(self, x) and x.dtype == torch.float32:
             return self._assemble(*self._features_eval(x))
         return self._assemble(*self._features_train(x))
 
@@ -237,7 +222,7 @@ class PointNetEncoder(nn.Module):
         require_cuda(x)
         x = x.contiguous()
         trans = self.stn._forward_eval(x)
-        W1, t1 = _folded(self.conv1, self.bn1)
+        W1, t1 = fold.affine(self.conv1, self.bn1)
         W1 = torch.cat([torch.matmul(W1[:, :3], trans.transpose(1, 2)), W1[:, 3:].expand(x.shape[0], -1, -1)], dim=2)   # (B, C, D)
         h = _per_scan_mm(W1, x).add_(t1[:, None]).relu_()
         trans_feat = None
@@ -273,7 +258,7 @@ class get_model(nn.Module):
 
     def forward(self, x_in):
         x = x_in[0]
-        if _frozen(self, x) and x.dtype == torch.float32:
+        if fold.frozen(self, x) and x.dtype == torch.float32:
             return self._forward_eval(x)
         return self._forward_train(x)
 
@@ -293,8 +278,8 @@ class get_model(nn.Module):
         B, ng = g.shape
 
         def build():
-            W1, t1 = _folded(self.conv1, self.bn1)
-            W4, t4 = _folded(self.conv4, None)
+            W1, t1 = fold.affine(self.conv1, self.bn1)
+            W4, t4 = fold.affine(self.conv4)
             return W1[:, ng:].contiguous(), W1[:, :ng].t().double(), t1.double(), W4.double(), t4.double()[:, None]
         W1p, W1g, t1, W4, t4 = _derived.cached(self, "pointnet_head", _derived.sources(self.conv1, self.bn1, self.conv4), ng, build)
         out = torch.empty(B, self.k, x.shape[2], dtype=torch.float32, device=x.device)

@@ -26,11 +26,11 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd import Function
 
-from . import _derived, _lib, config
+from . import _derived, _lib, config, fold
 from . import _fps_prefix
 from ._fps_prefix import PrefixBook
-from ._lib import as_int, ops, require_cuda, stream
-from .sa_fused import (_f32c, bn_scale_shift, fold_first_layer, fold_second_layer, pad16, sa_all_mlp2_max,  # noqa: F401
+from ._lib import as_int, f32c, ops, require_cuda, stream
+from .sa_fused import (fold_first_layer, fold_second_layer, pad16, sa_all_mlp2_max,  # noqa: F401
                        sa_first_layer, sa_level_max, sa_level_mlp2_max, sa_point_transform, split_point_transform, split_second_layer)
 
 _fwd = torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
@@ -60,7 +60,7 @@ class _SquareDistance3(Function):
     @staticmethod
     @_fwd
     def forward(ctx, src, dst):
-        src, dst = _f32c(src), _f32c(dst)
+        src, dst = f32c(src), f32c(dst)
         B, N, _ = src.shape
         if dst.shape[0] != B:
             raise RuntimeError(f"square_distance: batch sizes differ ({B} vs {dst.shape[0]})")
@@ -135,7 +135,7 @@ def index_points(points, idx):
     require_cuda(points, idx)
     if idx.dtype not in (torch.int64, torch.int32):
         idx = idx.long()
-    points = _f32c(points)
+    points = f32c(points)
     out = _IndexPoints.apply(points, idx.contiguous())
     return out
 
@@ -165,7 +165,7 @@ def _fps_dense(xyz, npoint, want_coords=False, cuda_compat=False, prefix=False, 
     """mode: explicit tie-order / contraction flag bits (None: the process-wide _lib.set_fps_mode() setting)."""
     require_cuda(xyz)
     npoint = as_int(npoint)
-    xyz = _f32c(xyz.detach())
+    xyz = f32c(xyz.detach())
     B, N, _ = xyz.shape
     mode = _lib.fps_flags(cuda_compat) if mode is None else int(mode)
     # prefix: this call site chains sampling levels (FPS of an FPS result is the identity); the tree tie order breaks it
@@ -252,7 +252,7 @@ def query_ball_point(radius, nsample, xyz, new_xyz):
     their first hit (reference pointnet2_utils.py:120-144, without its (B,S,N) matrix and sort)."""
     require_cuda(xyz, new_xyz)
     nsample = as_int(nsample)
-    xyz, new_xyz = _f32c(xyz.detach()), _f32c(new_xyz.detach())
+    xyz, new_xyz = f32c(xyz.detach()), f32c(new_xyz.detach())
     B, N, _ = xyz.shape
     S = new_xyz.shape[1]
     # `sqrdists > radius ** 2`: python evaluates radius**2 in double, torch compares in fp32
@@ -309,7 +309,7 @@ def group_points(xyz, new_xyz, points, idx, xyz_first=True):
     empty ball yields index N (pointnet2_utils.py:136-141) -- after one stream synchronisation per call;
     TGN_INDEX_CHECK=off drops check and sync (rows with a bad index are then filled from point 0)."""
     require_cuda(xyz, new_xyz, idx)
-    out = _GroupPoints.apply(_f32c(xyz), _f32c(new_xyz), None if points is None else _f32c(points),
+    out = _GroupPoints.apply(f32c(xyz), f32c(new_xyz), None if points is None else f32c(points),
                              idx.contiguous(), bool(xyz_first))
     return out
 
@@ -348,7 +348,7 @@ def three_nn(xyz1, xyz2):
     """3 nearest points of xyz2 (B,S,3) for every point of xyz1 (B,N,3): (dist (B,N,3) squared,
     expanded form, ascending by (dist, index); idx (B,N,3) int64) -- pointnet2_utils.py:333-335."""
     require_cuda(xyz1, xyz2)
-    xyz1, xyz2 = _f32c(xyz1.detach()), _f32c(xyz2.detach())
+    xyz1, xyz2 = f32c(xyz1.detach()), f32c(xyz2.detach())
     B, N, _ = xyz1.shape
     S = xyz2.shape[1]
     dist = torch.empty(B, N, 3, dtype=torch.float32, device=xyz1.device)
@@ -401,11 +401,11 @@ def three_interpolate_add_relu(points2, dist, idx, add=None, relu=False):
     require_cuda(points2, dist, idx)
     if idx.dtype not in (torch.int64, torch.int32):
         idx = idx.long()
-    points2, dist, idx = _f32c(points2), _f32c(dist), idx.contiguous()
+    points2, dist, idx = f32c(points2), f32c(dist), idx.contiguous()
     B, S, C = points2.shape
     N = dist.shape[1]
     if add is not None:
-        add = _f32c(add)
+        add = f32c(add)
         if tuple(add.shape) != (B, N, C):
             raise ValueError(f"three_interpolate_add_relu: add must be ({B}, {N}, {C}), got {tuple(add.shape)}")
     out = add if add is not None else torch.empty(B, N, C, dtype=torch.float32, device=points2.device)
@@ -418,7 +418,7 @@ def three_interpolate(points2, dist, idx):
     require_cuda(points2, dist, idx)
     if idx.dtype not in (torch.int64, torch.int32):
         idx = idx.long()
-    return _ThreeInterpolate.apply(_f32c(points2), _f32c(dist), idx.contiguous())
+    return _ThreeInterpolate.apply(f32c(points2), f32c(dist), idx.contiguous())
 
 
 # ---------------------------------------------------------------------------------------------
@@ -510,8 +510,8 @@ class PointNetSetAbstraction(nn.Module):
             points = points.permute(0, 2, 1)
         if not self.group_all and len(self.mlp_convs) > 0 and _can_fuse(self, xyz, points):
             # eval fast path: FPS (+coordinates) -> ball query -> fused shared MLP + max; `grouped` is never built
-            xyz_c = _f32c(xyz)
-            points_c = None if points is None else _f32c(points)
+            xyz_c = f32c(xyz)
+            points_c = None if points is None else f32c(points)
             _, new_xyz = _fps_dense(xyz_c, self.npoint, want_coords=True, prefix=True)
             idx = query_ball_point(self.radius, self.nsample, xyz_c, new_xyz)
             new_points = _fused_level(xyz_c, new_xyz, points_c, idx, self.mlp_convs, self.mlp_bns, True, xyz_c.shape[1],
@@ -523,7 +523,7 @@ class PointNetSetAbstraction(nn.Module):
         if (self.group_all and len(self.mlp_convs) == 2 and xyz.shape[1] >= 1 and _can_fuse(self, xyz, points)
                 and _mlp2_shape_ok(min(xyz.shape[1], 64), self.mlp_convs[0].out_channels)):
             # eval fast path of the form the reference builds (tsg_seg_module.py:28): the whole cloud is one group
-            y = sa_all_mlp2_max(_f32c(xyz), None if points is None else _f32c(points), self.mlp_convs, self.mlp_bns)
+            y = sa_all_mlp2_max(f32c(xyz), None if points is None else f32c(points), self.mlp_convs, self.mlp_bns)
             return xyz.new_zeros(xyz.shape[0], xyz.shape[2], 1), y.unsqueeze(2)
         if self.group_all:
             new_xyz, new_points = sample_and_group_all(xyz, points)
@@ -569,8 +569,8 @@ class PointNetSetAbstractionMsg(nn.Module):
             new_xyz = index_points(xyz, farthest_point_sample(xyz, S))
         else:
             _, new_xyz = _fps_dense(xyz, S, want_coords=True, prefix=not self.training)
-        xyz_c = _f32c(xyz)
-        points_c = None if points is None else _f32c(points)
+        xyz_c = f32c(xyz)
+        points_c = None if points is None else f32c(points)
         fuse = _can_fuse(self, xyz, points)
         new_points_list = []
         chained = fuse and all(len(c) == 2 and _fused_shape_ok(k, c[0].out_channels) and _mlp2_shape_ok(k, c[0].out_channels)
@@ -599,6 +599,12 @@ class PointNetSetAbstractionMsg(nn.Module):
         new_xyz = new_xyz.permute(0, 2, 1)
         new_points_concat = torch.cat(new_points_list, dim=1)
         return new_xyz, new_points_concat
+
+
+def fold_fp_stack(convs, bns):
+    """[(W', b')] of a feature-propagation stack of Conv1d(1x1) + eval-mode BatchNorm1d pairs, memoised on its first BatchNorm."""
+    return _derived.cached(bns[0], "fp_eval", _derived.sources(*convs, *bns), None,
+                           lambda: [fold.affine(c, b) for c, b in zip(convs, bns)])
 
 
 class PointNetFeaturePropagation(nn.Module):
@@ -638,16 +644,7 @@ class PointNetFeaturePropagation(nn.Module):
                 # eval: every BatchNorm folded into its 1x1 convolution (memoised), the whole stack on channel-last rows -- one GEMM
                 # with bias + an in-place ReLU per layer, no normalisation kernels and no (B,N,C) <-> (B,C,N) copies in between; the
                 # result goes out as the channel-first VIEW of the channel-last tensor
-                def fold():
-                    out = []
-                    for conv, bn in zip(self.mlp_convs, self.mlp_bns):
-                        sc, sh = bn_scale_shift(bn)
-                        Wc = conv.weight.detach().squeeze(-1).float()
-                        bias = conv.bias.detach().float() if conv.bias is not None else torch.zeros_like(sh)
-                        out.append(((Wc * sc[:, None]).contiguous(), (bias * sc + sh).contiguous()))
-                    return out
-                srcs = _derived.sources(*self.mlp_convs, *self.mlp_bns)
-                layers = _derived.cached(self.mlp_bns[0], "fp_eval", srcs, None, fold)
+                layers = fold_fp_stack(self.mlp_convs, self.mlp_bns)
                 W0, b0 = layers[0]
                 # relu(interpolation of the transformed coarse rows + the skip features' share + bias): the bias rides in the COARSE
                 # GEMM (S contiguous rows; the interpolation weights sum to one, so it comes through unchanged up to one rounding --

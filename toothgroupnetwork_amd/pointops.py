@@ -18,30 +18,10 @@ from torch.utils.weak import WeakTensorKeyDictionary
 from . import _lib, config
 from . import _fps_prefix
 from ._fps_prefix import PrefixBook
-from ._lib import as_int, ops, require_cuda, stream
+from ._lib import as_int, f32c, idx32c, ops, require_cuda, stream
 
 _fwd = torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
 _bwd = torch.amp.custom_bwd(device_type="cuda")
-
-
-def _i32(t):
-    return t if t.dtype == torch.int32 else t.to(torch.int32)
-
-
-def _f32c(t, what):
-    """What every float tensor argument goes through on its way to a kernel (the kernels read packed fp32 rows): any floating dtype,
-    any strides, any storage offset in; float32 and contiguous out -- the same tensor when it already is.  Applied in the public
-    functions, outside the autograd Functions, so that gradients come back in the caller's dtype and layout."""
-    if not isinstance(t, torch.Tensor) or not t.is_floating_point():
-        raise TypeError(f"{what} must be a floating-point tensor, got {getattr(t, 'dtype', type(t).__name__)}")
-    t = t if t.dtype == torch.float32 else t.float()
-    return t if t.is_contiguous() else t.contiguous()
-
-
-def _idx32c(t, what):
-    if not isinstance(t, torch.Tensor) or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
-        raise TypeError(f"{what} must be an integer tensor, got {getattr(t, 'dtype', type(t).__name__)}")
-    return _i32(t).contiguous()
 
 
 def _packed(t, what):
@@ -142,9 +122,9 @@ def fps_with_coords(xyz, offset, new_offset, cuda_compat=False, prefix=False):
     (what blocks.py:69-70 computes with a second gather).  Returns (idx int32 (m,), new_xyz (m,3)).
     prefix=True: this call site chains sampling levels -- take part in the FPS-of-an-FPS-result shortcut."""
     require_cuda(xyz, offset, new_offset)
-    xyz = _f32c(xyz.detach(), "xyz")
+    xyz = f32c(xyz.detach(), "xyz")
     off_h, noff_h = offsets_host(offset, new_offset)   # one device->host copy, or none (register_offsets)
-    offset, new_offset = _idx32c(offset, "offset"), _idx32c(new_offset, "new_offset")
+    offset, new_offset = idx32c(offset, "offset"), idx32c(new_offset, "new_offset")
     b = offset.shape[0]
     if b == 0 or noff_h[-1] == 0:      # nothing to sample (no segments, or only empty ones): an empty result, no launch
         return (torch.zeros(0, dtype=torch.int32, device=xyz.device),
@@ -195,8 +175,8 @@ def _knn_raw(nsample, xyz, new_xyz, offset, new_offset):
     if new_xyz is None:
         new_xyz = xyz
     require_cuda(xyz, new_xyz, offset, new_offset)
-    xyz, new_xyz = _f32c(xyz.detach(), "xyz"), _f32c(new_xyz.detach(), "new_xyz")
-    offset, new_offset = _idx32c(offset, "offset"), _idx32c(new_offset, "new_offset")
+    xyz, new_xyz = f32c(xyz.detach(), "xyz"), f32c(new_xyz.detach(), "new_xyz")
+    offset, new_offset = idx32c(offset, "offset"), idx32c(new_offset, "new_offset")
     m = new_xyz.shape[0]
     idx = torch.empty(m, nsample, dtype=torch.int32, device=xyz.device)
     dist2 = torch.empty(m, nsample, dtype=torch.float32, device=xyz.device)
@@ -319,7 +299,7 @@ class Grouping(Function):
 def grouping(input, idx):
     """input (n, c) of any floating dtype and layout, idx (m, nsample) of any integer dtype -> (m, nsample, c) float32"""
     require_cuda(input, idx)
-    return Grouping.apply(_f32c(input, "input"), _idx32c(idx, "idx"))
+    return Grouping.apply(f32c(input, "input"), idx32c(idx, "idx"))
 
 
 class _QueryGroup(Function):
@@ -384,12 +364,12 @@ def queryandgroup(nsample, xyz, new_xyz, feat, idx, offset, new_offset, use_xyz=
         new_xyz = xyz
     require_cuda(xyz, new_xyz, feat)
     same = new_xyz is xyz
-    xyz, feat = _f32c(xyz, "xyz"), _f32c(feat, "feat")
-    new_xyz = xyz if same else _f32c(new_xyz, "new_xyz")
+    xyz, feat = f32c(xyz, "xyz"), f32c(feat, "feat")
+    new_xyz = xyz if same else f32c(new_xyz, "new_xyz")
     own_idx = idx is None
     if own_idx:
         idx, _ = knnquery(nsample, xyz, new_xyz, offset, new_offset)  # (m, nsample)
-    idx = _idx32c(idx, "idx")
+    idx = idx32c(idx, "idx")
     if not own_idx and use_xyz:
         _lib.begin_index_check()
     out = _QueryGroup.apply(xyz, new_xyz, feat, idx, bool(use_xyz))
@@ -438,7 +418,7 @@ class Subtraction(Function):
 def subtraction(input1, input2, idx):
     """input1, input2 (n, c) of any floating dtype and layout, idx (n, nsample) of any integer dtype -> (n, nsample, c) float32"""
     require_cuda(input1, input2, idx)
-    return Subtraction.apply(_f32c(input1, "input1"), _f32c(input2, "input2"), _idx32c(idx, "idx"))
+    return Subtraction.apply(f32c(input1, "input1"), f32c(input2, "input2"), idx32c(idx, "idx"))
 
 
 class Aggregation(Function):
@@ -483,7 +463,7 @@ def aggregation(input, position, weight, idx):
     """input (n, c), position (n, nsample, c), weight (n, nsample, c') of any floating dtype and layout, idx (n, nsample) of any
     integer dtype -> (n, c) float32"""
     require_cuda(input, position, weight, idx)
-    return Aggregation.apply(_f32c(input, "input"), _f32c(position, "position"), _f32c(weight, "weight"), _idx32c(idx, "idx"))
+    return Aggregation.apply(f32c(input, "input"), f32c(position, "position"), f32c(weight, "weight"), idx32c(idx, "idx"))
 
 
 def _inverse_distance_weights(dist):
@@ -526,7 +506,7 @@ def interpolation(xyz, new_xyz, feat, offset, new_offset, k=3):
     output: (n, c)                  [pointops.py:164-180; weights detached as there]
     """
     require_cuda(xyz, new_xyz, feat)
-    xyz, new_xyz, feat = _f32c(xyz, "xyz"), _f32c(new_xyz, "new_xyz"), _f32c(feat, "feat")
+    xyz, new_xyz, feat = f32c(xyz, "xyz"), f32c(new_xyz, "new_xyz"), f32c(feat, "feat")
     k = as_int(k)
     idx, dist = knnquery(k, xyz, new_xyz, offset, new_offset)  # (n, k), (n, k)
     weight = _inverse_distance_weights(dist).detach().contiguous()
@@ -569,4 +549,4 @@ class Interpolation(Function):
 def interpolation2(xyz, new_xyz, input, offset, new_offset, k=3):
     """Interpolation.apply on arguments of any floating dtype and layout (the gradient reaches `input` only, as in the reference)"""
     require_cuda(xyz, new_xyz, input)
-    return Interpolation.apply(_f32c(xyz, "xyz"), _f32c(new_xyz, "new_xyz"), _f32c(input, "input"), offset, new_offset, k)
+    return Interpolation.apply(f32c(xyz, "xyz"), f32c(new_xyz, "new_xyz"), f32c(input, "input"), offset, new_offset, k)

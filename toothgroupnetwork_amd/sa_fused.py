@@ -10,46 +10,30 @@ modules of pointnet2_utils, by HotPath (what bench.py --fused measures), by Tran
               Wd  (16, C1)        rows [x, y, z, features..., 0] -- the direct forms (3+D <= 16)
               b   (C,)            shift + scale * bias
               W2f (C1p/8, C2, 8)  W2f[kb, c, i] = scale[c] * W[c, 8*kb + i], zero for the padded input channels
-            C1p = C1 rounded up to 16 (pad16), zero columns added: what the two-layer kernels want of the first layer;
+            C1p = C1 rounded up to 16 (pad16), zero columns added: what the two-layer kernels want of the first layer.
+            scale and shift of a module's BatchNorm come from fold.scale_shift (fold.py: the one place that knows the fold); the
+            packers take them as plain arguments and scale inside the layout they own;
   plan      plan_branch: everything that depends on shape and configuration only -- direct or commuted first layer, padding, the
             bf16 x 3 weight images, one or two layers -- decided once per (weights, shape);
   launch    launch_branch: the per-point transform where the plan is commuted, then exactly one level kernel.  It only enqueues.
 """
 import torch
 
-from . import _derived, _lib, config
-from ._lib import ops, require_cuda, stream
-
-
-def _f32c(t):
-    t = t if t.dtype == torch.float32 else t.float()
-    return t if t.is_contiguous() else t.contiguous()
-
-
-def _idxc(idx):
-    """Index tensors reach the kernels as packed int64 or int32 (a flag tells which); any other integer width is widened."""
-    if idx.dtype not in (torch.int64, torch.int32):
-        idx = idx.long()
-    return idx if idx.is_contiguous() else idx.contiguous()
+from . import _derived, _lib, config, fold
+from ._lib import f32c, idx_packed, ops, require_cuda, stream
 
 
 def _sa_operands(xyz, new_xyz, points, idx):
     """The tensor arguments of the fused set-abstraction entries as the kernels read them: packed fp32 rows, packed indices.  The
     modules pass them in that form already (then nothing is copied); a direct caller may pass any floating dtype or layout."""
     require_cuda(xyz, new_xyz, points, idx)
-    return (_f32c(xyz.detach()), None if new_xyz is None else _f32c(new_xyz.detach()), None if points is None else _f32c(points.detach()),
-            None if idx is None else _idxc(idx))
+    return (f32c(xyz.detach()), None if new_xyz is None else f32c(new_xyz.detach()), None if points is None else f32c(points.detach()),
+            None if idx is None else idx_packed(idx))
 
 
 # ---------------------------------------------------------------------------------------------
 # packers
 # ---------------------------------------------------------------------------------------------
-def bn_scale_shift(bn):
-    """Eval-mode BatchNorm as the affine map y = scale * x + shift."""
-    scale = (bn.weight.detach() / torch.sqrt(bn.running_var + bn.eps)).float()
-    return scale, (bn.bias.detach() - bn.running_mean * scale).float()
-
-
 def pad16(C1):
     return (C1 + 15) // 16 * 16
 
@@ -98,7 +82,7 @@ def pack_second_layer(W, bias, scale, shift, C1p):
 
 def _conv_operands(conv, bn):
     W = conv.weight.detach().reshape(conv.out_channels, -1).float()
-    return (W, None if conv.bias is None else conv.bias.detach().float()) + bn_scale_shift(bn)
+    return (W, None if conv.bias is None else conv.bias.detach().float()) + fold.scale_shift(bn)
 
 
 def fold_first_layer(conv, bn, D, xyz_first):
@@ -203,7 +187,7 @@ def sa_point_transform(xyz, points, Wt, Wts=None):
     xyz (B,N,3), points (B,N,D) or None, Wt (D+3, C1) -> (B,N,C1).  Wts = split_point_transform(Wt): the bf16 x 3 form
     (tgn_sa_point_transform_bf16x3, fp32-class rounding at up to 2.7x the rate); None: exact fp32 MFMA (tgn_sa_point_transform)."""
     xyz, _, points, _ = _sa_operands(xyz, None, points, None)
-    Wt = _f32c(Wt)
+    Wt = f32c(Wt, "Wt")
     B, N, _ = xyz.shape
     D = 0 if points is None else points.shape[2]
     if Wt.dim() != 2 or Wt.shape[0] != D + 3:
