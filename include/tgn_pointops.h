@@ -662,9 +662,21 @@ int tgn_seg_scores(int b, int nlab, const int *ins_gt, const int *ins_sem, int i
  * 4. Mesh input of the preprocess path (HOST pointers, CPU code): gen_utils.read_txt_obj_ls (gen_utils.py:207-233).
  * ---------------------------------------------------------------------------------------- */
 /*
- * Text-OBJ reader with the reference loop's semantics (gen_utils.py:211-226): only lines whose first token is exactly
- * "v" or "f" count, reading stops at the first blank line, "a//b" face references are cut at "//", anything int() /
- * float() would reject is an error.  vertices (cap_v,3) double, faces (cap_f,3) int64, 1-based as in the file.
+ * Text-OBJ reader with the reference loop's semantics (gen_utils.py:211-226), quirks included.  The contract, which the native
+ * code meets on an ASCII subset and a Python loop (preprocess.read_obj) on everything else:
+ *   - the file is opened as text: a line ends at "\n", "\r\n" or a lone "\r";
+ *   - each line is split on white space; reading stops at the first line without a token (an empty or blank line);
+ *   - only lines whose first token is exactly "v" or "f" count;
+ *   - "v": float() of tokens 1..3 (further tokens are ignored);
+ *   - "f": tokens 1..3; if the first holds "//", each is cut at its first "//"; then int().  Indices stay 1-based as in the file;
+ *   - whatever float() / int() / the final array build reject is an error (TGN_ERR_INVALID_ARGUMENT natively, ValueError in Python).
+ * The native subset: bytes below 0x80 only, in the whole file (behind the blank line that ends the read too); white space = space,
+ * \t \n \v \f \r and \x1c - \x1f (what str.split() splits ASCII on); no '_' in a parsed token (Python takes "1_0"); coordinate tokens
+ * of at most 400 and face references of at most 60 characters; three tokens behind every "v" and "f".  float() spellings taken
+ * natively: sign, decimal and exponent forms, "inf" / "infinity" / "nan" in any letter case -- not hex, not "nan(...)".
+ * A text outside the subset is TGN_ERR_UNSUPPORTED (tgn_last_error names the line and the reason), never a guess: the caller runs
+ * the contract above in Python.  vertices (cap_v,3) double, faces (cap_f,3) int64.  tgn_obj_count reports exactly the counts
+ * tgn_obj_read then delivers.
  */
 int tgn_obj_count(const char *path, long long *n_vertices, long long *n_faces);
 int tgn_obj_read(const char *path, double *vertices, long long *faces, long long cap_v, long long cap_f,
@@ -702,9 +714,12 @@ int tgn_subdivide_midpoint(long long nv, long long nf, const double *vertices, c
  * with tgn_obj_read's semantics, computes the vertex normals, centres the vertices and maps [y_min, y_max] to [-1, 1]
  * (:48-50, with numpy's summation order), and holds the (n, 7) float64 rows [x y z nx ny nz label] behind *handle.
  * jaw receives the json's "jaw" string (NUL-terminated, at most jaw_cap - 1 bytes).
- * TGN_ERR_UNSUPPORTED: the json is not the plain shape above (floats among the labels, escapes, missing keys) -- the caller
- * falls back to a general json parser; TGN_ERR_INVALID_ARGUMENT: what the reference raises on (unreadable file, bad OBJ
- * token, label count != vertex count).
+ * The json reader takes a top-level object whose "labels" member is an array of plain integers of at most 18 digits and whose
+ * "jaw" member is a string of printable ASCII without escapes; every other member is validated as json.load would read it (strings:
+ * UTF-8, no raw byte below 0x20, only the JSON escapes; numbers, true / false / null, NaN / Infinity / -Infinity; nesting up to 64).
+ * TGN_ERR_UNSUPPORTED: the json is not that (floats among the labels, escapes, missing keys, a byte-order mark, anything json.load
+ * refuses) or the OBJ is outside tgn_obj_read's native subset -- the caller falls back to Python;
+ * TGN_ERR_INVALID_ARGUMENT: what the reference raises on (unreadable file, bad OBJ token, label count != vertex count).
  */
 int tgn_scan_open(const char *obj_path, const char *json_path, double y_min, double y_max, void **handle,
                   long long *n_vertices, char *jaw, int jaw_cap);

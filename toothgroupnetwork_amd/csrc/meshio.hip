@@ -3,13 +3,23 @@
 // vertex normals its open3d call produces (gen_utils.py:228-233).  No device code: it lives in libtgn_pointops.so so
 // that the whole preprocess path binds one C ABI.
 //
-// Reader semantics are the reference loop's, quirks included:
-//   * a line is split on ASCII whitespace; only lines whose FIRST token is exactly "v" or "f" count ("vn", "vt", "#",
-//     "g", ... are skipped);
+// Reader semantics are the reference loop's, quirks included, on the ASCII subset stated below:
+//   * the file is text: a line ends at "\n", "\r\n" or a lone "\r" (Python's universal newlines);
+//   * a line is split on what str.split() splits ASCII text on (space, \t \n \v \f \r, \x1c - \x1f); only lines whose FIRST token
+//     is exactly "v" or "f" count ("vn", "vt", "vv", "#", "g", ... are skipped);
 //   * reading STOPS at the first line without any token (an empty or blank line) -- `if not line: break` (:216);
-//   * "v": tokens 1..3 parsed as Python float() would (strtod; full token must be consumed);
+//   * "v": tokens 1..3 parsed as Python float() would: decimal and exponent forms, "inf" / "infinity" / "nan" in any letter case,
+//     a sign; no hex literal, no "nan(...)"; the full token must be consumed;
 //   * "f": tokens 1..3; if the first contains "//", every token is cut at its first "//" (:221-223); the result must be
 //     a plain integer (int() raises on "1/2/3": status TGN_ERR_INVALID_ARGUMENT here); indices stay 1-based as in the file.
+// OUTSIDE the subset -- status TGN_ERR_UNSUPPORTED, and the caller runs the loop in Python, which decides (preprocess.read_obj):
+//   * a byte >= 0x80 anywhere in the file, behind the blank line that ends the read too (Unicode white space and digits, and what is
+//     no valid text at all, are the text decoder's and str.split()'s business, and the decoder reads ahead of the loop);
+//   * an underscore in one of the three tokens (float("1_0") == 10.0);
+//   * a coordinate token beyond 400 or a face reference beyond 60 characters (the parsers' stack buffers);
+//   * a "v" or "f" line with fewer than three tokens behind it (the reference's np.array build raises or, when every line is short
+//     alike, reshapes).
+// Inside the subset no input gives other arrays than the reference loop, and none is accepted that it raises on, or the reverse.
 // Vertex normals restate open3d's TriangleMesh::ComputeVertexNormals (0.13+: area-weighted sum of cross(v1-v0, v2-v0)
 // over the triangles in file order, then normalisation, (0,0,1) where the result is NaN) in double precision.  open3d is
 // not installed in the build container: PARITY UNPINNED for the normals.
@@ -27,7 +37,18 @@
 
 namespace tgn {
 
-static bool is_ws(char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '\v' || c == '\f'; }
+// What Python's str.split() splits ASCII text on: space (bit 0x20), \t \n \v \f \r (bits 9 - 13) and the separators \x1c - \x1f.
+// One compare and one bit test: this runs on every character of the file (written as range comparisons it costs the reader 10 %).
+static bool is_ws(char c) { return (unsigned char)c <= 0x20 && ((0x1F0003E00ull >> (unsigned char)c) & 1); }
+
+// Whether the text holds a byte >= 0x80.  The reference reads the file as TEXT, so such a byte is part of a code point that may be
+// white space (U+00A0, U+2003), a digit float() / int() take (U+FF11), or no valid text at all: that file goes back to the caller.
+// One OR over the buffer, which the compiler vectorises: a few hundred microseconds for a 100 000-vertex scan.
+static bool has_foreign_byte(const std::string &data) {
+    unsigned char acc = 0;
+    for (const char c : data) acc |= (unsigned char)c;
+    return acc >= 0x80;
+}
 
 struct Tok {
     const char *p;
@@ -48,8 +69,11 @@ static size_t split_ws(const char *s, const char *e, Tok *out, size_t cap) {
     return k;
 }
 
-static bool parse_double(const Tok &t, double *v) {
-    if (t.n == 0 || t.n > 400) return false;
+// What a number parser says about a token: it is the number, float() / int() raise on it, or it lies outside the subset this
+// reader takes (an underscore between digits, which Python allows; a token beyond the stack buffers) and Python decides.
+enum Parse { kParsed = 0, kBad = 1, kOutside = 2 };
+
+static bool parse_double_ascii(const Tok &t, double *v) {
     // Decimal tokens (every coordinate of a real scan): std::from_chars is correctly rounded like float() / strtod and does not
     // go through the locale.  The other spellings float() takes ("inf", "nan", ...) go through strtod below.
     const char *b = t.p, *e = t.p + t.n;
@@ -70,7 +94,7 @@ static bool parse_double(const Tok &t, double *v) {
         // overflow / underflow: strtod's inf / 0 below
     }
     for (const char *c = b; c < e; ++c)
-        if (*c == 'x' || *c == 'X') return false;                                       // float() takes no hex literals
+        if (*c == 'x' || *c == 'X' || *c == '(') return false;                         // float() takes no hex literals and no "nan(...)"
     char buf[408];
     memcpy(buf, t.p, t.n);
     buf[t.n] = 0;
@@ -80,7 +104,14 @@ static bool parse_double(const Tok &t, double *v) {
     return end == buf + t.n;
 }
 
-static bool parse_face_index(Tok t, bool cut, long long *v) {
+static Parse parse_double(const Tok &t, double *v) {
+    if (t.n > 400) return kOutside;
+    if (t.n != 0 && parse_double_ascii(t, v)) return kParsed;
+    return memchr(t.p, '_', t.n) ? kOutside : kBad;                                     // (off the hot path: only a token that failed)
+}
+
+static Parse parse_face_index(Tok t, bool cut, long long *v) {
+    const Tok whole = t;
     if (cut) {
         for (size_t i = 0; i + 1 < t.n; ++i)
             if (t.p[i] == '/' && t.p[i + 1] == '/') {
@@ -88,7 +119,9 @@ static bool parse_face_index(Tok t, bool cut, long long *v) {
                 break;
             }
     }
-    if (t.n == 0 || t.n > 60) return false;
+    if (t.n > 60) return kOutside;
+    const auto failed = [&] { return memchr(whole.p, '_', whole.n) ? kOutside : kBad; };   // (only a token that failed pays for this)
+    if (t.n == 0) return failed();
     {   // [+-]digits, at most 18 of them: what every face of a real scan is
         const char *c = t.p, *e = t.p + t.n;
         const bool neg = *c == '-';
@@ -98,9 +131,9 @@ static bool parse_face_index(Tok t, bool cut, long long *v) {
             for (; c < e && *c >= '0' && *c <= '9'; ++c) r = r * 10 + (*c - '0');
             if (c == e) {
                 *v = neg ? -r : r;
-                return true;
+                return kParsed;
             }
-            return false;   // a non-digit: int() raises
+            return failed();   // a non-digit: int() raises
         }
     }
     char buf[64];
@@ -109,7 +142,7 @@ static bool parse_face_index(Tok t, bool cut, long long *v) {
     char *end = nullptr;
     errno = 0;
     *v = strtoll(buf, &end, 10);
-    return end == buf + t.n && errno == 0;
+    return end == buf + t.n && errno == 0 ? kParsed : failed();
 }
 
 static bool has_double_slash(const Tok &t) {
@@ -137,28 +170,46 @@ static int read_file(const char *path, std::string &data) {
     return TGN_OK;
 }
 
-// One pass over the text; vertices / faces may be null (counting pass).
+static int outside_subset(long long line_no, const char *why) {
+    set_error("tgn_obj_read: line %lld: %s: outside the subset the native reader takes, Python's loop decides", line_no, why);
+    return TGN_ERR_UNSUPPORTED;
+}
+
+// One pass over the text; vertices / faces may be null (counting pass).  A line ends at "\n", "\r\n" or a lone "\r", as in the
+// text mode the reference opens the file in.  TGN_ERR_UNSUPPORTED: the text leaves the subset stated at the top of this file.
 static int parse_obj(const std::string &data, double *vertices, long long *faces, long long cap_v, long long cap_f,
                      long long *nv_out, long long *nf_out, std::vector<double> *vsink = nullptr,
                      std::vector<long long> *fsink = nullptr) {
+    if (has_foreign_byte(data)) {
+        set_error("tgn_obj_read: a byte >= 0x80 in the file: outside the subset the native reader takes, Python's loop decides");
+        return TGN_ERR_UNSUPPORTED;
+    }
     const char *s = data.data(), *end = s + data.size();
+    const bool any_cr = memchr(s, '\r', data.size()) != nullptr;   // (most files hold none: then a line costs one memchr, as before)
+    const char *nl = nullptr;   // the next '\n' at or behind s (end: none), found once per line feed even in a text of lone '\r's
     long long nv = 0, nf = 0, line_no = 0;
     while (s < end) {
-        const char *e = (const char *)memchr(s, '\n', (size_t)(end - s));
-        const char *next = e ? e + 1 : end;
-        if (!e) e = end;
+        if (!nl || nl < s) {
+            nl = (const char *)memchr(s, '\n', (size_t)(end - s));
+            if (!nl) nl = end;
+        }
+        const char *e = nl;
+        const char *next = e < end ? e + 1 : end;
+        if (any_cr)
+            if (const char *cr = (const char *)memchr(s, '\r', (size_t)(e - s))) {
+                e = cr;
+                next = (cr + 1 < end && cr[1] == '\n') ? cr + 2 : cr + 1;
+            }
         ++line_no;
         Tok t[4];
         const size_t k = split_ws(s, e, t, 4);
         if (k == 0) break;   // `if not line: break`
         if (t[0].n == 1 && t[0].p[0] == 'v') {
-            if (k < 4) {
-                set_error("tgn_obj_read: line %lld: a vertex needs three coordinates", line_no);
-                return TGN_ERR_INVALID_ARGUMENT;
-            }
+            if (k < 4) return outside_subset(line_no, "a vertex with fewer than three coordinates (numpy's array build decides)");
             double c[3];
             for (int i = 0; i < 3; ++i)
-                if (!parse_double(t[1 + i], &c[i])) {
+                if (const Parse r = parse_double(t[1 + i], &c[i])) {
+                    if (r == kOutside) return outside_subset(line_no, "a coordinate with '_' or beyond 400 characters");
                     set_error("tgn_obj_read: line %lld: could not convert a coordinate to float", line_no);
                     return TGN_ERR_INVALID_ARGUMENT;
                 }
@@ -174,14 +225,12 @@ static int parse_obj(const std::string &data, double *vertices, long long *faces
             }
             ++nv;
         } else if (t[0].n == 1 && t[0].p[0] == 'f') {
-            if (k < 4) {
-                set_error("tgn_obj_read: line %lld: a face needs three vertex references", line_no);
-                return TGN_ERR_INVALID_ARGUMENT;
-            }
+            if (k < 4) return outside_subset(line_no, "a face with fewer than three references (numpy's array build decides)");
             const bool cut = has_double_slash(t[1]);
             long long idx[3];
             for (int i = 0; i < 3; ++i)
-                if (!parse_face_index(t[1 + i], cut, &idx[i])) {
+                if (const Parse r = parse_face_index(t[1 + i], cut, &idx[i])) {
+                    if (r == kOutside) return outside_subset(line_no, "a face reference with '_' or beyond 60 characters");
                     set_error("tgn_obj_read: line %lld: invalid literal for int() in a face", line_no);
                     return TGN_ERR_INVALID_ARGUMENT;
                 }
@@ -207,7 +256,8 @@ static int parse_obj(const std::string &data, double *vertices, long long *faces
 
 // ---- the ground-truth json of a scan (preprocess_data.py:37-38): {"jaw": "upper" | "lower", "labels": [FDI numbers], ...}.
 // A strict reader for exactly that: a top-level object whose "labels" member is an array of plain integers and whose "jaw"
-// member is a string without escapes.  Anything else is TGN_ERR_UNSUPPORTED and the caller goes through Python's json.
+// member is a string of printable ASCII without escapes; the other members may be any JSON, which is VALIDATED as it is skipped (a
+// document json.load refuses is never taken).  Anything else is TGN_ERR_UNSUPPORTED and the caller goes through Python's json.
 struct JsonCur {
     const char *s, *e;
     void ws() {
@@ -221,7 +271,9 @@ struct JsonCur {
         }
         return false;
     }
-    // s at the opening quote; leaves s behind the closing one.  plain: no backslash inside.
+    // s at the opening quote; leaves s behind the closing one.  plain: no backslash inside.  False for what json.load refuses in a
+    // string: a raw byte below 0x20, an escape other than \" \\ \/ \b \f \n \r \t \uXXXX, bytes that are not UTF-8 (the file is
+    // opened as text; Python's decoder takes neither overlong forms nor surrogates nor anything above U+10FFFF).
     bool string(const char **b, size_t *n, bool *plain) {
         ws();
         if (s >= e || *s != '"') return false;
@@ -229,19 +281,46 @@ struct JsonCur {
         *b = s;
         *plain = true;
         while (s < e && *s != '"') {
-            if (*s == '\\') {
+            const unsigned char c = (unsigned char)*s;
+            if (c < 0x20) return false;
+            if (c == '\\') {
                 *plain = false;
+                if (++s >= e) return false;
+                if (*s == 'u') {
+                    if (e - s < 5) return false;
+                    for (int i = 1; i <= 4; ++i) {
+                        const char h = s[i];
+                        if (!((h >= '0' && h <= '9') || (h >= 'a' && h <= 'f') || (h >= 'A' && h <= 'F'))) return false;
+                    }
+                    s += 5;
+                } else if (*s == '"' || *s == '\\' || *s == '/' || *s == 'b' || *s == 'f' || *s == 'n' || *s == 'r' || *s == 't') {
+                    ++s;
+                } else {
+                    return false;
+                }
+            } else if (c < 0x80) {
                 ++s;
+            } else {
+                const int len = c >= 0xf0 ? 4 : c >= 0xe0 ? 3 : 2;
+                if (c < 0xc2 || c > 0xf4 || e - s < len) return false;
+                const unsigned char c1 = (unsigned char)s[1];
+                const unsigned char lo = c == 0xe0 ? 0xa0 : c == 0xf0 ? 0x90 : 0x80;      // no overlong forms
+                const unsigned char hi = c == 0xed ? 0x9f : c == 0xf4 ? 0x8f : 0xbf;      // no surrogates, nothing above U+10FFFF
+                if (c1 < lo || c1 > hi) return false;
+                for (int i = 2; i < len; ++i)
+                    if (((unsigned char)s[i] & 0xc0) != 0x80) return false;
+                s += len;
             }
-            ++s;
         }
         if (s >= e) return false;
         *n = (size_t)(s - *b);
         ++s;
         return true;
     }
-    // skips any value (nesting by bracket counting, strings honoured)
-    bool skip_value() {
+    // Validates and skips any value the way json.load reads it: recursive descent.  Nesting beyond kMaxDepth is false too (Python
+    // may well take it): false only ever means that the document goes back to the caller.
+    static constexpr int kMaxDepth = 64;
+    bool skip_value(int depth = 0) {
         ws();
         if (s >= e) return false;
         if (*s == '"') {
@@ -251,26 +330,22 @@ struct JsonCur {
             return string(&b, &n, &plain);
         }
         if (*s == '{' || *s == '[') {
-            long depth = 0;
-            while (s < e) {
-                if (*s == '"') {
+            if (depth >= kMaxDepth) return false;
+            const bool object = *s == '{';
+            const char close = object ? '}' : ']';
+            ++s;
+            if (eat(close)) return true;
+            for (;;) {
+                if (object) {
                     const char *b;
                     size_t n;
                     bool plain;
-                    if (!string(&b, &n, &plain)) return false;
-                    continue;
+                    if (!string(&b, &n, &plain) || !eat(':')) return false;
                 }
-                if (*s == '{' || *s == '[') ++depth;
-                if (*s == '}' || *s == ']') {
-                    --depth;
-                    if (depth == 0) {
-                        ++s;
-                        return true;
-                    }
-                }
-                ++s;
+                if (!skip_value(depth + 1)) return false;
+                if (eat(',')) continue;
+                return eat(close);
             }
-            return false;
         }
         const char *b = s;
         while (s < e && *s != ',' && *s != '}' && *s != ']' && *s != ' ' && *s != '\t' && *s != '\n' && *s != '\r') ++s;
@@ -327,6 +402,27 @@ struct JsonCur {
     }
 };
 
+// Whether the key [b, b + n) -- validated by JsonCur::string, with at least one escape -- decodes to `word` (ASCII letters): only
+// \uXXXX can spell a letter, every other escape stands for a character no word here holds.
+static bool escaped_key_spells(const char *b, size_t n, const char *word) {
+    size_t i = 0;
+    for (; *word; ++word) {
+        if (i >= n) return false;
+        unsigned c = (unsigned char)b[i++];
+        if (c == '\\') {
+            if (b[i] != 'u') return false;
+            c = 0;
+            for (int k = 1; k <= 4; ++k) {
+                const char h = b[i + k];
+                c = c * 16 + (unsigned)(h <= '9' ? h - '0' : (h | 0x20) - 'a' + 10);
+            }
+            i += 5;
+        }
+        if (c != (unsigned char)*word) return false;
+    }
+    return i == n;
+}
+
 static int parse_scan_json(const std::string &data, std::vector<long long> &labels, std::string &jaw) {
     JsonCur c{data.data(), data.data() + data.size()};
     bool have_labels = false, have_jaw = false;
@@ -337,7 +433,8 @@ static int parse_scan_json(const std::string &data, std::vector<long long> &labe
             size_t kn;
             bool plain;
             if (!c.string(&kb, &kn, &plain) || !c.eat(':')) return TGN_ERR_UNSUPPORTED;
-            if (!plain) return TGN_ERR_UNSUPPORTED;          // an escaped key could spell "labels" / "jaw"
+            if (!plain && (escaped_key_spells(kb, kn, "labels") || escaped_key_spells(kb, kn, "jaw")))
+                return TGN_ERR_UNSUPPORTED;                  // "l\u0061bels": Python's business
             if (kn == 6 && !memcmp(kb, "labels", 6)) {
                 if (!c.int_array(labels)) return TGN_ERR_UNSUPPORTED;
                 have_labels = true;
@@ -488,7 +585,8 @@ TGN_API int tgn_vertex_normals(const double *vertices, long long nv, const long 
 // float64 rows [x y z nx ny nz label] the reference holds in `labeled_vertices` before sampling.  The arithmetic repeats
 // numpy's: np.mean(axis=0) of a C-ordered (n, 3) view is a row-by-row running sum per column, and
 // ((v - mean) - Ymin) / (Ymax - Ymin) * 2 - 1 is evaluated per element in that order.
-// Returns TGN_ERR_UNSUPPORTED for a json this strict reader does not take (the caller then uses Python's json module) and
+// Returns TGN_ERR_UNSUPPORTED for a json this strict reader does not take or an OBJ outside the native subset (the caller then
+// takes the Python path: json module, read_obj's Python loop) and
 // TGN_ERR_INVALID_ARGUMENT where the reference raises (unreadable file, bad OBJ token, label count != vertex count).
 TGN_API int tgn_scan_open(const char *obj_path, const char *json_path, double y_min, double y_max, void **handle,
                           long long *n_vertices, char *jaw, int jaw_cap) {
@@ -520,7 +618,7 @@ TGN_API int tgn_scan_open(const char *obj_path, const char *json_path, double y_
     long long nv = 0, nf = 0;
     v.reserve(data.size() / 24);                                // ~ "v -12.345678 -12.345678 -12.345678\n" per vertex, two
     f.reserve(data.size() / 12);                                //   "f 123456 123457 123458\n" per vertex: a first guess
-    if (int rc = parse_obj(data, nullptr, nullptr, 0, 0, &nv, &nf, &v, &f)) return rc;
+    if (int rc = parse_obj(data, nullptr, nullptr, 0, 0, &nv, &nf, &v, &f)) return rc;   // (TGN_ERR_UNSUPPORTED goes up as it is)
     nrm.resize((size_t)nv * 3);
     for (auto &x : f) x -= 1;                                   // gen_utils.py:226
     if (int rc = tgn_vertex_normals(v.data(), nv, f.data(), nf, nrm.data())) return rc;
@@ -573,7 +671,8 @@ TGN_API int tgn_scan_take(void *handle, double *labeled, float *xyz32) {
         set_error("tgn_scan_take: null handle");
         return TGN_ERR_INVALID_ARGUMENT;
     }
-    if (labeled) memcpy(labeled, sc->labeled.data(), sc->labeled.size() * sizeof(double));
+    if (labeled && !sc->labeled.empty())   // (a scan without vertices in a fresh object: data() is null, which memcpy must not be given)
+        memcpy(labeled, sc->labeled.data(), sc->labeled.size() * sizeof(double));
     if (xyz32)
         for (long long i = 0; i < sc->n; ++i)
             for (int a = 0; a < 3; ++a) xyz32[i * 3 + a] = (float)sc->labeled[i * 7 + a];

@@ -28,13 +28,45 @@ Y_AXIS_MIN = -36.9843781139949
 N_SAMPLED = 24000                    # preprocess_data.py:55
 
 
+def _read_obj_text(path):
+    """The contract of tgn_obj_read (include/tgn_pointops.h) in Python, for the texts outside the native reader's ASCII subset:
+    open as text, split each line on white space, stop at the first line without a token, float() of tokens 1..3 behind "v",
+    int() of tokens 1..3 behind "f" (each cut at its first "//" when the first holds one), then the array build.  Every refusal
+    -- the text decoder's, float()'s, int()'s, a face without tokens, an index beyond int64, rows of unequal length -- is a
+    ValueError."""
+    vertices, faces = [], []
+    try:
+        with open(path, "r") as st:
+            while True:
+                tokens = st.readline().split()
+                if not tokens:
+                    break
+                if tokens[0] == "v":
+                    vertices.append([float(t) for t in tokens[1:4]])
+                elif tokens[0] == "f":
+                    refs = tokens[1:4]
+                    if "//" in refs[0]:
+                        refs = [t.split("//")[0] for t in refs]
+                    faces.append([int(t) for t in refs])
+        return np.array(vertices, dtype=np.float64).reshape(-1, 3), np.array(faces, dtype=np.int64).reshape(-1, 3)
+    except (IndexError, OverflowError, OSError) as exc:
+        raise ValueError(f"read_obj: {path}: {exc}") from exc
+
+
 def read_obj(path):
     """(vertices (n,3) float64, faces (m,3) int64, 1-based) of a text OBJ, with the reference loop's semantics
-    (gen_utils.py:211-226): see tgn_obj_read in include/tgn_pointops.h.  Raises ValueError where float() / int() would."""
+    (gen_utils.py:211-226): see tgn_obj_read in include/tgn_pointops.h.  Raises ValueError where the reference loop raises
+    (float(), int(), the text decoder, the array build) and returns its arrays where it returns.  The native reader takes the
+    ASCII subset stated there (bytes below 0x80, no '_' in a number, tokens within 400 / 60 characters, three tokens behind every
+    "v" and "f"); a text outside it comes back as TGN_ERR_UNSUPPORTED and is read by the same contract in Python
+    (_read_obj_text), slowly and with the same result the reference loop gives."""
     L = _lib.lib()
     nv, nf = ctypes.c_longlong(0), ctypes.c_longlong(0)
     bpath = os.fsencode(path)
-    if L.tgn_obj_count(bpath, ctypes.byref(nv), ctypes.byref(nf)):
+    rc = L.tgn_obj_count(bpath, ctypes.byref(nv), ctypes.byref(nf))
+    if rc == _lib.ERR_UNSUPPORTED:
+        return _read_obj_text(path)
+    if rc:
         raise ValueError(L.tgn_last_error().decode("utf-8", "replace"))
     v = np.empty((max(nv.value, 0), 3), dtype=np.float64)
     f = np.empty((max(nf.value, 0), 3), dtype=np.int64)
@@ -206,8 +238,11 @@ def load_scan_native(obj_path, json_path, with_xyz32=False, pools=None):
     """load_scan in ONE native call that never holds the interpreter lock (tgn_scan_open / tgn_scan_take): what the sharded
     runner's load threads use, since json.load, the label remap and the numpy glue of load_scan serialise on the GIL.
     -> (labeled_vertices, base_name, jaw, xyz32 or None); xyz32 = float32 copy of the coordinates when with_xyz32 and the
-    scan has more than N_SAMPLED vertices.  Returns None when the json is not the plain {"jaw": str, "labels": [int]} shape
-    (the caller then takes load_scan); raises ValueError where load_scan raises.  pools: optional (ArrayPool(7, float64),
+    scan has more than N_SAMPLED vertices.  Returns None when the native reader hands the scan back (TGN_ERR_UNSUPPORTED): the json
+    is not a top-level object with "labels": [plain ints of at most 18 digits] and "jaw": printable ASCII without escapes, beside
+    any other valid members -- which includes every document json.load refuses --, or the OBJ is outside the ASCII subset of
+    read_obj; the caller then takes load_scan, which decides.  Rows are returned only where load_scan returns the same bits;
+    raises ValueError where load_scan raises.  pools: optional (ArrayPool(7, float64),
     ArrayPool(3, float32)) the two arrays are taken from (the caller gives them back)."""
     L = _lib.lib()
     handle, nv = ctypes.c_void_p(), ctypes.c_longlong(0)
