@@ -19,13 +19,17 @@ available where the fixtures are made.  A mesh that still has no more than 24 00
 reference fails on it too (gen_utils.py:136-137).
 
 TSegNetInferencePipeLine is the same for tsegnet (inference_pipelines/inference_pipeline_tsegnet.py): the centroid module, the join and
-the painting on the GPU (tsegnet.py), pinned against the reference's class in the same way (tests/golden/make_golden_r11_tsegnet.py)."""
+the painting on the GPU (tsegnet.py), pinned against the reference's class in the same way (tests/golden/make_golden_r11_tsegnet.py).
+
+TgnInferencePipeLine is tgnet's (inference_pipelines/inference_pipeline_tgn.py): two GroupingNetworkModules with the boundary-aware
+resampling between them (tgnet.py), pinned in the same way (tests/golden/make_golden_r16_tgnet.py).  make_inference_pipeline is the
+reference's factory (inference_pipelines/inference_pipeline_maker.py) with its six model names."""
 import time
 
 import numpy as np
 import torch
 
-from . import preprocess, resample, tsegnet
+from . import preprocess, resample, tgnet, tsegnet
 
 N_POINTS = 24000
 
@@ -158,6 +162,140 @@ class TSegNetInferencePipeLine:
         t.append(time.perf_counter())
         self.times = dict(zip(("load", "sample", "centroids", "join", "segmentation", "paint", "transfer"), np.diff(t).tolist()))
         return {"sem": result.reshape(-1), "ins": result.reshape(-1)}
+
+
+def first_occurrences(vertices):
+    """vertices (n, 3) -> (keep (u,) int64 ascending, to_kept (n,) int64): the rows open3d's remove_duplicated_vertices keeps -- the
+    first occurrence, in file order, of every distinct coordinate triple (exact equality of the three coordinates) -- and for every
+    row the position in `keep` of the row that stands for it."""
+    v = np.ascontiguousarray(np.asarray(vertices)[:, :3])
+    _, first, inverse = np.unique(v, axis=0, return_index=True, return_inverse=True)
+    keep = np.sort(first)
+    return keep.astype(np.int64), np.searchsorted(keep, first[inverse.reshape(-1)]).astype(np.int64)
+
+
+class TgnInferencePipeLine:
+    """inference_pipelines/inference_pipeline_tgn.py:10-157 (the "tgnet" model) on this package's operators: pipeline(path) ->
+    {"sem": FDI-style tooth number per vertex, "ins": instance per vertex}.  `first_module` and `bdl_module` are two
+    nets.GroupingNetworkModule (five-stage over the 24 000 sampled points, two-stage over the boundary-aware resampling), the
+    reference's own classes, or stand-ins with the same call and output dict.  Stages, with `times` holding their durations:
+      load       the native reader; duplicated vertices collapse to their first occurrence (first_occurrences), as open3d's
+                 remove_duplicated_vertices does, a kept vertex keeping its normal and the triangles re-indexed
+      sample     the pipeline's normalisation, one midpoint subdivision below 24 000 vertices (points_to_sample: those rows are then
+                 also what the boundary pass resamples, :35-39), FPS to 24 000
+      first      the first module without labels, tgnet.first_instances
+      resample   tgnet.boundary_resample: boundary rows by np.random.permutation of numpy's GLOBAL generator, the rest by FPS
+      boundary   the boundary module called as bdl_module([feats, labels - 1], test=True) -- the labels ranked densely first
+                 (tgnet.dense_rank_labels) -- and tgnet.second_instances
+      merge      tgnet.number_teeth, tgnet.merge_boundary
+      transfer   the nearest of the 24 000 + boundary points per vertex (preprocess.transfer_labels), the FDI relabelling of `sem` only
+
+    Deviations from the reference, all deliberate: k-means starts from the first-pass instances' means instead of k-means++ seeds
+    drawn from numpy's global generator (tgnet.py); EVERY vertex of the file gets a label, a duplicate its first occurrence's (the
+    reference returns labels for the de-duplicated vertices only, which results.process cannot write; identical where a file has no
+    duplicates); the native reader keeps file order where the reference loads through trimesh, which "can change vertex order"
+    (gen_utils.py:202).  Parity with open3d's subdivision and normals is unpinned as for the other pipelines.  A vertex equally near
+    two of the 24 000 + boundary points takes the one with the lower index (the first pass's); the KDTree leaves that open.  Where the
+    reference dies by accident -- no foreground, fewer than three instances -- tgnet.py raises ValueError saying which; more than 64
+    first-pass instances are a ValueError too (crops.MAX_CLUSTERS)."""
+
+    STAGES = ("load", "sample", "first", "resample", "boundary", "merge", "transfer")
+
+    def __init__(self, first_module, bdl_module, boundary_sampling_info=None):
+        self.first_module = first_module
+        self.bdl_module = bdl_module
+        self.boundary_sampling_info = dict(tgnet.DEFAULT_INFO if boundary_sampling_info is None else boundary_sampling_info)
+        self.scaler = 1.8
+        self.shifter = 0.8
+        self.times = {}
+
+    @classmethod
+    def from_config(cls, config):
+        """The reference's constructor (:11-22): config["fps_model_info"] and config["boundary_model_info"] each hold a
+        "model_parameter" dict for GroupingNetworkModule and a "load_ckpt_path"; config["boundary_sampling_info"] is the resampling's."""
+        from . import nets
+        modules = []
+        for key in ("fps_model_info", "boundary_model_info"):
+            module = nets.GroupingNetworkModule(config[key])
+            module.cuda()
+            module.load_state_dict(torch.load(config[key]["load_ckpt_path"]))
+            modules.append(module.eval())
+        return cls(modules[0], modules[1], config.get("boundary_sampling_info"))
+
+    def __call__(self, stl_path):
+        t = [time.perf_counter()]
+        _, mesh = preprocess.read_txt_obj_ls(stl_path, ret_mesh=True)
+        keep, to_kept = first_occurrences(mesh["vertices"])
+        triangles = to_kept[mesh["triangles"]]
+        t.append(time.perf_counter())
+        vertices = normalise_for_inference(mesh["vertices"][keep], self.scaler, self.shifter)
+        org_feats = np.concatenate([vertices, mesh["vertex_normals"][keep]], axis=1)
+        bdl_feats = points_to_sample(org_feats, triangles)
+        idx = resample.fps(bdl_feats[:, :3], N_POINTS, prefix=True)
+        sampled_feats = bdl_feats[idx[:N_POINTS]]
+        t.append(time.perf_counter())
+        with torch.no_grad():
+            inp = torch.from_numpy(np.ascontiguousarray(sampled_feats.astype("float32"))[None]).cuda().permute(0, 2, 1).contiguous()
+            first = tgnet.first_instances(inp, self.first_module([inp]))
+            first = {k: v.cpu().numpy() for k, v in first.items()}
+            t.append(time.perf_counter())
+            feats, labels, only_bdl, _ = tgnet.boundary_resample(bdl_feats, sampled_feats, first["ins"], self.boundary_sampling_info)
+            t.append(time.perf_counter())
+            inp = torch.from_numpy(np.ascontiguousarray(feats.astype("float32"))[None]).cuda().permute(0, 2, 1).contiguous()
+            lab = torch.from_numpy(tgnet.dense_rank_labels(labels)[None, None]).cuda()
+            second = tgnet.second_instances(inp, lab, self.bdl_module([inp, lab], test=True))
+            nb = only_bdl.shape[0]
+            bdl_xyz, bdl_ins = second["xyz"][:nb].cpu().numpy(), second["ins"][:nb].cpu().numpy()
+        t.append(time.perf_counter())
+        sem, ins = tgnet.number_teeth(first["xyz"], first["ins"], first["sem"])
+        points, ins, sem = tgnet.merge_boundary(first["xyz"], ins, sem, bdl_xyz, bdl_ins)
+        t.append(time.perf_counter())
+        nearest = preprocess.transfer_labels(points, np.arange(points.shape[0]), org_feats[:, :3])
+        sem, ins = fdi_from_classes(sem[nearest]), ins[nearest]
+        t.append(time.perf_counter())
+        self.times = dict(zip(self.STAGES, np.diff(t).tolist()))
+        return {"sem": sem[to_kept].reshape(-1), "ins": ins[to_kept].reshape(-1)}
+
+
+_FIVE_STAGE = {"input_feat": 6, "stride": [1, 4, 4, 4, 4], "nstride": [2, 2, 2, 2], "nsample": [36, 24, 24, 24, 24], "blocks": [2, 3, 4, 6, 3],
+               "block_num": 5, "planes": [32, 64, 128, 256, 512], "crop_sample_size": 3072}
+_BOUNDARY = {"input_feat": 6, "stride": [1, 1], "nsample": [36, 24], "blocks": [2, 3], "block_num": 2, "planes": [16, 32],
+             "crop_sample_size": 3072}
+MODEL_NAMES = ("tsegnet", "tgnet", "pointnet", "pointnetpp", "dgcnn", "pointtransformer")
+
+
+def inference_config(model_name, ckpt_path_ls=(None, None)):
+    """The configuration dict inference_pipeline_maker.py:3-104 builds for a model name ({} for the three models it gives none)."""
+    if model_name == "tsegnet":
+        return {"model_info": {"model_parameter": dict(_FIVE_STAGE)}, "run_tooth_segmentation_module": True}
+    if model_name == "tgnet":
+        return {"fps_model_info": {"model_parameter": dict(_FIVE_STAGE), "load_ckpt_path": ckpt_path_ls[0]},
+                "boundary_model_info": {"model_parameter": dict(_BOUNDARY), "load_ckpt_path": ckpt_path_ls[1]},
+                "boundary_sampling_info": dict(tgnet.DEFAULT_INFO)}
+    if model_name == "pointtransformer":
+        return {"model_info": {"model_parameter": dict(_FIVE_STAGE)}}
+    if model_name in MODEL_NAMES:
+        return {}
+    raise ValueError(f"undefined model {model_name!r}: the names are {', '.join(MODEL_NAMES)}")
+
+
+def make_inference_pipeline(model_name, ckpt_path_ls):
+    """inference_pipelines/inference_pipeline_maker.py:3-106: the pipeline of one of the reference's six model names with its
+    checkpoints loaded (ckpt_path_ls: one path, two for "tgnet": first module, boundary module), on the GPU, in eval mode.  The one
+    place that says which module and which pipeline a name means.  Another name: ValueError (the reference raises a string)."""
+    from . import nets
+    config = inference_config(model_name, ckpt_path_ls)
+    if model_name == "tgnet":
+        return TgnInferencePipeLine.from_config(config)
+    module, pipeline = {"tsegnet": (lambda: nets.TSegNetModule(config), TSegNetInferencePipeLine),
+                        "pointnet": (lambda: nets.PointFirstModule({}), InferencePipeLine),
+                        "pointnetpp": (lambda: nets.PointPpFirstModule({}), InferencePipeLine),
+                        "dgcnn": (lambda: nets.DGCnnModule({}), InferencePipeLine),
+                        "pointtransformer": (lambda: nets.PointTransformerModule(config["model_info"]), InferencePipeLine)}[model_name]
+    module = module()
+    module.load_state_dict(torch.load(ckpt_path_ls[0]))
+    module.cuda()
+    return pipeline(module.eval())
 
 
 def infer_scans(paths, model, batch=8, workers=None):

@@ -25,6 +25,10 @@ of the fused eval paths.  Parameter names and shapes equal the reference classes
                        all crops as one batch.  Without labels the centroids come from on-device clustering (cluster.py, which
                        reaches crop.hip's kNN and label means through crops.py).  The offset, direction and chamfer terms of its loss are
                        losses.grouping_loss_terms (fused kernels, csrc/loss.hip); the cbl terms stay the reference's Python.
+                       `block_num` 5 (tgnet_fps, tgnet's first module) or 2 (tgnet's boundary module,
+                       inference_pipeline_maker.py:43-54); up to crops.MAX_CLUSTERS labels.
+  PointPpFirstModule, PointTransformerModule  models/modules/pointnet_pp.py:73-92 and models/modules/point_transformer.py:4-28: the wrappers
+                       whose state_dict the "pointnetpp" and "pointtransformer" checkpoints hold (inference.make_inference_pipeline).
   TSegNetModule        models/modules/tsegnet.py:10-88 (the "tsegnet" model): TsgCentroidNet, the join on the GPU (tsegnet.py of this
                        package: proposal filter, DBSCAN, cluster means, crops with the distance feature; the means and the crops'
                        kNN through crops.py's wrappers of crop.hip), TsgSegNet over the crops.
@@ -224,24 +228,33 @@ class MultiHead(nn.Module):
 
 
 class PointTransformerSeg(nn.Module):
+    """`block_num` stages (cbl_point_transformer_module.py:46-57): 5, the network the reference ships for every scan-level model, or 2,
+    tgnet's boundary network (inference_pipeline_maker.py:43-54: planes [16, 32], stride [1, 1]).  The top decoder stage is the head
+    (`TransitionUp(in, None)`), and the heads' latent width is the reference's fixed base_fdim = 32 (:227), not planes[0]."""
+
+    BASE_FDIM = 32
+
     def __init__(self, c=6, k=17, planes=(32, 64, 128, 256, 512), blocks=(2, 3, 4, 6, 3), stride=(1, 4, 4, 4, 4),
-                 nsample=(36, 24, 24, 24, 24), share_planes=8):
+                 nsample=(36, 24, 24, 24, 24), share_planes=8, block_num=5):
         super().__init__()
-        self.c, self.k = c, k
+        if block_num not in (2, 5):
+            raise ValueError(f"block_num = {block_num}: the reference's forward exists for 2, 3 and 5 stages; 2 and 5 are mirrored")
+        self.c, self.k, self.block_num = c, k, block_num
+        planes = tuple(planes)[:block_num]
         in_planes = c
-        for i in range(5):
+        for i in range(block_num):
             layers = [PT.TransitionDown(in_planes, planes[i], stride[i], nsample[i])]
             in_planes = planes[i]
             layers += [PT.PointTransformerBlock(in_planes, in_planes, share_planes, nsample[i]) for _ in range(1, blocks[i])]
             setattr(self, f"enc{i + 1}", nn.Sequential(*layers))
-        for i in range(4, -1, -1):
-            layers = [PT.TransitionUp(in_planes, None if i == 4 else planes[i])]
+        for i in range(block_num - 1, -1, -1):
+            layers = [PT.TransitionUp(in_planes, None if i == block_num - 1 else planes[i])]
             in_planes = planes[i]
             layers.append(PT.PointTransformerBlock(in_planes, in_planes, share_planes, nsample[i]))
             setattr(self, f"dec{i + 1}", nn.Sequential(*layers))
-        self.mask_head = MultiHead(planes, 2, planes[0])
-        self.cls_head = MultiHead(planes, k, planes[0])
-        self.offset_head = MultiHead(planes, 3, planes[0])
+        self.mask_head = MultiHead(planes, 2, self.BASE_FDIM)
+        self.cls_head = MultiHead(planes, k, self.BASE_FDIM)
+        self.offset_head = MultiHead(planes, 3, self.BASE_FDIM)
 
     @_one_index_check
     def forward(self, inputs, all_offsets=False):
@@ -255,12 +268,13 @@ class PointTransformerSeg(nn.Module):
         p = pxo[:, :, :3].reshape(-1, 3).contiguous()
         o = pointops.register_offsets(torch.arange(1, B + 1, dtype=torch.int32, device=feats.device) * N,
                                       [N * (i + 1) for i in range(B)])
+        stages = self.block_num
         down, cur = [], [p, x, o]
-        for i in range(1, 6):
+        for i in range(1, stages + 1):
             cur = getattr(self, f"enc{i}")(cur)
             down.append(cur)
-        up, above = [None] * 5, None
-        for i in range(4, -1, -1):
+        up, above = [None] * stages, None
+        for i in range(stages - 1, -1, -1):
             pi, xi, oi = down[i]
             dec = getattr(self, f"dec{i + 1}")
             head = dec[0]([pi, xi, oi]) if above is None else dec[0]([pi, xi, oi], above)
@@ -269,6 +283,33 @@ class PointTransformerSeg(nn.Module):
         cls = self.cls_head(up).view(B, N, self.k).permute(0, 2, 1)
         offset = self.offset_head(up).view(B, N, 3).permute(0, 2, 1) if B == 1 or all_offsets else None
         return [cls, offset, None, up[0][1]]
+
+
+class PointPpFirstModule(nn.Module):
+    """models/modules/pointnet_pp.py:73-92 (the "pointnetpp" model): PointNetPPSeg as `first_sem_model`, its class logits as "cls_pred"."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.config = config
+        self.first_sem_model = PointNetPPSeg()
+
+    def forward(self, inputs, test=False):
+        return {"cls_pred": self.first_sem_model(inputs)[6]}
+
+
+class PointTransformerModule(nn.Module):
+    """models/modules/point_transformer.py:4-28 (the "pointtransformer" model): a 17-class PointTransformerSeg as `first_ins_cent_model`."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.config = config
+        mp = config["model_parameter"]
+        self.first_ins_cent_model = PointTransformerSeg(c=mp["input_feat"], k=16 + 1, planes=tuple(mp["planes"]), blocks=tuple(mp["blocks"]),
+                                                        stride=tuple(mp["stride"]), nsample=tuple(mp["nsample"]), block_num=mp.get("block_num", 5))
+
+    def forward(self, inputs, test=False):
+        sem_1, offset_1, mask_1, first_features = self.first_ins_cent_model([inputs[0]])
+        return {"sem_1": sem_1, "offset_1": offset_1, "mask_1": mask_1, "first_features": first_features, "cls_pred": sem_1}
 
 
 class GroupingNetworkModule(nn.Module):
@@ -294,9 +335,12 @@ class GroupingNetworkModule(nn.Module):
         super().__init__()
         self.config = config
         mp = config["model_parameter"]
-        if mp.get("block_num", 5) != 5:
-            raise ValueError(f"block_num = {mp['block_num']}: only the five-stage network (train_configs/tgnet_fps.py) is mirrored")
-        arch = dict(planes=tuple(mp["planes"]), blocks=tuple(mp["blocks"]), stride=tuple(mp["stride"]), nsample=tuple(mp["nsample"]))
+        block_num = mp.get("block_num", 5)
+        if block_num not in (2, 5):
+            raise ValueError(f"block_num = {block_num}: the five-stage network (train_configs/tgnet_fps.py) and tgnet's two-stage boundary "
+                             "network (inference_pipeline_maker.py:43-54) are mirrored")
+        arch = dict(planes=tuple(mp["planes"]), blocks=tuple(mp["blocks"]), stride=tuple(mp["stride"]), nsample=tuple(mp["nsample"]),
+                    block_num=block_num)
         class_num = 9
         self.first_ins_cent_model = PointTransformerSeg(c=mp["input_feat"], k=class_num + 1, **arch)
         self.second_ins_cent_model = PointTransformerSeg(c=mp["input_feat"], k=2, **arch)
@@ -317,7 +361,8 @@ class GroupingNetworkModule(nn.Module):
         out = {"sem_1": sem_1, "offset_1": offset_1, "mask_1": mask_1, "first_features": first_features}
         if unlabelled:
             centroids = [self._cluster_centroids(feats[b], sem_1[b], offset_1[b]) for b in range(B)]
-        cr = _crops.tooth_crops(feats, labels, centroids, self.crop_sample_size)
+        # labels: up to crops.MAX_CLUSTERS of them, not the 16 of a ground-truth jaw -- tgnet's boundary pass hands in cluster numbers
+        cr = _crops.tooth_crops(feats, labels, centroids, self.crop_sample_size, num_labels=_crops.MAX_CLUSTERS)
         if labels is not None:
             out["cluster_gt_seg_label"] = cr.cluster_gt_seg_label
         sem_2, offset_2, mask_2, _ = self.second_ins_cent_model([cr.cropped])
