@@ -1,0 +1,70 @@
+#!/usr/bin/env python3
+"""start_train.py over this package: train one of the reference's models from a directory of preprocessed scans
+(`*_sampled_points.npy`, preprocess_data.py's output) on one GPU.
+
+    python tools/train.py --model_name pointnetpp --config_path train_configs/pointnetpp.py --experiment_name run1 \\
+        --input_data_dir_path data_preprocessed --train_data_split_txt_path train.txt --val_data_split_txt_path val.txt --epochs 60
+
+The arguments are start_train.py's, plus --epochs (the reference loops 100 000 times) and --seed (numpy's and torch's generators:
+shuffling, augmentation draws, initial weights, tsegnet's 8-of-T crop choice).  The configuration is the reference's:
+train_configs/train_config_maker.get_default_config merged with the `config` dict of the Python file at --config_path, so the
+reference's own train_configs/*.py files work as they are (for tgnet_fps set the two cbl weights to 0: see training.py).
+Prints the trainer's JSON lines: one per scheduler step, one per epoch.  Checkpoints: ckpts/<experiment_name>.h5 after every epoch,
+ckpts/<experiment_name>_val.h5 at every best validation total; both load into inference.make_inference_pipeline."""
+import argparse
+import importlib.util
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+DEFAULT_AUG = "aug.Augmentator([aug.Scaling([0.85, 1.15]), aug.Rotation([-30,30], 'fixed'), aug.Translation([-0.2, 0.2])])"
+
+
+def get_default_config(experiment_name, input_data_dir_path, train_data_split_txt_path, val_data_split_txt_path):
+    """train_config_maker.get_default_config without its wandb block, which nothing here reads."""
+    return {"generator": {"input_data_dir_path": f"{input_data_dir_path}", "train_data_split_txt_path": f"{train_data_split_txt_path}",
+                          "val_data_split_txt_path": f"{val_data_split_txt_path}", "aug_obj_str": DEFAULT_AUG,
+                          "train_batch_size": 1, "val_batch_size": 1},
+            "checkpoint_path": f"ckpts/{experiment_name}"}
+
+
+def get_train_config(config_path, experiment_name, input_data_dir_path, train_data_split_txt_path, val_data_split_txt_path):
+    """train_config_maker.get_train_config: the defaults, then the top-level keys of the file's `config` over them."""
+    config = get_default_config(experiment_name, input_data_dir_path, train_data_split_txt_path, val_data_split_txt_path)
+    spec = importlib.util.spec_from_file_location("tgn_train_config", config_path)
+    loaded = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(loaded)
+    config.update(loaded.config)
+    return config
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--model_name", default="tsegnet", help="tsegnet | tgnet_fps | pointnet | pointnetpp | dgcnn | pointtransformer")
+    ap.add_argument("--config_path", default="train_configs/tsegnet.py", help="train config file: a Python file with a `config` dict")
+    ap.add_argument("--experiment_name", default="tsegnet_0620", help="names the checkpoints: ckpts/<experiment_name>.h5")
+    ap.add_argument("--input_data_dir_path", default="data_preprocessed_path", help="directory of *_sampled_points.npy")
+    ap.add_argument("--train_data_split_txt_path", default="base_name_train_fold.txt", help="patient ids of the training split, one per line")
+    ap.add_argument("--val_data_split_txt_path", default="base_name_val_fold.txt", help="patient ids of the validation split")
+    ap.add_argument("--epochs", type=int, default=100000, help="epochs to run (the reference's loop count is the default)")
+    ap.add_argument("--seed", type=int, default=None, help="seeds numpy's and torch's generators")
+    args = ap.parse_args(argv)
+
+    import numpy as np
+    import torch
+    from toothgroupnetwork_amd import training
+    if args.seed is not None:
+        np.random.seed(args.seed)
+        torch.manual_seed(args.seed)
+    config = get_train_config(args.config_path, args.experiment_name, args.input_data_dir_path, args.train_data_split_txt_path,
+                              args.val_data_split_txt_path)
+    model = training.make_training_model(args.model_name, config)
+    gen_set = [training.get_generator_set(config["generator"])]
+    print("train_set", len(gen_set[0][0]), file=sys.stderr)
+    print("validation_set", len(gen_set[0][1]), file=sys.stderr)
+    training.Trainer(config=config, model=model, gen_set=gen_set).run(args.epochs)
+
+
+if __name__ == "__main__":
+    main()

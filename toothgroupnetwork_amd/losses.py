@@ -5,6 +5,10 @@
   centroid_loss                                           models/tsg_loss.py:57-61, plus an optional `exists` mask of the centroids
   grouping_loss_terms                                     FpsGroupingNetworkModel.get_loss (models/fps_grouping_network_model.py:8-24)
   tsegnet_centroid_loss_terms                             the three centroid terms of TSegNetModel.get_loss (models/tsegnet_model.py:15-24)
+  first_seg_loss, second_seg_loss, id_loss,               models/tsg_loss.py:63-135 (names and argument order kept): torch compositions with
+  segmentation_loss                                       autograd over crops x 3072 elements, no kernel of their own
+  seg_label_to_cent                                       ops_utils.seg_label_to_cent through crops.label_centroids: 16 slots and an `exists` mask
+  tsegnet_loss_terms                                      all six terms of TSegNetModel.get_loss from the module's output dict and the labels
 
 The reference loops over B x 16 teeth with boolean masks (one host round trip per tooth and scan) and sorts a (B, M, C) distance
 matrix to read two columns; here a forward is the per-tooth counts and centroids (crops.label_centroids), a point pass and a finishing
@@ -24,6 +28,7 @@ A label outside [-1, 16) latches _lib.INDEX_ERROR_CROP on the stream, as crops.l
 Arguments: floating tensors of any dtype and strides are cast and packed to contiguous float32 by differentiable torch operations in
 front of the kernels, so the gradient comes back in the caller's dtype and layout; labels go through crops.labels_2d; anything else
 raises TypeError / ValueError naming the argument before the library is touched; CPU tensors raise (no CPU fallback)."""
+import numpy as np
 import torch
 import torch.nn.functional as F
 from torch.autograd import Function
@@ -182,6 +187,106 @@ def grouping_loss_terms(output, gt_seg_label, input_coords):
     return {"tooth_class_loss_1": F.cross_entropy(output["sem_1"].float(), half + 1),
             "tooth_class_loss_2": F.cross_entropy(output["sem_2"].float(), crop_labels + 1),
             "offset_1_loss": offset_loss, "offset_1_dir_loss": dir_loss, "chamf_1_loss": chamf_loss}
+
+
+def first_seg_loss(pred_mask_1, pred_weight_1, gt_bin_label):
+    """models/tsg_loss.py:63-75: pred_mask_1 (T, 2, k), the first mask head's softmax; pred_weight_1 (T, 1, k) confidence logits;
+    gt_bin_label (T, 1, k), 1 inside the tooth -> mean((nll * w)^2 + (1 - w)^2) with w = sigmoid(pred_weight_1) and nll the reference's
+    NLLLoss of the PROBABILITIES (minus the probability of the true class, not its logarithm: the reference's own choice, kept)."""
+    T = gt_bin_label.shape[0]
+    target = gt_bin_label.reshape(T, 1, -1).long()
+    nll = -pred_mask_1.gather(1, target)[:, 0]
+    w = torch.sigmoid(pred_weight_1).reshape(T, -1)
+    return torch.mean((nll * w) ** 2 + (1 - w) ** 2)
+
+
+def second_seg_loss(pred_mask_2, pred_weight_1, gt_bin_label):
+    """models/tsg_loss.py:92-104: pred_mask_2 (T, 1, k) mask logits -> mean((2 - w) * binary cross entropy with logits)."""
+    T = gt_bin_label.shape[0]
+    bce = F.binary_cross_entropy_with_logits(pred_mask_2.reshape(T, -1), gt_bin_label.reshape(T, -1).to(torch.float32), reduction="none")
+    w = torch.sigmoid(pred_weight_1).reshape(T, -1)
+    return torch.mean((2.0 - w) * bce)
+
+
+def id_loss(gt_label, pred_id):
+    """models/tsg_loss.py:122-128: gt_label, T tooth ids 1..16 in any shape and integer or float dtype; pred_id (T, 17) logits -> cross entropy."""
+    return F.cross_entropy(pred_id, gt_label.reshape(-1).long())
+
+
+def segmentation_loss(pd_1, weight_1, pd_2, id_pred, pred_cluster_gt_ids, pred_cluster_gt_points_bin_labels):
+    """models/tsg_loss.py:130-135 -> (seg_1_loss, seg_2_loss, id_pred_loss).  Torch compositions with autograd, on whatever device the
+    tensors live: crops x 3072 elements, nothing a kernel would win."""
+    return (first_seg_loss(pd_1, weight_1, pred_cluster_gt_points_bin_labels),
+            second_seg_loss(pd_2, weight_1, pred_cluster_gt_points_bin_labels),
+            id_loss(pred_cluster_gt_ids, id_pred))
+
+
+def seg_label_to_cent(feats_xyz, gt_seg_label):
+    """ops_utils.seg_label_to_cent on the GPU: feats_xyz (B, 3, N) floating (more channels are ignored), gt_seg_label (B, N) or
+    (B, 1, N) int32 or int64, -1 = gingiva -> (centroid (B, 3, 16) float32, exists (B, 16) bool): the mean of every tooth's points
+    (crops.label_centroids: one launch, no loop over the teeth, no host synchronisation) and whether the tooth has a point.  An absent
+    tooth's column is zero where the reference writes (-10, -10, -10): `exists` carries the information, as centroid_loss takes it.
+    The reference flattens the batch and is meaningful for B = 1; here every scan has its own 16 slots."""
+    if not isinstance(feats_xyz, torch.Tensor) or not feats_xyz.is_floating_point():
+        raise TypeError(f"feats_xyz must be a floating-point tensor, got {getattr(feats_xyz, 'dtype', type(feats_xyz).__name__)}")
+    if feats_xyz.dim() != 3 or feats_xyz.shape[1] < 3:
+        raise ValueError(f"feats_xyz must be channel-first (B, C >= 3, N), got {tuple(feats_xyz.shape)}")
+    B, _, N = feats_xyz.shape
+    try:
+        labels = crops.labels_2d(gt_seg_label, B, N, (torch.int32, torch.int64))
+    except (TypeError, ValueError) as e:
+        raise type(e)(f"gt_seg_label: {e}") from None
+    _lib.require_cuda(feats_xyz, labels)
+    counts, cent = crops.label_centroids(_lib.f32c(feats_xyz.detach()), labels, crops.NUM_LABELS)
+    exists = counts > 0
+    return torch.where(exists[:, :, None], cent, torch.zeros_like(cent)).permute(0, 2, 1), exists
+
+
+def _stacked_centres(center_points, B, dev):
+    """TSegNetModule's `center_points` -- a (1, T, 3) array for B = 1, a list over scans of (1, T_b, 3) arrays otherwise -> ((T, 3) float32
+    on dev, (T,) int64 scan of every centre)."""
+    per_scan = [center_points] if B == 1 and not isinstance(center_points, (list, tuple)) else list(center_points)
+    if len(per_scan) != B:
+        raise ValueError(f"center_points must hold the centres of {B} scans, got {len(per_scan)}")
+    flat = [c.reshape(-1, 3) if isinstance(c, torch.Tensor) else np.asarray(c, np.float32).reshape(-1, 3) for c in per_scan]
+    cent, scan, _ = crops.stack_centres(flat, B, dev, "center_points")
+    return cent, scan.to(torch.int64)
+
+
+def tsegnet_crop_targets(center_points, centroid, exists, cluster_gt_seg_label):
+    """The targets of tsegnet's segmentation terms (models/tsegnet_model.py:26-32): every crop centre (T, 3) is assigned to the nearest
+    EXISTING ground-truth centroid of its own scan (float32 direct-form squared distance, argmin: the first slot on a tie); the crop's
+    tooth id is that slot + 1, its binary labels are cluster_gt_seg_label + 1 == id.  centroid (B, 3, 16), exists (B, 16) as
+    seg_label_to_cent gives them -> (ids (T,) int64, bin_labels (T, 1, k) int64).  Plain torch on the tensors' device; the reference
+    indexes scan 0 for every crop, which is the same for B = 1."""
+    B = centroid.shape[0]
+    cent, scan = _stacked_centres(center_points, B, centroid.device)
+    diff = cent[:, :, None] - centroid.detach().to(torch.float32)[scan]                      # (T, 3, 16)
+    d = (diff * diff).sum(1)
+    d = torch.where(exists[scan], d, torch.full_like(d, float("inf")))
+    ids = d.argmin(dim=1) + 1
+    return ids, (cluster_gt_seg_label + 1 == ids[:, None, None]).to(torch.int64)
+
+
+def tsegnet_segmentation_loss_terms(outputs, centroid, exists):
+    """The three segmentation terms of TSegNetModel.get_loss (models/tsegnet_model.py:25-40) on nets.TSegNetModule's output dict and
+    the 16 centroid slots of seg_label_to_cent: {"seg_1_loss", "seg_2_loss", "id_pred_loss"}, unweighted."""
+    ids, bin_labels = tsegnet_crop_targets(outputs["center_points"], centroid, exists, outputs["cluster_gt_seg_label"])
+    seg_1, seg_2, id_pred = segmentation_loss(outputs["pd_1"], outputs["weight_1"], outputs["pd_2"], outputs["id_pred"], ids, bin_labels)
+    return {"seg_1_loss": seg_1, "seg_2_loss": seg_2, "id_pred_loss": id_pred}
+
+
+def tsegnet_loss_terms(outputs, gt_seg_label):
+    """TSegNetModel.get_loss and the label work of TSegNetModel.step (models/tsegnet_model.py:14-60) on nets.TSegNetModule's output dict
+    and the (B, 1, N) labels: always {"dist_loss", "cent_loss", "chamf_loss"} (fused kernels, the 16 slots passed with `exists`
+    instead of compacted on the host) and, when the dict has the segmentation outputs, {"seg_1_loss", "seg_2_loss", "id_pred_loss"}.
+    Unweighted: the reference's weights (1, 1, 0.1, 1, 1, 1) are the step class's.  For B > 1, where the reference indexes scan 0 and
+    means nothing, every scan's crops are assigned against that scan's own centroids."""
+    centroid, exists = seg_label_to_cent(outputs["l0_xyz"], gt_seg_label)
+    terms = tsegnet_centroid_loss_terms(outputs, centroid, exists)
+    if "pd_1" in outputs:
+        terms.update(tsegnet_segmentation_loss_terms(outputs, centroid, exists))
+    return terms
 
 
 def tsegnet_centroid_loss_terms(outputs, centroid_coords, exists=None):

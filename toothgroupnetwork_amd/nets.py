@@ -394,8 +394,8 @@ class TSegNetModule(nn.Module):
     `center_points` is what the reference returns for B = 1, a (1, T, 3) float32 numpy array, and for B > 1 a list over scans of
     (1, T_b, 3) arrays.  Host synchronisations per forward: tsegnet.py's two (kept counts, cluster counts) and the copy of
     `center_points` to the host that the reference's return type asks for.  In eval mode the segmentation module runs scan by scan
-    (`segment`), so a scan's outputs do not depend on the rest of the batch.  The centroid terms of its loss (tsg_loss.centroid_loss) are
-    losses.tsegnet_centroid_loss_terms (fused kernels, csrc/loss.hip); segmentation_loss and id_loss stay the reference's Python."""
+    (`segment`), so a scan's outputs do not depend on the rest of the batch.  All six terms of its loss are losses.tsegnet_loss_terms: the
+    centroid terms as fused kernels (csrc/loss.hip), segmentation_loss and id_loss as torch compositions; training.TSegNetModel is its step."""
 
     MAX_CROPS = 8            # tsegnet.py:70
     CROP_K = 3072            # tsegnet.py:73
@@ -430,10 +430,15 @@ class TSegNetModule(nn.Module):
         outs = [self.seg_module(c) for c in cropped.split(per_scan)]
         return tuple(torch.cat(parts) for parts in zip(*outs))
 
-    def forward(self, inputs):
+    def forward(self, inputs, on_no_centre="raise"):
         """inputs: [features (B, 6, N), labels (B, 1, N)] (labels may be left out: cluster_gt_seg_label is then None) -> the
         reference's output dict: l0_points, l3_points, l0_xyz, l3_xyz, offset_result, dist_result and, when the segmentation module
-        runs, pd_1, weight_1, pd_2, id_pred, center_points, cluster_gt_seg_label, cropped_feature_ls."""
+        runs, pd_1, weight_1, pd_2, id_pred, center_points, cluster_gt_seg_label, cropped_feature_ls.
+        A scan for which no centre survives the join (no proposal below the threshold, or no DBSCAN cluster) raises ValueError naming
+        the scan -- the reference dies there with an IndexError.  on_no_centre="skip" returns the centroid outputs alone for such a
+        batch instead, which is what a training step early in a run needs (training.TSegNetModel)."""
+        if on_no_centre not in ("raise", "skip"):
+            raise ValueError(f"on_no_centre must be 'raise' or 'skip', got {on_no_centre!r}")
         feats = inputs[0]
         labels = inputs[1] if len(inputs) >= 2 else None
         l0_points, l3_points, l0_xyz, l3_xyz, offset_result, dist_result = self.cent_module(feats)
@@ -443,7 +448,12 @@ class TSegNetModule(nn.Module):
             return outputs
         with torch.no_grad():
             moved, counts = _tsg.centroid_proposals(l3_xyz, offset_result, dist_result)
-            centres = _tsg.cluster_centers(moved, counts)
+            try:
+                centres = _tsg.cluster_centers(moved, counts)
+            except _tsg.NoCentre:
+                if on_no_centre == "skip":
+                    return outputs
+                raise
             chosen = []
             for c in centres:
                 rand_indexes = np.random.permutation(c.shape[0])[:self.MAX_CROPS]

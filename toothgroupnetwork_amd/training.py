@@ -1,0 +1,465 @@
+"""The training entry point: what start_train.py chains in the reference -- generator.py, runner.py, loss_meter.py, trainer.py,
+models/base_model.py and the seven models/*_model.py steps -- over this package's modules (nets.py), augmentations (augment.py) and
+criteria (losses.py).  No new kernel: the hot path of a step is the module's forward and backward and the fused losses, which are
+HIP already; this is the layer above them.
+
+  DentalModelGenerator, collate_fn, get_generator_set   generator.py, runner.py:7-50
+  LossMap                                               loss_meter.py:26-61 (the meter is eval_sharded.LossMeter)
+  build_optimizer, build_scheduler, CosineSchedule      BaseModel.__init__ (models/base_model.py:16-28)
+  TrainingModel and one step class per model name       BaseModel and models/*_model.py
+  make_training_model                                   start_train.py:22-49
+  Trainer                                               trainer.py
+
+Where it differs from the reference on purpose:
+  * LossMap.get_loss_dict_for_print reads all terms with ONE device-to-host copy and keeps the values for the step's other post-fixes;
+    the reference calls .item() per term and post-fix: nine synchronisations for a three-term step, where this has one.
+  * no wandb: the trainer writes one JSON line per scheduler step and per epoch to a stream of the caller's;
+    torch.cuda.empty_cache() per step is not mirrored; Trainer.run takes the number of epochs.
+  * tgnet_fps trains on its five geometric and class terms only.  The contrastive-boundary terms (cbl_loss_1 / cbl_loss_2) do not
+    exist in this package, so a configuration with a non-zero weight for either is refused, and so is tgnet_bdl, which needs them
+    and the boundary-sampled training inputs.  Nothing here trains silently on another objective than the configuration names.
+  * tsegnet: a batch for which no tooth centre survives the join (early in a run, nets.TSegNetModule.forward(on_no_centre="skip"))
+    contributes its three centroid terms only and is counted in `skipped_segmentation`; the reference would fail there.
+  * the cosine schedule is what build_scheduler_from_cfg really builds from a dict: every `getattr(args, ..., default)` of
+    scheduler_factory.py returns its default, so there is no warm-up, one cycle of `full_steps` steps from lr to min_lr, and min_lr after.
+"""
+import copy
+import glob
+import json
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+from torch.utils.data import DataLoader, Dataset
+
+from . import augment, eval_sharded, losses, nets
+from .eval_sharded import LossMeter  # noqa: F401
+
+MODEL_NAMES = ("tgnet_fps", "tsegnet", "dgcnn", "pointnet", "pointnetpp", "pointtransformer", "tgnet_bdl")
+SCHEDULERS = ("exp", "cosine")
+OPTIMIZERS = ("sgd", "adam")
+STACKED_KEYS = ("feat", "gt_seg_label", "uniform_feat", "uniform_gt_seg_label")      # runner.py:17
+
+
+# ---- data -------------------------------------------------------------------------------------------------------------------------
+
+class DentalModelGenerator(Dataset):
+    """generator.py:10-71: the `*_sampled_points.npy` files of data_dir, optionally only the patients of a split file (the patient id
+    is the file name up to its first underscore, and must be a stripped line of the file).  An item is feat (6, N) float32,
+    gt_seg_label (1, N) int64 with gingiva = -1, aug_obj (a deep copy of the augmentation as it was applied, None without) and
+    mesh_path.  With an augmentation: reload_vals(), then run, per item.
+
+    The un-augmented item is eval_sharded.load_item's without its batch axis: the two build the same arrays (the columns, the float32
+    cast, the `- 1`); load_item adds the loader's batch axis of 1 and wraps mesh_path in a list, which is what collate_fn does to
+    one item.  The file order is glob's, as in the reference; eval_sharded.list_preprocessed sorts."""
+
+    def __init__(self, data_dir=None, split_with_txt_path=None, aug_obj_str=None):
+        self.data_dir = data_dir
+        self.mesh_paths = glob.glob(os.path.join(data_dir, "*_sampled_points.npy"))
+        if split_with_txt_path:
+            with open(split_with_txt_path) as f:
+                self.split_base_name_ls = [line.strip() for line in f]
+            self.mesh_paths = [p for p in self.mesh_paths if os.path.basename(p).split("_")[0] in self.split_base_name_ls]
+        self.aug_obj = augment.from_config_string(aug_obj_str)
+
+    def __len__(self):
+        return len(self.mesh_paths)
+
+    def __getitem__(self, idx):
+        path = self.mesh_paths[idx]
+        item = eval_sharded.load_item(path.strip())
+        feat, seg_label = item["feat"][0], item["gt_seg_label"][0]
+        if self.aug_obj:
+            self.aug_obj.reload_vals()
+            rows = np.ascontiguousarray(feat.numpy().T)                     # (N, 6) float32, as the reference hands it over
+            feat = torch.from_numpy(self.aug_obj.run(rows)).permute(1, 0)
+        return {"feat": feat, "gt_seg_label": seg_label, "aug_obj": copy.deepcopy(self.aug_obj), "mesh_path": path}
+
+
+def collate_fn(batch):
+    """runner.py:7-19: every key becomes the list of the items' values; the tensor keys are stacked."""
+    output = {}
+    for batch_item in batch:
+        for key, value in batch_item.items():
+            output.setdefault(key, []).append(value)
+    for key in output:
+        if key in STACKED_KEYS:
+            output[key] = torch.stack(output[key])
+    return output
+
+
+def get_generator_set(config):
+    """runner.py:26-50 on config["generator"]'s dict: [train loader (shuffled, augmented), validation loader (neither)]."""
+    train = DataLoader(DentalModelGenerator(config["input_data_dir_path"], aug_obj_str=config["aug_obj_str"],
+                                            split_with_txt_path=config["train_data_split_txt_path"]),
+                       shuffle=True, batch_size=config["train_batch_size"], collate_fn=collate_fn)
+    val = DataLoader(DentalModelGenerator(config["input_data_dir_path"], aug_obj_str=None,
+                                          split_with_txt_path=config["val_data_split_txt_path"]),
+                     shuffle=False, batch_size=config["val_batch_size"], collate_fn=collate_fn)
+    return [train, val]
+
+
+# ---- losses of a step ---------------------------------------------------------------------------------------------------------------
+
+class LossMap:
+    """loss_meter.py:26-61: named (value, weight) terms of one step.  get_sum() is the weighted sum the step differentiates;
+    get_loss_dict_for_print(post_fix) is {"<term>_<post_fix>": value * weight, ..., "total_<post_fix>": their sum} as python floats."""
+
+    def __init__(self):
+        self.loss_dict = {}
+        self._host = None
+
+    def add_loss(self, name, value, weight):
+        self.loss_dict[name] = (value, weight)
+        self._host = None
+
+    def add_loss_by_dict(self, loss_dict):
+        for key, (value, weight) in loss_dict.items():
+            if key in self.loss_dict:
+                raise KeyError(f"LossMap already holds a term named {key!r}")
+            self.add_loss(key, value, weight)
+
+    def del_loss(self, name):
+        del self.loss_dict[name]
+        self._host = None
+
+    def get_sum(self):
+        summation = 0
+        for value, weight in self.loss_dict.values():
+            summation = summation + value * weight
+        return summation
+
+    def _values_on_host(self):
+        """Every term's value as a python float: the tensor terms are stacked on their device and read with ONE .tolist() -- one
+        copy, one synchronisation, whatever the number of terms -- and kept, because a step's map is printed under up to three
+        post-fixes (trainer.py:33-35).  A float32 value becomes the same python float that .item() gives."""
+        if self._host is None:
+            names = [n for n, (v, _) in self.loss_dict.items() if isinstance(v, torch.Tensor)]
+            host = {n: float(v) for n, (v, _) in self.loss_dict.items() if not isinstance(v, torch.Tensor)}
+            if names:
+                stacked = torch.stack([self.loss_dict[n][0].detach().reshape(()) for n in names])
+                host.update(zip(names, stacked.tolist()))                                  # the one read
+            self._host = host
+        return self._host
+
+    def get_loss_dict_for_print(self, post_fix):
+        host = self._values_on_host()
+        out = {f"{name}_{post_fix}": host[name] * weight for name, (_, weight) in self.loss_dict.items()}
+        total = 0
+        for value in out.values():
+            total += value
+        out[f"total_{post_fix}"] = total
+        return out
+
+
+# ---- optimiser and schedule -----------------------------------------------------------------------------------------------------------
+
+def build_optimizer(tr_set, parameters):
+    """models/base_model.py:16-19 on config["tr_set"]."""
+    opt = tr_set["optimizer"]
+    if opt["NAME"] == "sgd":
+        return torch.optim.SGD(parameters, lr=opt["lr"], momentum=opt["momentum"], weight_decay=opt["weight_decay"])
+    if opt["NAME"] == "adam":
+        return torch.optim.Adam(parameters, lr=opt["lr"], weight_decay=opt["weight_decay"])
+    raise ValueError(f"optimizer NAME = {opt['NAME']!r}: the supported ones are {', '.join(OPTIMIZERS)}")
+
+
+class CosineSchedule:
+    """The CosineLRScheduler that build_scheduler_from_cfg returns for the dict BaseModel hands it (see the module docstring): no
+    warm-up, no noise, one cycle.  step(t) sets every group's rate to min_lr + (base - min_lr) / 2 * (1 + cos(pi t / full_steps)) for
+    t < full_steps and to min_lr from there on; `base` is the group's rate at construction.  get_last_lr() is the reference's: the
+    rates of the step AFTER the last one given to step()."""
+
+    def __init__(self, optimizer, full_steps, min_lr):
+        if min_lr < 0:
+            raise ValueError(f"min_lr must not be negative, got {min_lr}")
+        self.optimizer, self.t_initial, self.lr_min, self.epoch = optimizer, full_steps, min_lr, -1
+        for group in optimizer.param_groups:
+            group.setdefault("initial_lr", group["lr"])
+        self.base_values = [group["initial_lr"] for group in optimizer.param_groups]
+        self._set(self.base_values)
+
+    def _set(self, values):
+        for group, value in zip(self.optimizer.param_groups, values):
+            group["lr"] = value
+
+    def _get_lr(self, t):
+        if t // self.t_initial >= 1:
+            return [self.lr_min for _ in self.base_values]
+        return [self.lr_min + 0.5 * (base - self.lr_min) * (1 + math.cos(math.pi * t / self.t_initial)) for base in self.base_values]
+
+    def step(self, epoch):
+        self.epoch = epoch
+        self._set(self._get_lr(epoch))
+
+    def get_last_lr(self):
+        return self._get_lr(self.epoch + 1)
+
+
+def check_scheduler(tr_set):
+    sched = tr_set["scheduler"]["sched"]
+    if sched not in SCHEDULERS:
+        raise ValueError(f"sched = {sched!r}: the supported schedulers are {' and '.join(SCHEDULERS)}")
+
+
+def build_scheduler(tr_set, optimizer):
+    """models/base_model.py:21-28 on config["tr_set"]: "exp" is torch's ExponentialLR(step_decay), "cosine" is CosineSchedule."""
+    check_scheduler(tr_set)
+    sched = tr_set["scheduler"]
+    if sched["sched"] == "exp":
+        return torch.optim.lr_scheduler.ExponentialLR(optimizer, sched["step_decay"])
+    return CosineSchedule(optimizer, sched["full_steps"], sched["min_lr"])
+
+
+# ---- model steps ------------------------------------------------------------------------------------------------------------------------
+
+class TrainingModel:
+    """models/base_model.py: the module in train mode on the GPU, its optimiser and its scheduler; step / save / load.
+
+    step(batch_idx, batch_item, phase) -> LossMap: phase "train" runs forward, the weighted sum's backward and an optimiser step;
+    "val" and "test" run the forward in eval mode under torch.no_grad().  The batch moves to the device here.  A subclass names its
+    module class and gives `losses_of(output, seg_label, points)` -> {name: (value, weight)}."""
+
+    module_class = None
+
+    def __init__(self, config, module=None):
+        self.config = config
+        self.check_config(config)
+        if not torch.cuda.is_available():
+            raise RuntimeError("training needs a GPU: the modules' operators are HIP kernels and have no CPU fallback")
+        self.device = torch.device("cuda")
+        self.module = (module or self.module_class)(config)
+        self.module.train()
+        self.module.cuda()
+        self.optimizer = build_optimizer(config["tr_set"], self.module.parameters())
+        self.scheduler = build_scheduler(config["tr_set"], self.optimizer)
+
+    @classmethod
+    def check_config(cls, config):
+        """What can be refused before anything is built: raises for a configuration this class does not train."""
+        check_scheduler(config["tr_set"])
+        name = config["tr_set"]["optimizer"]["NAME"]
+        if name not in OPTIMIZERS:
+            raise ValueError(f"optimizer NAME = {name!r}: the supported ones are {', '.join(OPTIMIZERS)}")
+
+    def _set_model(self, phase):
+        if phase not in ("train", "val", "test"):
+            raise ValueError(f"phase must be 'train', 'val' or 'test', got {phase!r}")
+        # only when the phase changes: Module.train() walks every submodule, 1.4 ms of a 75 ms tgnet_fps step when it runs per step
+        # (tools/training_bench.py, profiles/r17_training.txt)
+        if self.module.training != (phase == "train"):
+            self.module.train(phase == "train")
+
+    def load(self):
+        self.module.load_state_dict(torch.load(self.config["checkpoint_path"] + ".h5"))
+
+    def save(self, phase):
+        if phase not in ("train", "val"):
+            raise ValueError(f"save: phase must be 'train' or 'val', got {phase!r}")
+        folder = os.path.dirname(self.config["checkpoint_path"])
+        if folder:
+            os.makedirs(folder, exist_ok=True)
+        torch.save(self.module.state_dict(), self.config["checkpoint_path"] + (".h5" if phase == "train" else "_val.h5"))
+
+    def forward(self, inputs):
+        return self.module(inputs)
+
+    def losses_of(self, output, seg_label, points):
+        raise NotImplementedError
+
+    def step(self, batch_idx, batch_item, phase):
+        self._set_model(phase)
+        points = batch_item["feat"].to(self.device)
+        seg_label = batch_item["gt_seg_label"].to(self.device)
+        if phase == "train":
+            output = self.forward([points, seg_label])
+        else:
+            with torch.no_grad():
+                output = self.forward([points, seg_label])
+        loss_meter = LossMap()
+        loss_meter.add_loss_by_dict(self.losses_of(output, seg_label, points))
+        if phase == "train":
+            loss_sum = loss_meter.get_sum()
+            self.optimizer.zero_grad()
+            loss_sum.backward()
+            self.optimizer.step()
+        return loss_meter
+
+
+class _ClassModel(TrainingModel):
+    """The four semantic models: tooth_class_loss (cross entropy on label + 1, tgn_loss.py:355-367) of one output, weight 1."""
+
+    output_key, weight = "cls_pred", 1
+
+    def get_loss(self, gt_seg_label_1, sem_1):
+        return {"tooth_class_loss_1": (eval_sharded.tooth_class_loss(sem_1, gt_seg_label_1), self.weight)}
+
+    def losses_of(self, output, seg_label, points):
+        return self.get_loss(seg_label, output[self.output_key])
+
+
+class PointFirstModel(_ClassModel):
+    """models/pointnet_model.py ("pointnet")."""
+    module_class = nets.PointFirstModule
+
+
+class PointPpFirstModel(_ClassModel):
+    """models/pointnet_pp_model.py ("pointnetpp")."""
+    module_class = nets.PointPpFirstModule
+
+
+class DGCnnModel(_ClassModel):
+    """models/dgcnn_model.py ("dgcnn")."""
+    module_class = nets.DGCnnModule
+
+
+class TransformerModel(_ClassModel):
+    """models/transformer_model.py ("pointtransformer"): the term is read from "sem_1" and weighted by the configuration's
+    tr_set.loss.tooth_class_loss_1; get_loss takes (sem_1, gt_seg_label_1), the reference's order for this model."""
+    module_class, output_key = nets.PointTransformerModule, "sem_1"
+
+    def __init__(self, config, module=None):
+        self.weight = config["tr_set"]["loss"]["tooth_class_loss_1"]
+        super().__init__(config, module)
+
+    def get_loss(self, sem_1, gt_seg_label_1):
+        return super().get_loss(gt_seg_label_1, sem_1)
+
+    def losses_of(self, output, seg_label, points):
+        return self.get_loss(output[self.output_key], seg_label)
+
+
+class FpsGroupingNetworkModel(TrainingModel):
+    """models/fps_grouping_network_model.py ("tgnet_fps") without the contrastive-boundary terms: the five terms of
+    losses.grouping_loss_terms with the configuration's weights.  A non-zero cbl_loss_1 / cbl_loss_2 weight is refused."""
+    module_class = nets.GroupingNetworkModule
+    TERMS = ("tooth_class_loss_1", "tooth_class_loss_2", "offset_1_loss", "offset_1_dir_loss", "chamf_1_loss")
+    CBL = ("cbl_loss_1", "cbl_loss_2")
+
+    @classmethod
+    def check_config(cls, config):
+        super().check_config(config)
+        asked = [n for n in cls.CBL if config["tr_set"]["loss"].get(n, 0) != 0]
+        if asked:
+            raise NotImplementedError(f"tgnet_fps: the configuration weights {' and '.join(asked)}, but the contrastive-boundary terms are not "
+                                      "built in this package; set tr_set.loss.cbl_loss_1 and cbl_loss_2 to 0 (or leave them out) to train "
+                                      "on the five class, offset, direction and chamfer terms alone")
+
+    def get_loss(self, output, gt_seg_label, input_coords):
+        terms = losses.grouping_loss_terms(output, gt_seg_label, input_coords)
+        return {name: (terms[name], self.config["tr_set"]["loss"][name]) for name in self.TERMS}
+
+    def losses_of(self, output, seg_label, points):
+        return self.get_loss(output, seg_label, points[:, :3, :])
+
+
+class TSegNetModel(TrainingModel):
+    """models/tsegnet_model.py ("tsegnet"): losses.tsegnet_loss_terms with the reference's weights.  Honours
+    run_tooth_segmentation_module (False: the centroid module alone is trained on its three terms) and
+    pretrained_centroid_model_path (loaded with strict=False, as the reference does).  `skipped_segmentation` counts the steps whose
+    batch had no tooth centre, so that the three segmentation terms are missing from their LossMap."""
+    module_class = nets.TSegNetModule
+    WEIGHTS = {"dist_loss": 1, "cent_loss": 1, "chamf_loss": 0.1, "seg_1_loss": 1, "seg_2_loss": 1, "id_pred_loss": 1}
+
+    def __init__(self, config, module=None):
+        super().__init__(config, module)
+        self.skipped_segmentation = 0
+        if config.get("pretrained_centroid_model_path") is not None:
+            self.module.load_state_dict(torch.load(config["pretrained_centroid_model_path"] + ".h5"), strict=False)
+
+    def forward(self, inputs):
+        output = self.module(inputs, on_no_centre="skip")
+        if self.config["run_tooth_segmentation_module"] and "pd_1" not in output:
+            self.skipped_segmentation += 1
+        return output
+
+    def get_loss(self, outputs, gt):
+        """gt: {"seg_label": (B, 1, N)}; the reference's centroid_coords / centroid_labels entries are computed from it on the device."""
+        terms = losses.tsegnet_loss_terms(outputs, gt["seg_label"])
+        return {name: (value, self.WEIGHTS[name]) for name, value in terms.items()}
+
+    def losses_of(self, output, seg_label, points):
+        return self.get_loss(output, {"seg_label": seg_label})
+
+
+_MODELS = {"tgnet_fps": FpsGroupingNetworkModel, "tsegnet": TSegNetModel, "dgcnn": DGCnnModel, "pointnet": PointFirstModel,
+           "pointnetpp": PointPpFirstModel, "pointtransformer": TransformerModel}
+
+
+def make_training_model(model_name, config):
+    """start_train.py:22-49: the step object of a model name.  tgnet_bdl is refused (NotImplementedError), another name is ValueError."""
+    if model_name == "tgnet_bdl":
+        raise NotImplementedError("tgnet_bdl is not built: its step needs the boundary-sampled training inputs and the contrastive-boundary "
+                                  "terms, neither of which exists in this package; tgnet_fps trains with zero cbl weights")
+    if model_name not in _MODELS:
+        raise ValueError(f"undefined model {model_name!r}: the names are {', '.join(MODEL_NAMES)}")
+    return _MODELS[model_name](config)
+
+
+# ---- the loop ---------------------------------------------------------------------------------------------------------------------------
+
+class Trainer:
+    """trainer.py: train(epoch, loader), test(epoch, loader, save_best_model), run(epochs) over gen_set = [[train loader, val loader]].
+
+    The bookkeeping is the reference's (trainer.py:26-63): the scheduler steps when (batch_idx + 1) % schedueler_step == 0, or on the
+    last batch of an epoch in which it has not stepped yet, each time with the running step count; save("train") after every training
+    epoch; save("val") whenever total_val improves.  Instead of wandb, `stream` (default stdout) gets one JSON line per scheduler
+    step -- the step meter's averages (`*_step`), `step_lr`, `step` -- and run() one per epoch: the epoch's `*_train` and `*_val`
+    averages, `epoch`, `step` and, for a model that counts them, `skipped_segmentation`."""
+
+    def __init__(self, config=None, model=None, gen_set=None, stream=None):
+        self.config, self.model, self.gen_set = config, model, gen_set
+        self.stream = stream
+        self.val_count = self.train_count = self.step_count = 0
+        self.best_val_loss = math.inf
+
+    def _emit(self, record):
+        stream = self.stream if self.stream is not None else sys.stdout
+        stream.write(json.dumps(record) + "\n")
+        stream.flush()
+
+    def train(self, epoch, data_loader):
+        total_loss_meter, step_loss_meter = LossMeter(), LossMeter()
+        pre_step = self.step_count
+        every = self.config["tr_set"]["scheduler"]["schedueler_step"]
+        last = len(data_loader) - 1
+        for batch_idx, batch_item in enumerate(data_loader):
+            loss = self.model.step(batch_idx, batch_item, "train")
+            total_loss_meter.aggr(loss.get_loss_dict_for_print("train"))
+            step_loss_meter.aggr(loss.get_loss_dict_for_print("step"))
+            if (batch_idx + 1) % every == 0 or (self.step_count == pre_step and batch_idx == last):
+                record = {"step": self.step_count, **step_loss_meter.get_avg_results(), "step_lr": self.model.scheduler.get_last_lr()[0]}
+                self.step_count += 1
+                self.model.scheduler.step(self.step_count)
+                step_loss_meter.init()
+                self._emit(record)
+        self.train_count += 1
+        self.model.save("train")
+        return total_loss_meter.get_avg_results() if total_loss_meter.step_num else {}
+
+    def test(self, epoch, data_loader, save_best_model):
+        total_loss_meter = LossMeter()
+        for batch_idx, batch_item in enumerate(data_loader):
+            loss = self.model.step(batch_idx, batch_item, "test")
+            total_loss_meter.aggr(loss.get_loss_dict_for_print("val"))
+        if not total_loss_meter.step_num:
+            return {}
+        avg_total_loss = total_loss_meter.get_avg_results()
+        self.val_count += 1
+        if save_best_model and self.best_val_loss > avg_total_loss["total_val"]:
+            self.best_val_loss = avg_total_loss["total_val"]
+            self.model.save("val")
+        return avg_total_loss
+
+    def run(self, epochs):
+        train_data_loader, val_data_loader = self.gen_set[0][0], self.gen_set[0][1]
+        for epoch in range(int(epochs)):
+            record = {"epoch": epoch}
+            record.update(self.train(epoch, train_data_loader))
+            record.update(self.test(epoch, val_data_loader, True))
+            record["step"] = self.step_count
+            if hasattr(self.model, "skipped_segmentation"):
+                record["skipped_segmentation"] = self.model.skipped_segmentation
+            self._emit(record)

@@ -24,6 +24,10 @@ CROP_K = 3072                      # tsegnet.py:73
 MAX_M = 1024                       # tgn_tsg_proposals: one workgroup per scan
 
 
+class NoCentre(ValueError):
+    """A scan without a tooth centre: no proposal below the threshold, or no cluster among the proposals (cluster_centers)."""
+
+
 def _f32(t, what, shape_text, ok):
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{what} must be a torch tensor, got {type(t).__name__}")
@@ -72,7 +76,7 @@ def cluster_centers(moved, counts, eps=EPS, min_samples=MIN_SAMPLES):
         raise ValueError(f"counts must be non-negative and sum to {moved.shape[0]} rows, got {counts}")
     for b, c in enumerate(counts):
         if c == 0:
-            raise ValueError(f"tsegnet: scan {b} has no centroid proposal with dist < threshold, so no cluster")
+            raise NoCentre(f"tsegnet: scan {b} has no centroid proposal with dist < threshold, so no cluster")
     _lib.require_cuda(moved)
     moved = moved.detach().contiguous()
     ends = np.cumsum(counts).tolist()
@@ -80,7 +84,7 @@ def cluster_centers(moved, counts, eps=EPS, min_samples=MIN_SAMPLES):
     ncl = ncl.cpu().tolist()                                                                  # the synchronisation
     for b, t in enumerate(ncl):
         if t == 0:
-            raise ValueError(f"tsegnet: DBSCAN found no cluster among the {counts[b]} proposals of scan {b}")
+            raise NoCentre(f"tsegnet: DBSCAN found no cluster among the {counts[b]} proposals of scan {b}")
         if t > _crops.MAX_CLUSTERS:
             raise ValueError(f"tsegnet: {t} clusters in scan {b}: at most {_crops.MAX_CLUSTERS} are supported (tgn_label_centroids)")
     out, lo = [], 0
