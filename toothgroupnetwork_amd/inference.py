@@ -23,7 +23,11 @@ the painting on the GPU (tsegnet.py), pinned against the reference's class in th
 
 TgnInferencePipeLine is tgnet's (inference_pipelines/inference_pipeline_tgn.py): two GroupingNetworkModules with the boundary-aware
 resampling between them (tgnet.py), pinned in the same way (tests/golden/make_golden_r16_tgnet.py).  make_inference_pipeline is the
-reference's factory (inference_pipelines/inference_pipeline_maker.py) with its six model names."""
+reference's factory (inference_pipelines/inference_pipeline_maker.py) with its six model names.
+
+Each of the three classes states its stages once, as methods (_StagedPipeLine), and `__call__` composes them.  infer_paths runs many scans
+through any of them: the semantic pipelines through infer_scans, the two-stage ones through run_staged, an engine that puts the same
+stage methods on loader, sampler and finisher threads around the calling thread (measured: profiles/r18_inference.txt)."""
 import time
 
 import numpy as np
@@ -83,7 +87,65 @@ def fdi_from_classes(cls):
     return cls
 
 
-class InferencePipeLine:
+class _Laps:
+    """Durations between marks: compute() of a pipeline marks the end of each of its parts."""
+
+    def __init__(self):
+        self.durations, self.last = {}, time.perf_counter()
+
+    def mark(self, name):
+        now = time.perf_counter()
+        self.durations[name], self.last = now - self.last, now
+
+
+class _StagedPipeLine:
+    """What the three pipelines share: a scan goes through five stages, each a method, and `__call__` is their composition.
+      load(path)                       host only: the reader (_mesh), the pipeline's normalisation (:21-22) and the decision whether the mesh
+                                       is subdivided -> the scan: {"path", "org_feats" (n, 6), "triangles" (None unless it is), "to_kept"}
+      dense_rows(scan)                 the rows that are sampled: the scan's own, or the once-subdivided mesh's (GPU)
+      take_sample(dense, idx)          the 24 000 sampled rows, given the FPS indices of the dense rows
+      compute(scan, dense, sampled)    the networks and what joins them -> what finish needs; the durations of its parts go into `laps`
+      finish(scan, sampled, computed)  the label transfer onto every vertex (GPU), the FDI relabelling -> {"sem", "ins"}
+    infer_paths runs the same methods over many scans, each stage on threads of its own.  No method keeps anything about a scan on
+    the pipeline object besides `times`, which only `__call__` writes."""
+
+    FPS_PREFIX = True       # leave the FPS-of-an-FPS-result certificate for the network's first level (resample.fps)
+
+    def _mesh(self, path):
+        """-> (vertices, vertex normals, triangles, to_kept or None)"""
+        _, mesh = preprocess.read_txt_obj_ls(path, ret_mesh=True)
+        return mesh["vertices"], mesh["vertex_normals"], mesh["triangles"], None
+
+    def load(self, path):
+        vertices, normals, triangles, to_kept = self._mesh(path)
+        org_feats = np.concatenate([normalise_for_inference(vertices, self.scaler, self.shifter), normals], axis=1)
+        small = needs_subdivision(org_feats.shape[0], int(np.asarray(triangles).shape[0]))
+        return {"path": path, "org_feats": org_feats, "triangles": triangles if small else None, "to_kept": to_kept}
+
+    def dense_rows(self, scan):
+        return scan["org_feats"] if scan["triangles"] is None else subdivided_rows(scan["org_feats"], scan["triangles"])
+
+    def take_sample(self, dense, idx):
+        return dense[idx[:N_POINTS]]
+
+    def __call__(self, stl_path):
+        t = [time.perf_counter()]
+        scan = self.load(stl_path)
+        t.append(time.perf_counter())
+        dense = self.dense_rows(scan)
+        idx = resample.fps(dense[:, :3], N_POINTS, prefix=self.FPS_PREFIX)         # gen_utils.resample_pcd(..., "fps")
+        sampled_feats = self.take_sample(dense, idx)
+        t.append(time.perf_counter())
+        laps = _Laps()
+        computed = self.compute(scan, dense, sampled_feats, laps)
+        t.append(time.perf_counter())
+        result = self.finish(scan, sampled_feats, computed)
+        t.append(time.perf_counter())
+        self.times = {"load": t[1] - t[0], "sample": t[2] - t[1], **laps.durations, "transfer": t[4] - t[3]}
+        return result
+
+
+class InferencePipeLine(_StagedPipeLine):
     """Same constructor and call as the reference class: pipeline(path) -> {"sem": labels per vertex, "ins": the same}.
     `model` maps [features (1, 6, 24000)] to a dict with "cls_pred" (the reference's model wrappers) or to a list whose first
     entry is the class logits (B, 17, N) (nets.PointTransformerSeg).  `times` holds the stage times of the last call."""
@@ -94,30 +156,23 @@ class InferencePipeLine:
         self.shifter = 0.8
         self.times = {}
 
-    def __call__(self, stl_path):
-        t = [time.perf_counter()]
-        feats, mesh = preprocess.read_txt_obj_ls(stl_path, ret_mesh=True)
-        t.append(time.perf_counter())
-        vertices = normalise_for_inference(mesh["vertices"], self.scaler, self.shifter)
-        org_feats = np.concatenate([vertices, mesh["vertex_normals"]], axis=1)
-        dense = points_to_sample(org_feats, mesh["triangles"])
-        idx = resample.fps(dense[:, :3], N_POINTS, prefix=True)                   # gen_utils.resample_pcd(..., "fps")
-        sampled_feats = dense[idx[:N_POINTS]]
-        t.append(time.perf_counter())
+    def compute(self, scan, dense, sampled_feats, laps=None):
+        laps = _Laps() if laps is None else laps
         with torch.no_grad():
             inp = torch.from_numpy(np.ascontiguousarray(sampled_feats.astype("float32"))[None]).cuda().permute(0, 2, 1)
             out = self.model([inp])
             cls_pred = out["cls_pred"] if isinstance(out, dict) else out[0]
             cls_pred = cls_pred.argmax(dim=1).reshape(-1).cpu().numpy()
-        t.append(time.perf_counter())
+        laps.mark("model")
+        return cls_pred
+
+    def finish(self, scan, sampled_feats, cls_pred):
         labels = fdi_from_classes(cls_pred)
-        result = preprocess.transfer_labels(sampled_feats[:, :3], labels, org_feats[:, :3])
-        t.append(time.perf_counter())
-        self.times = dict(zip(("load", "sample", "model", "transfer"), np.diff(t).tolist()))
+        result = preprocess.transfer_labels(sampled_feats[:, :3], labels, scan["org_feats"][:, :3])
         return {"sem": result.reshape(-1), "ins": result.reshape(-1)}
 
 
-class TSegNetInferencePipeLine:
+class TSegNetInferencePipeLine(_StagedPipeLine):
     """inference_pipelines/inference_pipeline_tsegnet.py:9-80 on this package's operators: same constructor and call as the
     reference class, pipeline(path) -> {"sem": labels per vertex, "ins": the same}.  `model` is anything with `cent_module`,
     `seg_module` and `get_ddf` (nets.TSegNetModule, the reference's own class, or a stand-in): the centroid module on the 24 000
@@ -126,42 +181,34 @@ class TSegNetInferencePipeLine:
     tsegnet.paint_labels, the FDI relabelling (:69-70) and the nearest-sample transfer onto every vertex (:72-74).
     `times` holds the stage times of the last call.  Meshes below 24 000 vertices: subdivided once, as in InferencePipeLine."""
 
+    FPS_PREFIX = False
+
     def __init__(self, model):
         self.model = model
         self.scaler = 1.8
         self.shifter = 0.8
         self.times = {}
 
-    def __call__(self, stl_path):
-        t = [time.perf_counter()]
-        feats, mesh = preprocess.read_txt_obj_ls(stl_path, ret_mesh=True)
-        t.append(time.perf_counter())
-        vertices = normalise_for_inference(mesh["vertices"], self.scaler, self.shifter)
-        org_feats = np.concatenate([vertices, mesh["vertex_normals"]], axis=1)
-        dense = points_to_sample(org_feats, mesh["triangles"])
-        idx = resample.fps(dense[:, :3], N_POINTS)                                 # gen_utils.resample_pcd(..., "fps")
-        sampled_feats = dense[idx[:N_POINTS]]
-        t.append(time.perf_counter())
+    def compute(self, scan, dense, sampled_feats, laps=None):
+        laps = _Laps() if laps is None else laps
         with torch.no_grad():
             inp = torch.from_numpy(np.ascontiguousarray(sampled_feats.astype("float32"))[None]).cuda().permute(0, 2, 1).contiguous()
             l0_points, _, _, l3_xyz, offset_result, dist_result = self.model.cent_module(inp)
             torch.cuda.current_stream().synchronize()
-            t.append(time.perf_counter())
+            laps.mark("centroids")
             moved, counts = tsegnet.centroid_proposals(l3_xyz, offset_result, dist_result)
             centres = tsegnet.cluster_centers(moved, counts)
             cropped, nn_crop_indexes, _ = tsegnet.crop_features(inp, l0_points, centres, tsegnet.CROP_K)
             torch.cuda.current_stream().synchronize()
-            t.append(time.perf_counter())
+            laps.mark("join")
             _, _, pd_2, id_pred = self.model.seg_module(cropped)
             torch.cuda.current_stream().synchronize()
-            t.append(time.perf_counter())
+            laps.mark("segmentation")
             cls_pred = tsegnet.paint_labels(nn_crop_indexes, pd_2, id_pred, N_POINTS).reshape(-1).cpu().numpy()
-        t.append(time.perf_counter())
-        labels = fdi_from_classes(cls_pred)
-        result = preprocess.transfer_labels(sampled_feats[:, :3], labels, org_feats[:, :3])
-        t.append(time.perf_counter())
-        self.times = dict(zip(("load", "sample", "centroids", "join", "segmentation", "paint", "transfer"), np.diff(t).tolist()))
-        return {"sem": result.reshape(-1), "ins": result.reshape(-1)}
+        laps.mark("paint")
+        return cls_pred
+
+    finish = InferencePipeLine.finish
 
 
 def first_occurrences(vertices):
@@ -174,7 +221,7 @@ def first_occurrences(vertices):
     return keep.astype(np.int64), np.searchsorted(keep, first[inverse.reshape(-1)]).astype(np.int64)
 
 
-class TgnInferencePipeLine:
+class TgnInferencePipeLine(_StagedPipeLine):
     """inference_pipelines/inference_pipeline_tgn.py:10-157 (the "tgnet" model) on this package's operators: pipeline(path) ->
     {"sem": FDI-style tooth number per vertex, "ins": instance per vertex}.  `first_module` and `bdl_module` are two
     nets.GroupingNetworkModule (five-stage over the 24 000 sampled points, two-stage over the boundary-aware resampling), the
@@ -222,39 +269,37 @@ class TgnInferencePipeLine:
             modules.append(module.eval())
         return cls(modules[0], modules[1], config.get("boundary_sampling_info"))
 
-    def __call__(self, stl_path):
-        t = [time.perf_counter()]
-        _, mesh = preprocess.read_txt_obj_ls(stl_path, ret_mesh=True)
+    def _mesh(self, path):
+        _, mesh = preprocess.read_txt_obj_ls(path, ret_mesh=True)
         keep, to_kept = first_occurrences(mesh["vertices"])
-        triangles = to_kept[mesh["triangles"]]
-        t.append(time.perf_counter())
-        vertices = normalise_for_inference(mesh["vertices"][keep], self.scaler, self.shifter)
-        org_feats = np.concatenate([vertices, mesh["vertex_normals"][keep]], axis=1)
-        bdl_feats = points_to_sample(org_feats, triangles)
-        idx = resample.fps(bdl_feats[:, :3], N_POINTS, prefix=True)
-        sampled_feats = bdl_feats[idx[:N_POINTS]]
-        t.append(time.perf_counter())
+        return mesh["vertices"][keep], mesh["vertex_normals"][keep], to_kept[mesh["triangles"]], to_kept
+
+    def compute(self, scan, bdl_feats, sampled_feats, laps=None):
+        """(the only stage that draws from numpy's global generator: boundary_resample's permutation)"""
+        laps = _Laps() if laps is None else laps
         with torch.no_grad():
             inp = torch.from_numpy(np.ascontiguousarray(sampled_feats.astype("float32"))[None]).cuda().permute(0, 2, 1).contiguous()
             first = tgnet.first_instances(inp, self.first_module([inp]))
             first = {k: v.cpu().numpy() for k, v in first.items()}
-            t.append(time.perf_counter())
+            laps.mark("first")
             feats, labels, only_bdl, _ = tgnet.boundary_resample(bdl_feats, sampled_feats, first["ins"], self.boundary_sampling_info)
-            t.append(time.perf_counter())
+            laps.mark("resample")
             inp = torch.from_numpy(np.ascontiguousarray(feats.astype("float32"))[None]).cuda().permute(0, 2, 1).contiguous()
             lab = torch.from_numpy(tgnet.dense_rank_labels(labels)[None, None]).cuda()
             second = tgnet.second_instances(inp, lab, self.bdl_module([inp, lab], test=True))
             nb = only_bdl.shape[0]
             bdl_xyz, bdl_ins = second["xyz"][:nb].cpu().numpy(), second["ins"][:nb].cpu().numpy()
-        t.append(time.perf_counter())
+        laps.mark("boundary")
         sem, ins = tgnet.number_teeth(first["xyz"], first["ins"], first["sem"])
         points, ins, sem = tgnet.merge_boundary(first["xyz"], ins, sem, bdl_xyz, bdl_ins)
-        t.append(time.perf_counter())
-        nearest = preprocess.transfer_labels(points, np.arange(points.shape[0]), org_feats[:, :3])
+        laps.mark("merge")
+        return points, ins, sem
+
+    def finish(self, scan, sampled_feats, computed):
+        points, ins, sem = computed
+        nearest = preprocess.transfer_labels(points, np.arange(points.shape[0]), scan["org_feats"][:, :3])
         sem, ins = fdi_from_classes(sem[nearest]), ins[nearest]
-        t.append(time.perf_counter())
-        self.times = dict(zip(self.STAGES, np.diff(t).tolist()))
-        return {"sem": sem[to_kept].reshape(-1), "ins": ins[to_kept].reshape(-1)}
+        return {"sem": sem[scan["to_kept"]].reshape(-1), "ins": ins[scan["to_kept"]].reshape(-1)}
 
 
 _FIVE_STAGE = {"input_feat": 6, "stride": [1, 4, 4, 4, 4], "nstride": [2, 2, 2, 2], "nsample": [36, 24, 24, 24, 24], "blocks": [2, 3, 4, 6, 3],
@@ -368,4 +413,235 @@ def infer_scans(paths, model, batch=8, workers=None):
     finally:
         for pool in (loaders, sampler, finishers):
             pool.shutdown(wait=True, cancel_futures=True)
+    return results
+
+
+def default_workers():
+    """Loader threads of a staged run: the host cores this rank may count on (sharding.cpus_for_this_rank: affinity mask and CPU quota,
+    shared with the other ranks of the node), at most 16 -- the reader scales no further (profiles/r04_preprocess_host_scaling.txt)."""
+    import os
+
+    from . import sharding
+    local_world = int(os.environ.get("LOCAL_WORLD_SIZE") or os.environ.get("WORLD_SIZE") or 1)
+    return max(1, min(16, sharding.cpus_for_this_rank(local_world)))
+
+
+def _with_path(error, path):
+    """the same kind of exception with the scan's path in front of its message"""
+    try:
+        named = type(error)(f"{path}: {error}")
+    except Exception:  # noqa: BLE001  (a constructor that wants more than a message)
+        named = RuntimeError(f"{path}: {type(error).__name__}: {error}")
+    named.__cause__ = error
+    return named
+
+
+def _settle(results, i, path, error, on_error):
+    named = _with_path(error, path)
+    if on_error == "raise":
+        raise named
+    results[i] = {"error": f"{type(named).__name__}: {named}"}
+
+
+def run_staged(paths, load, prepare, sample, compute, finish, batch=8, workers=None, on_error="raise", on_thread=None, stats=None):
+    """The engine of a staged run over many scans; the stages are the caller's:
+      load(path) -> loaded                            `workers` loader threads
+      prepare(loaded) -> prepared                     the one sampler thread, scan by scan
+      sample([prepared, ...]) -> [sampled, ...]       the sampler thread, ONE call per chunk of up to 4 x `batch` scans (the first: `batch`)
+      compute(loaded, prepared, sampled) -> computed  the CALLING thread, one scan at a time, in the order of `paths`
+      finish(loaded, sampled, computed) -> result     up to four finisher threads
+    -> the results in the order of `paths`.  on_thread(fn, *args) wraps what the sampler and the finishers run (infer_paths: a stream
+    of the thread's own, synchronised before the result is handed on).  At most two chunks are in front of the calling thread, so a
+    long list does not fill memory with loaded meshes.  A scan that fails in any stage raises its own exception with the path in
+    front of the message (on_error="raise"), or leaves {"error": message} in its slot while the others go on ("skip"); a `sample`
+    call that fails as a whole fails every scan of its chunk.  All pools have ended when this returns or raises.
+    stats: a dict that receives the mean seconds per scan in "load", "sample", "compute", "finish"."""
+    from collections import deque
+    from concurrent.futures import ThreadPoolExecutor
+    if on_error not in ("raise", "skip"):
+        raise ValueError(f"on_error is 'raise' or 'skip', not {on_error!r}")
+    call = on_thread if on_thread is not None else (lambda fn, *a: fn(*a))
+    paths = list(paths)
+    # an FPS launch costs the same for 1 or 64 scans (one workgroup each), so a chunk is four batches -- but the first is one batch: the
+    # calling thread has nothing to do until the first chunk is loaded and sampled
+    step, n = max(int(batch), 1), len(paths)
+    edges = [0] + list(range(min(step, n), n, 4 * step)) + [n]
+    chunks = [range(lo, hi) for lo, hi in zip(edges, edges[1:]) if hi > lo]
+    results = [None] * len(paths)
+    spent = {name: [] for name in ("load", "sample", "compute", "finish")}
+
+    def timed(name, fn, *a):
+        t0 = time.perf_counter()
+        try:
+            return fn(*a)
+        finally:
+            spent[name].append(time.perf_counter() - t0)
+
+    def sample_chunk(loads):
+        # (sampler thread) -> per scan (loaded, prepared, sampled), or the exception that stopped it
+        got = []
+        for f in loads:
+            try:
+                loaded = f.result()
+                got.append((loaded, call(prepare, loaded)))
+            except Exception as e:  # noqa: BLE001
+                got.append(e)
+        good = [g for g in got if not isinstance(g, Exception)]
+        sampled = []
+        if good:
+            try:
+                sampled = list(call(sample, [prepared for _, prepared in good]))
+                if len(sampled) != len(good):
+                    raise RuntimeError(f"the sample stage returned {len(sampled)} entries for {len(good)} scans")
+            except Exception as e:  # noqa: BLE001
+                sampled = [e] * len(good)
+        sampled = iter(sampled)
+        out = []
+        for g in got:
+            s = g if isinstance(g, Exception) else next(sampled)
+            out.append(s if isinstance(s, Exception) else (g[0], g[1], s))
+        return out
+
+    workers = default_workers() if workers is None else max(int(workers), 1)
+    loaders = ThreadPoolExecutor(max_workers=workers, thread_name_prefix="tgn-load")
+    sampler = ThreadPoolExecutor(max_workers=1, thread_name_prefix="tgn-sample")
+    finishers = ThreadPoolExecutor(max_workers=4, thread_name_prefix="tgn-finish")
+
+    def submit(c):
+        return sampler.submit(timed, "sample", sample_chunk, [loaders.submit(timed, "load", load, paths[i]) for i in chunks[c]])
+
+    pending = deque()
+
+    def collect(wait):
+        while pending and (wait or pending[0][1].done()):
+            i, f = pending.popleft()
+            try:
+                results[i] = f.result()
+            except Exception as e:  # noqa: BLE001
+                _settle(results, i, paths[i], e, on_error)
+
+    try:
+        ahead = deque(submit(c) for c in range(min(2, len(chunks))))
+        for c in range(len(chunks)):
+            items = ahead.popleft().result()
+            if c + 2 < len(chunks):
+                ahead.append(submit(c + 2))
+            for i, item in zip(chunks[c], items):
+                try:
+                    if isinstance(item, Exception):
+                        raise item
+                    loaded, prepared, sampled = item
+                    computed = timed("compute", compute, loaded, prepared, sampled)
+                except Exception as e:  # noqa: BLE001
+                    _settle(results, i, paths[i], e, on_error)
+                    continue
+                pending.append((i, finishers.submit(timed, "finish", call, finish, loaded, sampled, computed)))
+                collect(False)
+        collect(True)
+    finally:
+        for pool in (loaders, sampler, finishers):
+            pool.shutdown(wait=True, cancel_futures=True)
+    if stats is not None and paths:
+        stats.update({name: sum(times) / len(paths) for name, times in spent.items()})
+    return results
+
+
+class _OwnStreams:
+    """on_thread of a staged run on the GPU: every helper thread works on a stream of its own, on the calling thread's device, and the
+    stream is synchronised before the result -- or the exception -- leaves the thread.  (The index-error word is per device and
+    stream, so the checks of two threads do not cross.)"""
+
+    def __init__(self):
+        import threading
+        self.local, self.device = threading.local(), torch.cuda.current_device()
+
+    def __call__(self, fn, *a):
+        with torch.cuda.device(self.device):
+            st = getattr(self.local, "stream", None)
+            if st is None:
+                st = self.local.stream = torch.cuda.Stream()
+            with torch.cuda.stream(st):
+                try:
+                    return fn(*a)
+                finally:
+                    st.synchronize()
+
+
+def _one_by_one(pipeline, paths, on_error, stats):
+    """[pipeline(p) for p in paths] with the staged run's error rules"""
+    results, sums = [None] * len(paths), {}
+    for i, path in enumerate(paths):
+        try:
+            results[i] = pipeline(path)
+        except Exception as e:  # noqa: BLE001
+            _settle(results, i, path, e, on_error)
+            continue
+        for k, v in dict(getattr(pipeline, "times", None) or {}).items():
+            sums[k] = sums.get(k, 0.0) + v
+    if stats is not None and paths:
+        stats.update({k: v / len(paths) for k, v in sums.items()})
+    return results
+
+
+# Whether the staged run of a two-stage pipeline is what infer_paths uses: decided by measurement (tools/inference_bench.py --model_name,
+# profiles/r18_inference.txt), not by hope -- a name whose staged run is not faster than the loop by more than the spread of the
+# repeats goes through the loop.
+STAGED = {"tsegnet": True, "tgnet": True}
+
+
+def infer_paths(pipeline, paths, batch=8, workers=None, on_error="raise", stats=None, staged=None):
+    """Many scans through any pipeline -> the list of {"sem", "ins"} in the order of `paths`.
+      InferencePipeLine            infer_scans(paths, pipeline.model, batch, workers): the network runs on `batch` scans at a time
+      TSegNetInferencePipeLine,    a staged run (run_staged) of the pipeline's own stage methods: loader threads; a sampler thread that
+      TgnInferencePipeLine         subdivides small meshes and runs ONE resample.fps_batch launch per 4 x `batch` scans; compute on the
+                                   calling thread, ONE SCAN PER NETWORK CALL in the order of `paths`; the transfer on finisher threads
+      anything else callable       [pipeline(p) for p in paths]
+    The two-stage results equal pipeline(path) by construction, not by tolerance: the networks see the shapes the single-scan call
+    gives them (the library GEMMs pick kernels by row count, and the 0.3 filter, the DBSCAN radius and the 0.7 boundary ratio turn
+    last bits into other point sets), and only the calling thread draws from numpy's global generator, in path order -- after
+    np.random.seed(s) the run equals [pipeline(p) for p in paths] after the same seed.  fps_batch leaves no prefix certificate; the
+    certificate only short-cuts an identical result, so no label depends on it, and none left for a later scan can reach an earlier
+    scan's network.
+    workers: loader threads (default_workers()).  on_error: "raise" -- a failing scan raises its own exception with its path in front
+    of the message; "skip" -- its slot holds {"error": message} and the others are answered (for InferencePipeLine, whose batched run
+    fails as a whole, the scans are then answered one at a time).  stats receives mean seconds per scan and stage.  staged: overrides
+    STAGED for a two-stage pipeline (the measurement's switch)."""
+    paths = list(paths)
+    workers = default_workers() if workers is None else max(int(workers), 1)
+    if on_error not in ("raise", "skip"):
+        raise ValueError(f"on_error is 'raise' or 'skip', not {on_error!r}")
+    if isinstance(pipeline, InferencePipeLine):
+        if on_error == "raise":
+            return infer_scans(paths, pipeline.model, batch, workers)
+        try:
+            return infer_scans(paths, pipeline.model, batch, workers)
+        except Exception:  # noqa: BLE001  (which scan it was is not known: find it)
+            return _one_by_one(pipeline, paths, on_error, stats)
+    two_stage = isinstance(pipeline, (TSegNetInferencePipeLine, TgnInferencePipeLine))
+    if staged is None:
+        staged = two_stage and STAGED["tgnet" if isinstance(pipeline, TgnInferencePipeLine) else "tsegnet"]
+    if not (two_stage and staged):
+        return _one_by_one(pipeline, paths, on_error, stats)
+    laps_sum = {}
+
+    def prepare(scan):
+        dense = pipeline.dense_rows(scan)
+        if dense.shape[0] <= N_POINTS:
+            raise ValueError("new fps error")       # resample.fps's refusal, here: it fails this scan, not the chunk's launch
+        return dense
+
+    def sample(dense):
+        return [pipeline.take_sample(d, idx) for d, idx in zip(dense, resample.fps_batch(dense, N_POINTS))]
+
+    def compute(scan, dense, sampled):
+        laps = _Laps()
+        computed = pipeline.compute(scan, dense, sampled, laps)
+        for k, v in laps.durations.items():
+            laps_sum[k] = laps_sum.get(k, 0.0) + v
+        return computed
+
+    results = run_staged(paths, pipeline.load, prepare, sample, compute, pipeline.finish, batch=batch, workers=workers,
+                         on_error=on_error, on_thread=_OwnStreams(), stats=stats)
+    if stats is not None and paths:
+        stats.update({k: v / len(paths) for k, v in laps_sum.items()})
     return results
