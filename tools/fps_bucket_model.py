@@ -12,8 +12,10 @@ touched depends only on how the cloud was dealt out to the buckets, so it can be
     (a refresh only when a point that HELD the bucket's maximum came closer) and the arg-max with first-index ties;
 
 and prints, per cloud, the mean number of touched buckets per iteration, how many of those changed any point, how many
-were refreshed, the same two counts on the busiest wave (the one the others wait for at the barrier), and the histogram of
-the busiest wave's touched count.  `kd` is the yardstick of what a better partition than any curve over cells could give.
+were refreshed, the same two counts on the busiest wave (the one the others wait for at the barrier), how often the wave that
+wins an iteration did not have to search its candidate in it (`winner: clean`: its own-candidate mask is ready and the box test
+leaves its chain), how often it is the previous winner's wave, the extra buckets a reused mask walks per iteration, and the
+histogram of the busiest wave's touched count.  `kd` is the yardstick of what a better partition than any curve over cells could give.
 
 The samples it picks on the way are farthest point sampling itself; --check compares them with a plain numpy FPS, and the
 `hilbert` mapping with the table the library exports (tgn_fps_bucket_order).  numpy only, no GPU.
@@ -172,8 +174,23 @@ def _dist(dx, dy, dz):
     return ((dx * dx).astype(F32) + (dy * dy).astype(F32)).astype(F32) + (dz * dz).astype(F32)   # dist_direct_nofma
 
 
-def simulate(xyz, m, order="hilbert", bits=4, perm=3, nt=512, p=48):
-    """Run the kernel's bookkeeping for m samples.  Returns (indices, stats)."""
+def _box_test(blo, bhi, bmax, q):
+    """fps_box_mask of the kernel: True where a sample at q may change a bucket (fp32, the update's operation order)."""
+    e = np.fmax(np.fmax(blo - q, q - bhi), F32(0)).astype(F32)
+    return ~(_dist(e[:, 0], e[:, 1], e[:, 2]) >= bmax)
+
+
+def simulate(xyz, m, order="hilbert", bits=4, perm=3, nt=512, p=48, own_rule="b", trace=None):
+    """Run the kernel's bookkeeping for m samples.  Returns (indices, stats).
+
+    Every wave's candidate is tracked as the kernel tracks it: searched again only when the bucket that holds it is refreshed.  A
+    wave that did not search in an iteration takes the box test of its own buckets against its own candidate before the barrier
+    (`own mask`), and the wave that wins uses that mask for the next iteration instead of the test at the hand-off.  own_rule "a"
+    drops the own mask whenever a bucket of the wave is refreshed (it is then the mask of the hand-off, bit for bit); "b" keeps it
+    until the wave searches again (bucket maxima only shrink, so it contains the mask of the hand-off).  `trace`, if a list, gets
+    one (j, winning wave, reused, mask used for the wave's buckets, mask of the hand-off for them) per iteration."""
+    if own_rule not in ("a", "b"):
+        raise ValueError(f"own_rule {own_rule!r}: expected a or b")
     xyz = np.ascontiguousarray(xyz, dtype=F32)[:, :3]
     n = xyz.shape[0]
     nw = nt // WAVE
@@ -201,12 +218,26 @@ def simulate(xyz, m, order="hilbert", bits=4, perm=3, nt=512, p=48):
     busy_t = np.zeros(m, dtype=np.int64)
     busy_r = np.zeros(m, dtype=np.int64)
     q = xyz[0] if n else np.zeros(3, dtype=F32)
-    zero = F32(0)
+    # per wave: the bucket of its candidate (-1: to be searched), the candidate point, and the mask taken against it
+    wave_buckets = [np.nonzero(wave_of == w)[0] for w in range(nw)]
+    cand_bucket = np.full(nw, -1, dtype=np.int64)
+    cand_pt = np.zeros(nw, dtype=np.int64)
+    dirty = np.ones(nw, dtype=bool)
+    own_ok = np.zeros(nw, dtype=bool)
+    own_mask = [np.zeros(b.size, dtype=bool) for b in wave_buckets]
+    extra = np.zeros(m, dtype=np.int64)         # buckets walked only because a reused mask was older than the hand-off's
+    clean = same = 0
+    prev_wl = -1
     with np.errstate(invalid="ignore", over="ignore"):
+        exact = _box_test(blo, bhi, bmax, q)    # the mask of iteration 1, taken in front of the loop from point 0
+        used = exact.copy()
         for j in range(1, m):
-            e = np.fmax(np.fmax(blo - q, q - bhi), zero).astype(F32)
-            L = _dist(e[:, 0], e[:, 1], e[:, 2])
-            T = np.nonzero(~(L >= bmax))[0]
+            extra[j] = int((used & ~exact).sum())
+            U = np.nonzero(used & ~exact)[0]
+            if U.size:                          # a bucket of a stale mask: its update is a no-op, and nothing is refreshed
+                du = (pts[U] - q).astype(F32)
+                assert not (_dist(du[:, :, 0], du[:, :, 1], du[:, :, 2]) < d[U]).any()
+            T = np.nonzero(exact)[0]
             if T.size:
                 dT = d[T]
                 diff = (pts[T] - q).astype(F32)
@@ -221,22 +252,55 @@ def simulate(xyz, m, order="hilbert", bits=4, perm=3, nt=512, p=48):
                     mx = ndr.max(axis=1)
                     bmax[R] = mx
                     barg[R] = np.where(ndr == mx[:, None], key[R], np.iinfo(np.int64).max).min(axis=1)
+                    dirty[wave_of[R[R == cand_bucket[wave_of[R]]]]] = True
+                    if own_rule == "a":
+                        own_ok[wave_of[R]] = False
                 touched[j] = T.size
                 changed[j] = int(closer.any(axis=1).sum())
                 refreshed[j] = R.size
                 busy_t[j] = np.bincount(wave_of[T], minlength=nw).max()
                 if R.size:
                     busy_r[j] = np.bincount(wave_of[R], minlength=nw).max()
+            searched = dirty.copy()
+            for w in np.nonzero(dirty)[0]:      # section B: the wave's candidate, first index on ties
+                wb = wave_buckets[w]
+                if wb.size and bmax[wb].max() >= 0:
+                    at = wb[bmax[wb] == bmax[wb].max()]
+                    cand_bucket[w] = at[np.argmin(barg[at])]
+                    cand_pt[w] = barg[cand_bucket[w]]
+                dirty[w] = False
+                own_ok[w] = False
+            for w in np.nonzero(~searched & ~own_ok)[0]:    # off the chain, before the barrier
+                wb = wave_buckets[w]
+                own_mask[w] = _box_test(blo[wb], bhi[wb], bmax[wb], xyz[cand_pt[w]] if cand_bucket[w] >= 0 else np.zeros(3, dtype=F32))
+                own_ok[w] = True
             top = bmax.max()
             k = int(barg[bmax == top].min()) if top >= 0 else 0
             idx[j] = k
             q = xyz[k]
+            exact = _box_test(blo, bhi, bmax, q)            # the hand-off: the mask of iteration j + 1
+            used = exact.copy()
+            if top >= 0:
+                live = cand_bucket >= 0
+                wl = int(np.nonzero(live)[0][np.lexsort((cand_pt[live], -bmax[cand_bucket[live]]))[0]])
+                assert cand_pt[wl] == k, "the winning wave's candidate is not the block's arg-max"
+                reused = bool(own_ok[wl])
+                wb = wave_buckets[wl]
+                if reused:
+                    used[wb] = own_mask[wl]
+                if trace is not None:
+                    trace.append((j, wl, reused, used[wb].copy(), exact[wb].copy()))
+                clean += not searched[wl]
+                same += wl == prev_wl
+                prev_wl = wl
     it = max(m - 1, 1)
     stats = {
         "n": n, "m": m, "buckets": nb, "order": order, "bits": bits, "perm": perm, "nt": nt, "p": p,
         "touched": touched.sum() / it, "changed": changed.sum() / it, "refreshed": refreshed.sum() / it,
         "busiest_touched": busy_t.sum() / it, "busiest_refreshed": busy_r.sum() / it,
         "busiest_hist": np.bincount(busy_t[1:]).tolist(),
+        # the winning wave: did not search in the iteration it wins (its own mask can be ready); is the previous winner's wave
+        "winner_clean": clean / it, "winner_same_wave": same / it, "own_rule": own_rule, "extra_touched": extra.sum() / it,
     }
     return idx, stats
 
@@ -264,14 +328,16 @@ def _synth():
 
 
 HEADER = (f"{'cloud':>6s} {'order':>8s} {'bits':>4s} {'perm':>4s} {'kernel':>9s} {'buckets':>7s} | {'touched':>8s} {'changed':>8s} "
-          f"{'refreshed':>9s} | {'busiest wave: touched':>21s} {'refreshed':>9s} | histogram of the busiest wave's touched count")
+          f"{'refreshed':>9s} | {'busiest wave: touched':>21s} {'refreshed':>9s} | {'winner: clean':>13s} {'same wave':>9s} {'extra':>6s} | "
+          f"histogram of the busiest wave's touched count")
 
 
 def row(name, s):
     kernel = f"<{s['nt']},{s['p']}>"
     hist = " ".join(f"{i}:{c}" for i, c in enumerate(s["busiest_hist"]) if c)
     return (f"{name:>6s} {s['order']:>8s} {s['bits']:4d} {s['perm']:4d} {kernel:>9s} {s['buckets']:7d} | {s['touched']:8.2f} "
-            f"{s['changed']:8.2f} {s['refreshed']:9.2f} | {s['busiest_touched']:21.3f} {s['busiest_refreshed']:9.3f} | {hist}")
+            f"{s['changed']:8.2f} {s['refreshed']:9.2f} | {s['busiest_touched']:21.3f} {s['busiest_refreshed']:9.3f} | "
+            f"{s['winner_clean']:13.3f} {s['winner_same_wave']:9.3f} {s['extra_touched']:6.3f} | {hist}")
 
 
 def main(argv=None):

@@ -22,13 +22,29 @@
 //     point) and get their (bmax, key) refreshed by a 64-lane DPP max.
 //   * a wave's candidate is the max over its <= 64 bucket maxima (cached while the wave is untouched);
 //     the block argmax is the packed 64-bit max of fps.hip.
+//   * the box test does not sit in front of the iteration (TGN_FPS_OWN_MASK; 0 gives that form).  The mask of iteration j + 1 is
+//     taken at the end of iteration j, behind the hand-off at which the new sample q becomes known -- and the wave that WINS
+//     the hand-off, the one with the update, the refresh and the next candidate search in front of it, does not take it there
+//     at all.  q is the candidate (wx, wy, wz) that wave published, and it has known that candidate since its last search: a
+//     wave that did not search in an iteration evaluates fps_box_mask against its OWN candidate right before the barrier,
+//     where it would only wait (own_mask / own_ok), and if it wins -- in that iteration or any later one before it searches
+//     again, 87 - 90 % of the iterations on scans -- the mask is there, and so are q and its key (its own SGPRs: no readlane).
+//     Staleness, rule (b): own_mask stays valid until the wave SEARCHES again, also across refreshes of its other buckets.
+//     The boxes never change and bmax only shrinks, and `!(L >= bmax)` can only turn false as bmax shrinks, so a mask taken
+//     with an older bmax is a superset of the mask of the hand-off.  For a bucket in the superset only, L >= bmax holds now:
+//     its update is the provable no-op above, and the `unchanged` test keeps the refresh away.  (A refresh of the bucket that
+//     HOLDS the candidate sets `dirty`, the wave searches, and own_ok is cleared.)  Rule (a), dropping the mask at every
+//     refresh, is bit for bit the mask of the hand-off and measured slower (docs/NEGATIVE_RESULTS.md); the model counts one
+//     extra bucket per 350 - 1000 iterations under (b).  Both test and reuse go through fps_box_mask, the one place the
+//     arithmetic is written.
 //
 // Results are bit-identical to the plain kernel and to the oracle by construction (skipped updates are
 // provably no-ops); tests/test_gpu_parity.py runs every launch shape against the oracle, including
-// lattices and duplicated vertices (exact ties) and NaN coordinates.
-// Measured (profiles/fps_bucket_order_before_after.txt): 24 000 -> 4096 runs at 0.75 us per iteration (6.0 of 375 buckets
-// touched on average, 3.2 of them with a point that changes; what remains is the latency of the 1.6 bucket updates on the
-// busiest wave plus the block hand-off).
+// lattices and duplicated vertices (exact ties) and NaN coordinates; tests/test_gpu_fps_own_mask.py the reuse and the
+// fall-back path of the own-candidate mask.
+// Measured (profiles/fps_own_mask_before_after.txt): 24 000 -> 4096 runs at 0.73 us per iteration (0.745 - 0.75 with the box
+// test in front, profiles/fps_bucket_order_before_after.txt; 6.0 of 375 buckets touched on average, 3.2 of them with a point
+// that changes; what remains is the latency of the 1.6 bucket updates on the busiest wave plus the block hand-off).
 #include "dispatch.h"
 #include "fps_common.h"
 
@@ -39,6 +55,12 @@
 
 #ifndef TGN_REFRESH_SKIP
 #define TGN_REFRESH_SKIP 1
+#endif
+// 1: the box test of an iteration is evaluated behind the hand-off of the previous one, and the winning wave takes it from a mask
+// it worked out off the chain, against its own candidate, while it waited at the barrier (kernel header).  0: the box test sits at
+// the head of the iteration, in front of everything, for every wave.
+#ifndef TGN_FPS_OWN_MASK
+#define TGN_FPS_OWN_MASK 1
 #endif
 // Which wave holds bucket b = NW * s + i of the curve in its register slot s: wave (i + s) % NW.  The buckets one sample touches
 // are a run of neighbours along the curve plus whatever the curve folds next to them.  Every NW consecutive buckets sit on NW
@@ -79,10 +101,33 @@ constexpr int next_pow2(int v) {
     return p;
 }
 
+// The box test of fps_bucket_kernel: which of the P buckets of this wave can a sample at (ax, ay, az) change?  Lane s holds bucket
+// s's box and its largest minimum distance bmax; bit s of the result is set unless the distance L from the sample to the box, taken
+// with the operation order of the point update itself, is >= bmax (monotone lower bound, exact: kernel header).  The ONE place this
+// arithmetic is written: the test at the hand-off and the one a wave makes ahead of time against its own candidate must agree bit
+// for bit.
+template <bool FMA, int P>
+__device__ __forceinline__ unsigned long long fps_box_mask(float blo0, float blo1, float blo2, float bhi0, float bhi1, float bhi2,
+                                                            float bmax, float ax, float ay, float az) {
+    // (x, y) as packed fp32 pairs: a lone wave pays per instruction, not per lane-operation
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    const f2 axy = {ax, ay};
+    const f2 lo = f2{blo0, blo1} - axy, hi = axy - f2{bhi0, bhi1};
+    const float ex = fmaxf(fmaxf(lo.x, hi.x), 0.0f);
+    const float ey = fmaxf(fmaxf(lo.y, hi.y), 0.0f);
+    const float ez = fmaxf(fmaxf(blo2 - az, az - bhi2), 0.0f);
+    const float L = FMA ? dist_direct_fma(ex, ey, ez) : dist_direct_nofma(ex, ey, ez);
+    // lane mask of the compare, restricted to the P metadata lanes by a constant (a ballot of `lane < P && ...`
+    // makes the compiler rebuild the mask through a 0/1 select)
+    constexpr unsigned long long kSlotMask = P >= 64 ? ~0ull : ((1ull << P) - 1ull);
+    return ballot64(!(L >= bmax)) & kSlotMask;
+}
+
 template <int NT, int P, int MODE>
 __global__ __launch_bounds__(NT) void fps_bucket_kernel(FpsArgs a) {
     constexpr bool FMA = (MODE & 1) != 0, TREE = (MODE & 2) != 0, CERT = (MODE & kFpsModeCert) != 0;
     constexpr int NW = NT / kWave;
+    constexpr bool kOwnMask = TGN_FPS_OWN_MASK != 0;
     constexpr int CAP = NT * P;
     static_assert(P <= kWave, "bucket metadata lives in lanes 0..P-1");
     static_assert(CAP <= 32768, "15-bit local indices");
@@ -296,20 +341,18 @@ __global__ __launch_bounds__(NT) void fps_bucket_kernel(FpsArgs a) {
     // the 4-wave kernels, which run beside the level-1 ball query, measured no better with it and keep lane 0)
     constexpr bool kRecAllLanes = NT >= 512;
 
+    constexpr unsigned long long kSlotMask = P >= 64 ? ~0ull : ((1ull << P) - 1ull);
+    auto box_mask = [&](float ax, float ay, float az) -> unsigned long long {  // against the boxes and bmax as they are NOW
+        return fps_box_mask<FMA, P>(blo0, blo1, blo2, bhi0, bhi1, bhi2, bmax, ax, ay, az);
+    };
+    // The mask of iteration j is worked out at the end of iteration j - 1, behind the hand-off (for j = 1: here, from point 0).
+    // own_mask is the same test against this wave's OWN candidate (wx, wy, wz), taken while the wave waits at the barrier.
+    unsigned long long mask = kOwnMask ? box_mask(qx, qy, qz) : 0ull, own_mask = 0ull;
+    bool own_ok = false;  // wave-uniform: own_mask was taken for the candidate this wave publishes
+
     for (int j = 1; j < m; ++j) {
         // ---- A. which of my buckets can the new sample change? (monotone lower bound, exact) -------------
-        // (x, y) as packed fp32 pairs: a lone wave pays per instruction, not per lane-operation
-        typedef float f2 __attribute__((ext_vector_type(2)));
-        const f2 qxy = {qx, qy};
-        const f2 lo = f2{blo0, blo1} - qxy, hi = qxy - f2{bhi0, bhi1};
-        const float ex = fmaxf(fmaxf(lo.x, hi.x), 0.0f);
-        const float ey = fmaxf(fmaxf(lo.y, hi.y), 0.0f);
-        const float ez = fmaxf(fmaxf(blo2 - qz, qz - bhi2), 0.0f);
-        const float L = FMA ? dist_direct_fma(ex, ey, ez) : dist_direct_nofma(ex, ey, ez);
-        // lane mask of the compare, restricted to the P metadata lanes by a constant (a ballot of `lane < P && ...`
-        // makes the compiler rebuild the mask through a 0/1 select)
-        constexpr unsigned long long kSlotMask = P >= 64 ? ~0ull : ((1ull << P) - 1ull);
-        const unsigned long long mask = ballot64(!(L >= bmax)) & kSlotMask;
+        if constexpr (!kOwnMask) mask = box_mask(qx, qy, qz);
         if (mask) {  // wave-uniform
             // A lone wave issues roughly one instruction per 5 cycles whatever its kind, so the mask is walked
             // hierarchically (groups of 8 slots, 32-bit tests: 2 scalar instructions per test) rather than bit by bit.
@@ -362,6 +405,7 @@ __global__ __launch_bounds__(NT) void fps_bucket_kernel(FpsArgs a) {
             }
         }
         // ---- B. wave candidate = max over my bucket maxima (recomputed only if a bucket changed) ---------
+        const bool searched = dirty;  // wave-uniform
         if (dirty) {
             // the arg-max records of ALL my buckets (coordinates, tie key) are requested BEFORE the reduction that says which
             // one is wanted: the LDS round trip then hides behind the six DPP steps instead of following them (this is the
@@ -386,9 +430,11 @@ __global__ __launch_bounds__(NT) void fps_bucket_kernel(FpsArgs a) {
             pub_bits = wm < 0.0f ? 0u : __float_as_uint(wm);  // what the hand-off publishes (a wave without points: 0, ~0)
             pub_key = wm < 0.0f ? 0xFFFFFFFFu : wkey;
             dirty = false;
+            own_ok = false;  // own_mask belongs to the candidate before this one
         }
         // ---- C. block argmax over the wave candidates: one LDS record per wave, ONE barrier ------------------
         unsigned kwin;
+        bool mine = false;  // wave-uniform: the new sample is this wave's own candidate
         if constexpr (NW == 1) {
             kwin = wm < 0.0f ? 0xFFFFFFFFu : wkey;
             if constexpr (CERT) cert.update(wm < 0.0f ? 0u : __float_as_uint(wm));
@@ -399,6 +445,14 @@ __global__ __launch_bounds__(NT) void fps_bucket_kernel(FpsArgs a) {
             if (kRecAllLanes || lane == 0) {  // {value bits, tie key} and {x, y, z}: 8 + 12 bytes of the wave's 32-byte record
                 *(uint2 *)(recb + wr_off) = make_uint2(pub_bits, pub_key);
                 *(float3 *)(recb + wr_off + 16) = make_float3(wx, wy, wz);
+            }
+            // Off the chain: a wave that did not search this iteration is early at the barrier (the one that searched is the one
+            // the others wait for, and pays nothing here).  If it wins, now or in any later iteration until it searches again,
+            // the new sample IS (wx, wy, wz), and its mask is ready.  Out of line: the wave that searched falls through to the
+            // barrier, the waves with time to spare take the branch.
+            if (__builtin_expect(kOwnMask && !searched && !own_ok, 0)) {  // wave-uniform
+                own_mask = box_mask(wx, wy, wz);
+                own_ok = true;
             }
             __syncthreads();
             // distances are >= 0: their bit patterns order like unsigned integers
@@ -430,10 +484,21 @@ __global__ __launch_bounds__(NT) void fps_bucket_kernel(FpsArgs a) {
                 const unsigned kmin = __builtin_amdgcn_readfirstlane(wave_min_u32_shfl(kk));
                 wl = __builtin_ctzll(ballot64(kk == kmin));
             }
-            kwin = (unsigned)__builtin_amdgcn_readlane((int)r0.y, wl);
-            qx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(r1.x), wl));
-            qy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(r1.y), wl));
-            qz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(r1.z), wl));
+            // The winning wave is the one with the update, the refresh and the new search in front of it, so the code is laid out for
+            // IT: its sample and key are what it published (already in its SGPRs: no v_readlane, no wait for the coordinates' LDS
+            // read), and it falls through here and below; the seven waves with time to spare take the branches.
+            mine = kOwnMask && wl == wave;
+            if (__builtin_expect(mine, 1)) {
+                kwin = pub_key;
+                qx = wx;
+                qy = wy;
+                qz = wz;
+            } else {
+                kwin = (unsigned)__builtin_amdgcn_readlane((int)r0.y, wl);
+                qx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(r1.x), wl));
+                qy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(r1.y), wl));
+                qz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(r1.z), wl));
+            }
         }
         int k = kwin == 0xFFFFFFFFu ? 0 : (int)kwin;      // (records carry original indices in every mode)
         k = __builtin_amdgcn_readfirstlane(k);
@@ -443,6 +508,13 @@ __global__ __launch_bounds__(NT) void fps_bucket_kernel(FpsArgs a) {
             const float4 o = outbuf[tid];
             fps_emit(a, start_m + j - (NT - 1) + tid, start_n, __float_as_int(o.x), o.y, o.z, o.w);
             __syncthreads();
+        }
+        // ---- A', for iteration j + 1: the winning wave has the mask already unless it searched in this very iteration ----
+        if constexpr (kOwnMask) {
+            if (__builtin_expect(mine && own_ok, 1))
+                mask = own_mask;
+            else
+                mask = box_mask(qx, qy, qz);
         }
     }
     if (((m - 1) & (NT - 1)) != NT - 1) {  // rows of the last, partial chunk
