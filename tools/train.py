@@ -8,7 +8,9 @@
 The arguments are start_train.py's, plus --epochs (the reference loops 100 000 times) and --seed (numpy's and torch's generators:
 shuffling, augmentation draws, initial weights, tsegnet's 8-of-T crop choice).  The configuration is the reference's:
 train_configs/train_config_maker.get_default_config merged with the `config` dict of the Python file at --config_path, so the
-reference's own train_configs/*.py files work as they are (for tgnet_fps set the two cbl weights to 0: see training.py).
+reference's own train_configs/*.py files work as they are.  tr_set.contrastive_boundary defaults to True here, so tgnet_fps trains
+on the cbl_loss_1 / cbl_loss_2 weights its file names (losses.contrast_boundary_loss); --no_contrastive_boundary leaves the key
+out, and a non-zero cbl weight is then refused (training.py).
 Prints the trainer's JSON lines: one per scheduler step, one per epoch.  Checkpoints: ckpts/<experiment_name>.h5 after every epoch,
 ckpts/<experiment_name>_val.h5 at every best validation total; both load into inference.make_inference_pipeline."""
 import argparse
@@ -49,6 +51,8 @@ def main(argv=None):
     ap.add_argument("--val_data_split_txt_path", default="base_name_val_fold.txt", help="patient ids of the validation split")
     ap.add_argument("--epochs", type=int, default=100000, help="epochs to run (the reference's loop count is the default)")
     ap.add_argument("--seed", type=int, default=None, help="seeds numpy's and torch's generators")
+    ap.add_argument("--no_contrastive_boundary", action="store_true",
+                    help="do not set tr_set.contrastive_boundary: tgnet_fps then refuses non-zero cbl_loss_1 / cbl_loss_2 weights")
     args = ap.parse_args(argv)
 
     import numpy as np
@@ -59,6 +63,8 @@ def main(argv=None):
         torch.manual_seed(args.seed)
     config = get_train_config(args.config_path, args.experiment_name, args.input_data_dir_path, args.train_data_split_txt_path,
                               args.val_data_split_txt_path)
+    if not args.no_contrastive_boundary and "tr_set" in config:
+        config["tr_set"].setdefault("contrastive_boundary", True)
     model = training.make_training_model(args.model_name, config)
     gen_set = [training.get_generator_set(config["generator"])]
     print("train_set", len(gen_set[0][0]), file=sys.stderr)

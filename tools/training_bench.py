@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """What the training entry point's bookkeeping costs: one training step of `training`'s tgnet_fps and pointnetpp models on ONE
-24 000-point scan, batch 1, fp32, against a bare loop in the same process.
+24 000-point scan, batch 1, fp32, against a bare loop in the same process.  `tgnet_fps_cbl` is tgnet_fps with the contrastive-boundary
+criterion on (tr_set.contrastive_boundary, both cbl weights 1): what the criterion adds to a step is its difference to `tgnet_fps`.
 
   trainer   model.step(batch_idx, batch_item, "train") and the three get_loss_dict_for_print calls Trainer.train makes per batch: the
             host-to-device copy of the item, forward, losses, backward, optimiser, LossMap, ONE device read.
@@ -30,6 +31,11 @@ CONFIGS = {
                                       "offset_1_dir_loss": 0.03, "chamf_1_loss": 0.15}},
                   "model_parameter": MODEL_PARAMETER},
 }
+# tgnet_fps with the contrastive-boundary criterion on: train_configs/tgnet_fps.py's weights for the two cbl terms
+CONFIGS["tgnet_fps_cbl"] = copy.deepcopy(CONFIGS["tgnet_fps"])
+CONFIGS["tgnet_fps_cbl"]["tr_set"]["loss"].update(cbl_loss_1=1, cbl_loss_2=1)
+CONFIGS["tgnet_fps_cbl"]["tr_set"]["contrastive_boundary"] = True
+MODEL_NAME = {"tgnet_fps_cbl": "tgnet_fps"}
 
 
 def quartiles(ms):
@@ -46,8 +52,8 @@ def run(name, points, steps, warmup, dev):
     item = {"feat": torch.from_numpy(np.ascontiguousarray(rows.T))[None], "gt_seg_label": torch.from_numpy(lab).view(1, 1, -1)}
     torch.manual_seed(0)
     np.random.seed(0)
-    model = training.make_training_model(name, cfg)
-    bare = training.make_training_model(name, cfg)            # its module, optimiser and loss functions, driven by hand below
+    model = training.make_training_model(MODEL_NAME.get(name, name), cfg)
+    bare = training.make_training_model(MODEL_NAME.get(name, name), cfg)            # its module, optimiser and loss functions, driven by hand below
     bare.module.load_state_dict(model.module.state_dict())
     feat, seg = item["feat"].to(dev), item["gt_seg_label"].to(dev)
 
@@ -59,7 +65,7 @@ def run(name, points, steps, warmup, dev):
 
     def bare_step(i, copy_item=False):
         f, g = (item["feat"].to(dev), item["gt_seg_label"].to(dev)) if copy_item else (feat, seg)
-        output = bare.module([f, g])
+        output = bare.forward([f, g])
         total = 0
         for value, weight in bare.losses_of(output, g, f).values():
             total = total + value * weight

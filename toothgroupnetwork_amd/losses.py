@@ -9,6 +9,9 @@
   segmentation_loss                                       autograd over crops x 3072 elements, no kernel of their own
   seg_label_to_cent                                       ops_utils.seg_label_to_cent through crops.label_centroids: 16 slots and an `exists` mask
   tsegnet_loss_terms                                      all six terms of TSegNetModel.get_loss from the module's output dict and the labels
+  contrast_boundary_stage, contrast_boundary_loss         the contrastive-boundary criterion (models/modules/cbl_point_transformer/heads.py:63-253
+                                                          with default.yaml's configuration): the neighbour lists are tgn_knnquery*, the
+                                                          (m, K-1, 32) latent differences and their gradient tgn_subtraction_forward / _backward
 
 The reference loops over B x 16 teeth with boolean masks (one host round trip per tooth and scan) and sorts a (B, M, C) distance
 matrix to read two columns; here a forward is the per-tooth counts and centroids (crops.label_centroids), a point pass and a finishing
@@ -33,7 +36,7 @@ import torch
 import torch.nn.functional as F
 from torch.autograd import Function
 
-from . import _lib, crops
+from . import _lib, crops, pointops
 
 _fwd = torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
 _bwd = torch.amp.custom_bwd(device_type="cuda")
@@ -295,3 +298,78 @@ def tsegnet_centroid_loss_terms(outputs, centroid_coords, exists=None):
     ops_utils.seg_label_to_cent can be passed as they are instead of compacted on the host."""
     dist_loss, cent_loss, chamf_loss = centroid_loss(outputs["offset_result"], outputs["l3_xyz"], outputs["dist_result"], centroid_coords, exists)
     return {"dist_loss": dist_loss, "cent_loss": cent_loss, "chamf_loss": chamf_loss}
+
+
+# ---- the contrastive-boundary criterion -----------------------------------------------------------------------------------------------
+
+CBL_WEIGHT = 0.1      # default.yaml `weight: w.1`
+CBL_EPS = 1e-12       # basic_operators._eps
+_VOTE_BASE = 1 << 20  # stage_vote packs (count, label) into one int64: labels stay below it
+
+
+def stage_vote(p0, o0, p, o, target, kr):
+    """The labels of a coarser decoder stage (basic_operators.get_subscene_label and the arg-max of heads.posmask_cnt): every point of
+    (p, o) takes the `kr` nearest stage-0 points of its own scan (knnquery(kr, p0, p, o0, o)); the reference averages their one-hot
+    targets and takes the arg-max.  The averaged counts are small integers over the same kr, so that is a majority vote, computed here
+    on integers; equal counts go to the LOWEST label (the first maximum, what the reference's CPU arg-max returns), stated here instead
+    of left to the device's arg-max.  target (n,) int64 in [0, 2^20) -> (m,) int64.  No synchronisation."""
+    idx = pointops.knn_indices(kr, p0, p, o0, o).long()
+    votes = target[idx]                                                     # (m, kr)
+    if kr == 1:
+        return votes[:, 0]
+    count = (votes[:, :, None] == votes[:, None, :]).sum(2)                 # (m, kr): how often slot j's label occurs in the row
+    key = count * _VOTE_BASE + (_VOTE_BASE - 1 - votes)                     # the largest count first, then the lowest label
+    return _VOTE_BASE - 1 - key.max(1).values % _VOTE_BASE
+
+
+def contrast_boundary_stage(p, f, o, stage_labels, nsample):
+    """heads.ContrastHead.point_contrast for one decoder stage: p (m, 3), latent features f (m, C), offsets o (b), integer labels
+    stage_labels (m,), nsample = K -> (loss, count): the soft nearest-neighbour contrast -log(sum_j e_ij [label_j == label_i] /
+    sum_j e_ij + 1e-12) with e_ij = exp(-d_ij + min_j d_ij), d_ij = sqrt(|f_i - f_j|^2 + 1e-12) over the K - 1 columns 1.. of
+    knnquery(K, p, p, o, o) -- column 0 is dropped whatever it holds, and the slots a scan shorter than K leaves are its first
+    point, as in the reference -- averaged over the points that have both a neighbour of their own label and one of another, times
+    0.1; `count` is the number of such points, an int64 device scalar.
+
+    Static shapes: points outside the mask are skipped with torch.where and get a zero gradient, the mean is sum / max(count, 1), so
+    a stage without such a point gives 0 (the reference returns 0.0 for stages >= 1 and raises at stage 0).  The differences
+    f_i - f_idx[i, j] are pointops.subtraction (tgn_subtraction_forward; the gradient is tgn_subtraction_backward's float atomics), so
+    no gathered copy of the neighbour features is kept beside the (m, K-1, C) difference tensor.  The rest is float32 torch on (m, K-1).
+    No synchronisation; forward and backward can be captured in a graph."""
+    K1 = int(nsample) - 1
+    if K1 < 1:
+        raise ValueError(f"nsample must be at least 2 (one neighbour beside the dropped column 0), got {nsample}")
+    lab = stage_labels.reshape(-1).long()
+    if lab.shape[0] != p.shape[0] or f.shape[0] != p.shape[0]:
+        raise ValueError(f"p, f and stage_labels must hold the same number of points, got {p.shape[0]}, {f.shape[0]} and {lab.shape[0]}")
+    idx = pointops.knn_indices(int(nsample), p, p, o, o)[:, 1:].contiguous()            # (m, K-1) int32
+    posmask = lab[idx.long()] == lab[:, None]
+    npos = posmask.sum(1)
+    point_mask = (npos > 0) & (npos < K1)
+    diff = pointops.subtraction(f, f, idx)                                               # (m, K-1, C) float32
+    z = -torch.sqrt((diff * diff).sum(2) + CBL_EPS)
+    e = torch.exp(z - z.max(1, keepdim=True).values)
+    neg = e.sum(1)
+    pos = torch.where(point_mask, (e * posmask).sum(1), neg)                             # unmasked rows: log(1 + eps), a finite backward
+    per_point = -torch.log(pos / neg + CBL_EPS)
+    count = point_mask.sum()
+    total = torch.where(point_mask, per_point, torch.zeros_like(per_point)).sum()
+    return total / count.clamp(min=1).to(total.dtype) * CBL_WEIGHT, count
+
+
+def contrast_boundary_loss(up_points, latents, target, nsample, stride):
+    """heads.ContrastHead.forward over the decoder stages (`stage: Ua`): up_points = [[p_i, o_i], ...], latents = [f_i (m_i, 32), ...],
+    target (n_0,) integer, already + 1 (cbl_point_transformer_module.py:200-202) -> (losses (stages,), counts (stages,) int64).  Stage 0
+    is labelled by the target itself, stage i >= 1 by stage_vote with kr = prod(stride[:i]) (get_model sets nstride = stride)."""
+    if len(up_points) != len(latents):
+        raise ValueError(f"{len(up_points)} stages of points and {len(latents)} of latent features")
+    target = target.reshape(-1).long()
+    p0, o0 = up_points[0]
+    if target.shape[0] != p0.shape[0]:
+        raise ValueError(f"target must hold one label per stage-0 point ({p0.shape[0]}), got {target.shape[0]}")
+    stage_losses, counts = [], []
+    for i, ((p, o), f) in enumerate(zip(up_points, latents)):
+        labels = target if i == 0 else stage_vote(p0, o0, p, o, target, int(np.prod(stride[:i])))
+        loss, count = contrast_boundary_stage(p, f, o, labels, nsample[i])
+        stage_losses.append(loss)
+        counts.append(count)
+    return torch.stack(stage_losses), torch.stack(counts)

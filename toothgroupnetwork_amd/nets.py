@@ -13,8 +13,8 @@ of the fused eval paths.  Parameter names and shapes equal the reference classes
                        of the reference (`flatten_sa`, :28).
   PointTransformerSeg  models/modules/cbl_point_transformer/cbl_point_transformer_module.py:28-216 with the configuration
                        the reference ships (default.yaml: five stages, `multi` heads over the decoder stages, latent
-                       features concatenated); BASELINE.json configs 3 / 4's network.  Inference outputs only: the
-                       contrastive-boundary criterion of training (heads.py:62-253) is the reference's own Python.
+                       features concatenated); BASELINE.json configs 3 / 4's network.  forward(contrast=True) adds the
+                       contrastive-boundary criterion of training (heads.py:62-253) as losses.contrast_boundary_loss.
   DGCnnModule          models/modules/dgcnn.py:43-143 (the "dgcnn" model): three EdgeConv levels over feature-space kNN graphs,
                        fused in eval mode (dgcnn.py of this package, re-exported here).
   PointFirstModule     models/modules/pointnet.py:49-68 (the "pointnet" model): PointNet at scale 2 with both transform regressors;
@@ -24,7 +24,7 @@ of the fused eval paths.  Parameter names and shapes equal the reference classes
                        PointTransformerSeg over the scan, on-device tooth crops (crops.tooth_crops), a second PointTransformerSeg over
                        all crops as one batch.  Without labels the centroids come from on-device clustering (cluster.py, which
                        reaches crop.hip's kNN and label means through crops.py).  The offset, direction and chamfer terms of its loss are
-                       losses.grouping_loss_terms (fused kernels, csrc/loss.hip); the cbl terms stay the reference's Python.
+                       losses.grouping_loss_terms (fused kernels, csrc/loss.hip); forward(contrast=True) adds cbl_loss_1 / cbl_loss_2.
                        `block_num` 5 (tgnet_fps, tgnet's first module) or 2 (tgnet's boundary module,
                        inference_pipeline_maker.py:43-54); up to crops.MAX_CLUSTERS labels.
   PointPpFirstModule, PointTransformerModule  models/modules/pointnet_pp.py:73-92 and models/modules/point_transformer.py:4-28: the wrappers
@@ -41,7 +41,7 @@ import functools
 
 import numpy as np
 
-from . import _lib, cluster as _cluster, crops as _crops, fold, point_transformer as PT, pointops, tsegnet as _tsg
+from . import _lib, cluster as _cluster, crops as _crops, fold, losses as _losses, point_transformer as PT, pointops, tsegnet as _tsg
 from .dgcnn import DGCnnModule  # noqa: F401
 from .pointnet import PointFirstModule  # noqa: F401
 from .pointnet2_utils import PointNetFeaturePropagation, PointNetSetAbstraction, PointNetSetAbstractionMsg, linear_relu, square_distance
@@ -218,11 +218,15 @@ class MultiHead(nn.Module):
         self.infer_list = nn.ModuleList([_LatentMLP(f, base_fdim) for f in fdims])
         self.cls = nn.Linear(base_fdim * len(fdims), k)
 
-    def forward(self, up_list):
+    def forward(self, up_list, latents=None):
+        """latents: a list that receives every stage's MLP output BEFORE interpolation -- what the reference stores back as
+        stage['latent'] (heads.py:56-57) and its contrastive-boundary criterion reads."""
         p0, _, o0 = up_list[0]
         cols = []
         for i, ((p, x, o), mlp) in enumerate(zip(up_list, self.infer_list)):
             y = mlp(x)
+            if latents is not None:
+                latents.append(y)
             cols.append(y if i == 0 else pointops.interpolation(p, p0, y.contiguous(), o, o0, k=1))
         return self.cls(torch.cat(cols, 1))
 
@@ -240,6 +244,8 @@ class PointTransformerSeg(nn.Module):
         if block_num not in (2, 5):
             raise ValueError(f"block_num = {block_num}: the reference's forward exists for 2, 3 and 5 stages; 2 and 5 are mirrored")
         self.c, self.k, self.block_num = c, k, block_num
+        self.stride, self.nsample = tuple(stride)[:block_num], tuple(nsample)[:block_num]     # the criterion's nstride and nsample
+        self.cbl_counts = None                                                                # see forward(contrast=True)
         planes = tuple(planes)[:block_num]
         in_planes = c
         for i in range(block_num):
@@ -257,11 +263,25 @@ class PointTransformerSeg(nn.Module):
         self.offset_head = MultiHead(planes, 3, self.BASE_FDIM)
 
     @_one_index_check
-    def forward(self, inputs, all_offsets=False):
+    def forward(self, inputs, all_offsets=False, contrast=False):
         """inputs: [features (B, C, N)] -> [cls (B, k, N), offset (1, 3, N) or None, None, x1 (B*N, planes[0])]
         (cbl_point_transformer_module.py:196-216 without the training criterion).  The offset head runs for B == 1 only, as in the
-        reference; all_offsets=True runs it for any B (GroupingNetworkModule's unlabelled path, one scan at a time)."""
+        reference; all_offsets=True runs it for any B (GroupingNetworkModule's unlabelled path, one scan at a time).
+
+        contrast=True: inputs = [features, labels (B, 1, N) or (B, N)] -> [cbl_loss (block_num,), cls, offset, None, x1], the reference's
+        list for two inputs (:198-204): losses.contrast_boundary_loss on target = labels + 1 with this network's nsample and stride,
+        over the latent features the LAST head that ran left behind -- every head overwrites stage['latent'] (heads.py:57), so the
+        criterion reads the offset head's when it ran (B == 1, or all_offsets) and the class head's otherwise.  Checkpoints trained
+        with the reference carry that quirk, so it is kept.  `self.cbl_counts` is the number of contributing points per stage of THIS
+        forward, an int64 device tensor (a stage without one gives 0, where the reference raises at stage 0), and None after a forward
+        without the criterion; GroupingNetworkModule hands it on in its output dict."""
         feats = inputs[0]
+        if contrast:
+            if len(inputs) < 2 or inputs[1] is None:
+                raise ValueError("contrast=True needs the labels as inputs[1], (B, 1, N) or (B, N)")
+            if inputs[1].numel() != feats.shape[0] * feats.shape[2]:
+                raise ValueError(f"inputs[1] must hold one label per point, (B, 1, N) or (B, N) = ({feats.shape[0]}, {feats.shape[2]}), "
+                                 f"got {tuple(inputs[1].shape)}")
         B, C, N = feats.shape
         pxo = feats.permute(0, 2, 1)
         x = pxo.reshape(-1, C).contiguous()
@@ -280,9 +300,20 @@ class PointTransformerSeg(nn.Module):
             head = dec[0]([pi, xi, oi]) if above is None else dec[0]([pi, xi, oi], above)
             xi = dec[1:]([pi, head, oi])[1]
             above = up[i] = [pi, xi, oi]
-        cls = self.cls_head(up).view(B, N, self.k).permute(0, 2, 1)
-        offset = self.offset_head(up).view(B, N, 3).permute(0, 2, 1) if B == 1 or all_offsets else None
-        return [cls, offset, None, up[0][1]]
+        if not contrast:
+            self.cbl_counts = None
+            cls = self.cls_head(up).view(B, N, self.k).permute(0, 2, 1)
+            offset = self.offset_head(up).view(B, N, 3).permute(0, 2, 1) if B == 1 or all_offsets else None
+            return [cls, offset, None, up[0][1]]
+        latents = []
+        cls = self.cls_head(up, latents).view(B, N, self.k).permute(0, 2, 1)
+        offset = None
+        if B == 1 or all_offsets:
+            latents = []
+            offset = self.offset_head(up, latents).view(B, N, 3).permute(0, 2, 1)
+        cbl_loss, self.cbl_counts = _losses.contrast_boundary_loss([[pi, oi] for pi, _, oi in up], latents, inputs[1].reshape(-1).long() + 1,
+                                                                     self.nsample, self.stride)
+        return [cbl_loss, cls, offset, None, up[0][1]]
 
 
 class PointPpFirstModule(nn.Module):
@@ -326,8 +357,9 @@ class GroupingNetworkModule(nn.Module):
     (cluster.cluster_centroids, over crops.label_centroids).  The reference's
     unlabelled path works for B == 1 only (it indexes inputs[b_idx] and its offset head runs for B == 1); here every scan of a batch
     is clustered on its own, and offset_1 is then returned for every B.  The contrastive-boundary terms cbl_loss_1 / cbl_loss_2 of
-    training (the reference's criterion, heads.py:62-253) are left out, as for PointTransformerSeg, so `test` changes nothing here:
-    both stages always run without the criterion.  One host synchronisation per forward with labels (the tooth count, see
+    training (the reference's criterion, heads.py:62-253) are computed on request only: forward(contrast=True) with labels and
+    `not test` adds them (PointTransformerSeg.forward(contrast=True) of both stages); the reference computes them whenever it has
+    labels and `not test`.  Without `contrast`, `test` changes nothing here.  One host synchronisation per forward with labels (the tooth count, see
     crops.tooth_crops); the unlabelled path adds the clustering's (cluster.get_clustering_labels) and one per scan for its cluster
     count."""
 
@@ -346,26 +378,42 @@ class GroupingNetworkModule(nn.Module):
         self.second_ins_cent_model = PointTransformerSeg(c=mp["input_feat"], k=2, **arch)
         self.crop_sample_size = int(mp["crop_sample_size"])
 
-    def forward(self, inputs, test=False, centroids=None):
+    def forward(self, inputs, test=False, centroids=None, contrast=False):
         """inputs: [features (B, C, N)] or [features, labels (B, 1, N)] -> the reference's output dict (sem_1, offset_1, mask_1,
         first_features, sem_2, offset_2, mask_2, cropped_feature_ls, nn_crop_indexes and, with labels, cluster_gt_seg_label);
-        offset_2 is None unless there is exactly one crop (the reference's head runs for B == 1 only)."""
+        offset_2 is None unless there is exactly one crop (the reference's head runs for B == 1 only).
+        contrast=True, with labels and `not test`: also cbl_loss_1 and cbl_loss_2, (block_num,) each, and cbl_counts_1 / cbl_counts_2, the
+        number of contributing points per stage (int64, on the device) -- the first network's criterion
+        on the half-jaw labels (labels >= 9 minus 8: 10 classes with gingiva), the second's on the crops' labels with every tooth set
+        to 0 (grouping_network_module.py:26-28, 79-82)."""
         feats = inputs[0]
         labels = inputs[1] if len(inputs) >= 2 else None
         B = feats.shape[0]
         unlabelled = labels is None and centroids is None
-        if unlabelled and B > 1:
+        contrast = bool(contrast) and labels is not None and not test
+        if contrast:
+            half_seg_label = torch.where(labels >= 9, labels - 8, labels)
+            cbl_loss_1, sem_1, offset_1, mask_1, first_features = self.first_ins_cent_model([feats, half_seg_label], contrast=True)
+        elif unlabelled and B > 1:
             sem_1, offset_1, mask_1, first_features = self.first_ins_cent_model([feats], all_offsets=True)
         else:
             sem_1, offset_1, mask_1, first_features = self.first_ins_cent_model([feats])
         out = {"sem_1": sem_1, "offset_1": offset_1, "mask_1": mask_1, "first_features": first_features}
+        if contrast:
+            out["cbl_loss_1"], out["cbl_counts_1"] = cbl_loss_1, self.first_ins_cent_model.cbl_counts
         if unlabelled:
             centroids = [self._cluster_centroids(feats[b], sem_1[b], offset_1[b]) for b in range(B)]
         # labels: up to crops.MAX_CLUSTERS of them, not the 16 of a ground-truth jaw -- tgnet's boundary pass hands in cluster numbers
         cr = _crops.tooth_crops(feats, labels, centroids, self.crop_sample_size, num_labels=_crops.MAX_CLUSTERS)
         if labels is not None:
             out["cluster_gt_seg_label"] = cr.cluster_gt_seg_label
-        sem_2, offset_2, mask_2, _ = self.second_ins_cent_model([cr.cropped])
+        if contrast:
+            crop_labels = cr.cluster_gt_seg_label
+            crop_labels = torch.where(crop_labels >= 0, torch.zeros_like(crop_labels), crop_labels)
+            out["cbl_loss_2"], sem_2, offset_2, mask_2, _ = self.second_ins_cent_model([cr.cropped, crop_labels], contrast=True)
+            out["cbl_counts_2"] = self.second_ins_cent_model.cbl_counts
+        else:
+            sem_2, offset_2, mask_2, _ = self.second_ins_cent_model([cr.cropped])
         out.update({"sem_2": sem_2, "offset_2": offset_2, "mask_2": mask_2, "cropped_feature_ls": cr.cropped,
                     "nn_crop_indexes": cr.nn_crop_indexes})
         return out

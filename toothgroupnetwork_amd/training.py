@@ -15,9 +15,11 @@ Where it differs from the reference on purpose:
     the reference calls .item() per term and post-fix: nine synchronisations for a three-term step, where this has one.
   * no wandb: the trainer writes one JSON line per scheduler step and per epoch to a stream of the caller's;
     torch.cuda.empty_cache() per step is not mirrored; Trainer.run takes the number of epochs.
-  * tgnet_fps trains on its five geometric and class terms only.  The contrastive-boundary terms (cbl_loss_1 / cbl_loss_2) do not
-    exist in this package, so a configuration with a non-zero weight for either is refused, and so is tgnet_bdl, which needs them
-    and the boundary-sampled training inputs.  Nothing here trains silently on another objective than the configuration names.
+  * tgnet_fps trains on its five geometric and class terms and, with tr_set["contrastive_boundary"] true, on the contrastive-boundary
+    terms cbl_loss_1 / cbl_loss_2 (losses.contrast_boundary_loss) with the configuration's weights.  Without that key a non-zero
+    weight for either is refused, and so is tgnet_bdl, which needs them together with the boundary-sampled training inputs.  Nothing
+    here trains silently on another objective than the configuration names.  The criterion runs in the train phase only; the
+    reference computes it in validation too and throws the value away.
   * tsegnet: a batch for which no tooth centre survives the join (early in a run, nets.TSegNetModule.forward(on_no_centre="skip"))
     contributes its three centroid terms only and is counted in `skipped_segmentation`; the reference would fail there.
   * the cosine schedule is what build_scheduler_from_cfg really builds from a dict: every `getattr(args, ..., default)` of
@@ -332,24 +334,46 @@ class TransformerModel(_ClassModel):
 
 
 class FpsGroupingNetworkModel(TrainingModel):
-    """models/fps_grouping_network_model.py ("tgnet_fps") without the contrastive-boundary terms: the five terms of
-    losses.grouping_loss_terms with the configuration's weights.  A non-zero cbl_loss_1 / cbl_loss_2 weight is refused."""
+    """models/fps_grouping_network_model.py ("tgnet_fps"): the five terms of losses.grouping_loss_terms with the configuration's
+    weights and, opt-in, the contrastive-boundary terms.  tr_set["contrastive_boundary"] true and a non-zero cbl_loss_1 / cbl_loss_2
+    weight: the train-phase forward runs the module with contrast=True and the train-phase LossMap gains cbl_loss_1 and cbl_loss_2,
+    output[...].sum() with the configuration's weights (fps_grouping_network_model.py:58-59).  Without the key a non-zero weight is
+    refused; with the key and both weights zero or absent the criterion is not computed at all."""
     module_class = nets.GroupingNetworkModule
     TERMS = ("tooth_class_loss_1", "tooth_class_loss_2", "offset_1_loss", "offset_1_dir_loss", "chamf_1_loss")
     CBL = ("cbl_loss_1", "cbl_loss_2")
 
     @classmethod
+    def cbl_asked(cls, config):
+        return [n for n in cls.CBL if config["tr_set"]["loss"].get(n, 0) != 0]
+
+    @classmethod
     def check_config(cls, config):
         super().check_config(config)
-        asked = [n for n in cls.CBL if config["tr_set"]["loss"].get(n, 0) != 0]
-        if asked:
-            raise NotImplementedError(f"tgnet_fps: the configuration weights {' and '.join(asked)}, but the contrastive-boundary terms are not "
-                                      "built in this package; set tr_set.loss.cbl_loss_1 and cbl_loss_2 to 0 (or leave them out) to train "
-                                      "on the five class, offset, direction and chamfer terms alone")
+        asked = cls.cbl_asked(config)
+        if asked and not config["tr_set"].get("contrastive_boundary"):
+            raise NotImplementedError(f"tgnet_fps: the configuration weights {' and '.join(asked)}, and the contrastive-boundary terms are "
+                                      "opt-in: set tr_set.contrastive_boundary to True to train on them, or set tr_set.loss.cbl_loss_1 and "
+                                      "cbl_loss_2 to 0 (or leave them out) to train on the five class, offset, direction and chamfer "
+                                      "terms alone")
+
+    def __init__(self, config, module=None):
+        super().__init__(config, module)
+        self.contrast = bool(config["tr_set"].get("contrastive_boundary")) and bool(self.cbl_asked(config))
+
+    def forward(self, inputs):
+        # self.module.training is the phase (TrainingModel._set_model): the criterion is part of the train phase only
+        if self.contrast and self.module.training:
+            return self.module(inputs, contrast=True)
+        return self.module(inputs)
 
     def get_loss(self, output, gt_seg_label, input_coords):
         terms = losses.grouping_loss_terms(output, gt_seg_label, input_coords)
-        return {name: (terms[name], self.config["tr_set"]["loss"][name]) for name in self.TERMS}
+        out = {name: (terms[name], self.config["tr_set"]["loss"][name]) for name in self.TERMS}
+        for name in self.CBL:
+            if name in output:
+                out[name] = (output[name].sum(), self.config["tr_set"]["loss"].get(name, 0))
+        return out
 
     def losses_of(self, output, seg_label, points):
         return self.get_loss(output, seg_label, points[:, :3, :])
