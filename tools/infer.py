@@ -5,6 +5,8 @@
         --save_path test_results --model_name tgnet --checkpoint_path ckpts/tgnet_fps --checkpoint_path_bdl ckpts/tgnet_bdl
     python tools/infer.py ... --gpus 8 --seed 0 --gt_dir ground-truth_labels         (starts its 8 ranks itself, scores the results)
 
+(both checkpoints come out of tools/train.py: --model_name tgnet_fps, then --model_name tgnet_bdl over the first one's file)
+
 The six arguments of the first form are start_inference.py's, with its defaults for all but the input directory ('.h5' is appended
 to both checkpoint paths, as there).  Added: --batch and --workers (inference.infer_paths), --seed (np.random.seed on every rank
 before its scans: tgnet's boundary resampling draws from numpy's global generator, so its labels are a function of the seed, the

@@ -10,7 +10,8 @@ shuffling, augmentation draws, initial weights, tsegnet's 8-of-T crop choice).  
 train_configs/train_config_maker.get_default_config merged with the `config` dict of the Python file at --config_path, so the
 reference's own train_configs/*.py files work as they are.  tr_set.contrastive_boundary defaults to True here, so tgnet_fps trains
 on the cbl_loss_1 / cbl_loss_2 weights its file names (losses.contrast_boundary_loss); --no_contrastive_boundary leaves the key
-out, and a non-zero cbl weight is then refused (training.py).
+out, and a non-zero cbl weight is then refused (training.py).  tgnet_bdl (train_configs/tgnet_bdl.py with its four paths edited)
+trains tgnet's boundary module from a tgnet_fps checkpoint: see training.BoundarySampler for the three directories it needs.
 Prints the trainer's JSON lines: one per scheduler step, one per epoch.  Checkpoints: ckpts/<experiment_name>.h5 after every epoch,
 ckpts/<experiment_name>_val.h5 at every best validation total; both load into inference.make_inference_pipeline."""
 import argparse
@@ -43,7 +44,7 @@ def get_train_config(config_path, experiment_name, input_data_dir_path, train_da
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--model_name", default="tsegnet", help="tsegnet | tgnet_fps | pointnet | pointnetpp | dgcnn | pointtransformer")
+    ap.add_argument("--model_name", default="tsegnet", help="tsegnet | tgnet_fps | tgnet_bdl | pointnet | pointnetpp | dgcnn | pointtransformer")
     ap.add_argument("--config_path", default="train_configs/tsegnet.py", help="train config file: a Python file with a `config` dict")
     ap.add_argument("--experiment_name", default="tsegnet_0620", help="names the checkpoints: ckpts/<experiment_name>.h5")
     ap.add_argument("--input_data_dir_path", default="data_preprocessed_path", help="directory of *_sampled_points.npy")

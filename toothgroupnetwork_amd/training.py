@@ -7,6 +7,7 @@ HIP already; this is the layer above them.
   LossMap                                               loss_meter.py:26-61 (the meter is eval_sharded.LossMeter)
   build_optimizer, build_scheduler, CosineSchedule      BaseModel.__init__ (models/base_model.py:16-28)
   TrainingModel and one step class per model name       BaseModel and models/*_model.py
+  BoundarySampler                                       models/bdl_grouping_netowrk_model.py:20-35, 56-192, over tgnet.py's device functions
   make_training_model                                   start_train.py:22-49
   Trainer                                               trainer.py
 
@@ -17,9 +18,12 @@ Where it differs from the reference on purpose:
     torch.cuda.empty_cache() per step is not mirrored; Trainer.run takes the number of epochs.
   * tgnet_fps trains on its five geometric and class terms and, with tr_set["contrastive_boundary"] true, on the contrastive-boundary
     terms cbl_loss_1 / cbl_loss_2 (losses.contrast_boundary_loss) with the configuration's weights.  Without that key a non-zero
-    weight for either is refused, and so is tgnet_bdl, which needs them together with the boundary-sampled training inputs.  Nothing
-    here trains silently on another objective than the configuration names.  The criterion runs in the train phase only; the
-    reference computes it in validation too and throws the value away.
+    weight for either is refused, for tgnet_bdl too.  Nothing here trains silently on another objective than the configuration names.
+    The criterion runs in the train phase only; the reference computes it in validation too and throws the value away.
+  * tgnet_bdl (BoundarySampler, BdlGroupingNetworkModel): the frozen first module runs in eval mode, so it is a function of its
+    checkpoint (the reference leaves it in train mode and its BatchNorm statistics drift); the k-means behind the boundary flags draws
+    nothing from numpy's generator; the cache file is written under a temporary name and renamed; a duplicate or missing base name, a
+    scan without foreground and one with too few non-boundary rows raise naming the scan.  BoundarySampler's docstring has the list.
   * tsegnet: a batch for which no tooth centre survives the join (early in a run, nets.TSegNetModule.forward(on_no_centre="skip"))
     contributes its three centroid terms only and is counted in `skipped_segmentation`; the reference would fail there.
   * the cosine schedule is what build_scheduler_from_cfg really builds from a dict: every `getattr(args, ..., default)` of
@@ -36,7 +40,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from . import augment, eval_sharded, losses, nets
+from . import augment, eval_sharded, losses, nets, preprocess, tgnet
 from .eval_sharded import LossMeter  # noqa: F401
 
 MODEL_NAMES = ("tgnet_fps", "tsegnet", "dgcnn", "pointnet", "pointnetpp", "pointtransformer", "tgnet_bdl")
@@ -340,6 +344,7 @@ class FpsGroupingNetworkModel(TrainingModel):
     output[...].sum() with the configuration's weights (fps_grouping_network_model.py:58-59).  Without the key a non-zero weight is
     refused; with the key and both weights zero or absent the criterion is not computed at all."""
     module_class = nets.GroupingNetworkModule
+    model_name = "tgnet_fps"
     TERMS = ("tooth_class_loss_1", "tooth_class_loss_2", "offset_1_loss", "offset_1_dir_loss", "chamf_1_loss")
     CBL = ("cbl_loss_1", "cbl_loss_2")
 
@@ -352,7 +357,7 @@ class FpsGroupingNetworkModel(TrainingModel):
         super().check_config(config)
         asked = cls.cbl_asked(config)
         if asked and not config["tr_set"].get("contrastive_boundary"):
-            raise NotImplementedError(f"tgnet_fps: the configuration weights {' and '.join(asked)}, and the contrastive-boundary terms are "
+            raise NotImplementedError(f"{cls.model_name}: the configuration weights {' and '.join(asked)}, and the contrastive-boundary terms are "
                                       "opt-in: set tr_set.contrastive_boundary to True to train on them, or set tr_set.loss.cbl_loss_1 and "
                                       "cbl_loss_2 to 0 (or leave them out) to train on the five class, offset, direction and chamfer "
                                       "terms alone")
@@ -408,15 +413,184 @@ class TSegNetModel(TrainingModel):
         return self.get_loss(output, {"seg_label": seg_label})
 
 
+def _path_map(root, extension):
+    """{base name: path} of the `*<extension>` files in every sub-directory of root, at any depth (bdl_grouping_netowrk_model.py:20-32).
+    Files lying directly in root are not looked at (`os.walk(...)[1:]`), nor are hidden files (glob's `*`); the key is
+    basename.split(".")[0].  Directories and files are visited in sorted order, and a base name found twice is a ValueError naming both
+    paths: the reference keeps whichever os.walk yields last, which depends on the file system."""
+    found = {}
+    for dir_path, dir_names, file_names in os.walk(root):
+        dir_names.sort()
+        if dir_path == root:
+            continue
+        for name in sorted(file_names):
+            if not name.endswith(extension) or name.startswith("."):
+                continue
+            key, path = name.split(".")[0], os.path.join(dir_path, name)
+            if key in found:
+                raise ValueError(f"two {extension} files are named {key!r} under {root}: {found[key]} and {path}")
+            found[key] = path
+    return found
+
+
+class BoundarySampler:
+    """The boundary-sampled inputs of tgnet's second module (bdl_grouping_netowrk_model.py:20-35, 56-192): per scan, num_of_all_points
+    rows of the ORIGINAL mesh, up to num_of_bdl_points of them from where the frozen first module's instances meet, the rest by FPS.
+
+    config: the reference's tgnet_bdl configuration; its boundary_sampling_info names the directories of the original `.obj` and
+    `.json` files (keys "orginal_data_obj_path" / "orginal_data_json_path", the reference's spelling), the cache directory and the
+    three numbers.  base_model: any callable with GroupingNetworkModule's call and output dict.  Constructing needs no GPU; a cache
+    miss does (the base model, tgnet.second_instances, tgnet.boundary_resample: all device functions of the inference pipeline).
+
+    Deliberate deviations from the reference:
+      * k-means seeding.  The reference seeds sklearn's k-means++ from numpy's global generator BEFORE it draws the boundary
+        permutation; this package's k-means draws nothing (tgnet.py).  After the same np.random.seed the two therefore permute from
+        different generator states: the flags are the same, the selected boundary rows are not unless the generator is seeded again
+        behind the reference's k-means.
+      * float32 output.  Both paths return float32 rows; the reference's cache-miss path returns whatever its augmentation produced.
+        The cache-hit path augments the float64 copy of the cached columns and rounds once, as the reference does.
+      * too few non-boundary rows: tgnet.boundary_resample's ValueError, with the base name in front (the reference raises a string).
+      * no foreground point: tgnet.second_instances' ValueError, with the base name in front (sklearn's escapes the reference's step).
+      * a base name found twice under a root is a ValueError, one missing from a root a KeyError naming it and the root.
+      * the cache file is written under a temporary name and renamed, so a killed run leaves no truncated file for the next to trust.
+      * a scan is never silently replaced by other inputs: apart from the reference's own rule for a mesh below num_of_all_points
+        (the batch is returned as it came), every failure raises."""
+
+    def __init__(self, config, base_model):
+        self.config, self.base_model = config, base_model
+        self.info = config["boundary_sampling_info"]
+        self.obj_root, self.json_root = self.info["orginal_data_obj_path"], self.info["orginal_data_json_path"]
+        self.stl_path_map = _path_map(self.obj_root, ".obj")
+        self.json_path_map = _path_map(self.json_root, ".json")
+
+    def load_mesh(self, base_name):
+        """-> (vertices (n, 6) float32: centred, normalised xyz and the vertex normals; labels (n, 1) int: -1 gingiva, teeth 0..15)
+        of the original mesh (:116-131)."""
+        for found, root, what in ((self.json_path_map, self.json_root, ".json"), (self.stl_path_map, self.obj_root, ".obj")):
+            if base_name not in found:
+                raise KeyError(f"no {base_name}{what} in a sub-directory of {root}")
+        with open(self.json_path_map[base_name], "r") as f:
+            loaded = json.load(f)
+        labels = preprocess.remap_fdi_labels(loaded["labels"], loaded["jaw"]) - 1
+        vertices = preprocess.normalise_vertices(preprocess.read_txt_obj_ls(self.stl_path_map[base_name])[0]).astype(np.float32)
+        if labels.shape[0] != vertices.shape[0]:
+            raise ValueError(f"{base_name}: {labels.shape[0]} labels for {vertices.shape[0]} vertices")
+        return vertices, labels.astype(int).reshape(-1, 1)
+
+    @staticmethod
+    def base_name_of(mesh_path):
+        pieces = os.path.basename(mesh_path).split("_")
+        if len(pieces) < 2:
+            raise ValueError(f"mesh_path {mesh_path!r}: the file name must start with <patient>_<jaw>_")
+        return pieces[0] + "_" + pieces[1]
+
+    @staticmethod
+    def write_cache(cache_path, array):
+        """np.save under a temporary name in cache_path's directory, then os.replace: cache_path either holds a whole array or does
+        not exist."""
+        folder = os.path.dirname(cache_path)
+        if folder:
+            os.makedirs(folder, exist_ok=True)
+        tmp_path = f"{cache_path}.{os.getpid()}.tmp"
+        try:
+            with open(tmp_path, "wb") as f:
+                np.save(f, array)
+            os.replace(tmp_path, cache_path)
+        except BaseException:
+            if os.path.exists(tmp_path):
+                os.remove(tmp_path)
+            raise
+
+    @staticmethod
+    def _as_batch(rows, labels):
+        return (torch.from_numpy(np.ascontiguousarray(rows.T)[None]),
+                torch.from_numpy(np.ascontiguousarray(labels.astype(np.int64).reshape(-1, 1).T)[None]))
+
+    def sample(self, batch_item):
+        """batch_item: one collated scan (feat (1, 6, N), gt_seg_label (1, 1, N), aug_obj [Augmentator or None], mesh_path [path]) ->
+        (feat (1, 6, num_of_all_points) float32, gt_seg_label (1, 1, num_of_all_points) int64), CPU tensors (:133-192); boundary rows
+        first.  The first call for a scan runs the base model and writes <bdl_cache_path>/<base name>.npy, the un-augmented selection
+        and its labels as (num_of_all_points, 7) float64 (the reference's file); later calls augment that file's rows."""
+        feat, gt_seg_label = batch_item["feat"], batch_item["gt_seg_label"]
+        if len(batch_item["mesh_path"]) != 1 or feat.shape[0] != 1 or gt_seg_label.shape[0] != 1:
+            raise ValueError(f"the boundary sampler takes one scan per batch, got {len(batch_item['mesh_path'])} paths and feat "
+                             f"{tuple(feat.shape)}: set train_batch_size and val_batch_size to 1")
+        base_name = self.base_name_of(batch_item["mesh_path"][0])
+        aug_obj = batch_item["aug_obj"][0]
+        n_all = int(self.info["num_of_all_points"])
+        cache_path = os.path.join(self.info["bdl_cache_path"], base_name + ".npy")
+        if os.path.exists(cache_path):
+            cached = np.load(cache_path)
+            if cached.ndim != 2 or cached.shape[1] != 7:
+                raise ValueError(f"{cache_path}: a cache file is (num_of_all_points, 7), got {cached.shape}")
+            rows = cached[:, :6].copy()
+            if aug_obj:
+                rows = aug_obj.run(rows)
+            return self._as_batch(rows.astype(np.float32), cached[:, 6])
+        mesh, mesh_labels = self.load_mesh(base_name)
+        if mesh.shape[0] < n_all:
+            return feat, gt_seg_label
+        device = torch.device("cuda")
+        points, seg_label = feat.to(device), gt_seg_label.to(device)
+        with torch.no_grad():
+            output = self.base_model([points, seg_label])
+        augmented = aug_obj.run(mesh.copy()) if aug_obj else mesh.copy()
+        try:
+            point_labels = tgnet.second_instances(points, seg_label, output)["ins"] - 1          # -1 background, clusters 0, 1, ...
+            picked = tgnet.boundary_resample(augmented, points[0, :3].t().contiguous(), point_labels, info=self.info,
+                                             carry=(mesh_labels, mesh))
+        except ValueError as error:
+            raise ValueError(f"{base_name}: {error}") from error
+        rows, (labels, plain_rows) = picked[0], picked[4]
+        self.write_cache(cache_path, np.concatenate([plain_rows, labels], axis=1).astype(np.float64))
+        return self._as_batch(rows.astype(np.float32), labels)
+
+
+class BdlGroupingNetworkModel(FpsGroupingNetworkModel):
+    """models/bdl_grouping_netowrk_model.py ("tgnet_bdl"): the two-stage GroupingNetworkModule of config["model_parameter"], trained on
+    BoundarySampler's inputs.  step() replaces the batch's feat / gt_seg_label with self.sampler.sample(batch_item) in every phase, then
+    runs tgnet_fps's step: the five terms, and cbl_loss_1 / cbl_loss_2 in the train phase under the same tr_set.contrastive_boundary rule.
+
+    The base model -- base_model, or nets.GroupingNetworkModule(config["fps_model_info"]) loaded from
+    fps_model_info.load_ckpt_path + ".h5" with strict=True -- is frozen: eval mode, requires_grad False, in neither the optimiser nor
+    save().  The reference never calls .eval() on it, so its BatchNorm normalises with batch statistics and its running statistics
+    drift during the second training; here a frozen first module is a function of its checkpoint."""
+    model_name = "tgnet_bdl"
+    SECTIONS = ("boundary_sampling_info", "fps_model_info")
+
+    @classmethod
+    def check_config(cls, config):
+        missing = [section for section in cls.SECTIONS if section not in config]
+        if missing:
+            raise NotImplementedError(f"tgnet_bdl trains on boundary-sampled inputs and the configuration has no {' and no '.join(missing)} "
+                                      "section: boundary_sampling_info names the original meshes, their labels and the cache directory, "
+                                      "fps_model_info the trained tgnet_fps module that finds the boundaries (train_configs/tgnet_bdl.py)")
+        super().check_config(config)
+
+    def __init__(self, config, module=None, base_model=None):
+        super().__init__(config, module)
+        if base_model is None:
+            base_model = nets.GroupingNetworkModule(config["fps_model_info"])
+            base_model.load_state_dict(torch.load(config["fps_model_info"]["load_ckpt_path"] + ".h5"), strict=True)
+            base_model.cuda()
+        if isinstance(base_model, torch.nn.Module):
+            base_model.eval()
+            base_model.requires_grad_(False)
+        self.base_model = base_model
+        self.sampler = BoundarySampler(config, base_model)
+
+    def step(self, batch_idx, batch_item, phase):
+        feat, gt_seg_label = self.sampler.sample(batch_item)
+        return super().step(batch_idx, dict(batch_item, feat=feat, gt_seg_label=gt_seg_label), phase)
+
+
 _MODELS = {"tgnet_fps": FpsGroupingNetworkModel, "tsegnet": TSegNetModel, "dgcnn": DGCnnModel, "pointnet": PointFirstModel,
-           "pointnetpp": PointPpFirstModel, "pointtransformer": TransformerModel}
+           "pointnetpp": PointPpFirstModel, "pointtransformer": TransformerModel, "tgnet_bdl": BdlGroupingNetworkModel}
 
 
 def make_training_model(model_name, config):
-    """start_train.py:22-49: the step object of a model name.  tgnet_bdl is refused (NotImplementedError), another name is ValueError."""
-    if model_name == "tgnet_bdl":
-        raise NotImplementedError("tgnet_bdl is not built: its step needs the boundary-sampled training inputs and the contrastive-boundary "
-                                  "terms, neither of which exists in this package; tgnet_fps trains with zero cbl weights")
+    """start_train.py:22-49: the step object of a model name.  Another name is ValueError; tgnet_bdl without its boundary_sampling_info
+    and fps_model_info sections is refused (NotImplementedError) before anything else in the configuration is looked at."""
     if model_name not in _MODELS:
         raise ValueError(f"undefined model {model_name!r}: the names are {', '.join(MODEL_NAMES)}")
     return _MODELS[model_name](config)
