@@ -108,11 +108,15 @@ def test_tgnet_real_modules_equal_the_sequential_loop(dev, objs):
     assert (got[0]["sem"] > 0).any()
 
 
-def test_a_semantic_pipeline_goes_to_infer_scans(dev, objs):
+def test_a_semantic_pipeline_equals_the_single_scan_pipeline(dev, objs):
+    """two scans per network call, a ragged last call: `fixed_model` is exactly rounded, so the labels are the single-scan call's"""
     from toothgroupnetwork_amd import inference
+    pipe = inference.InferencePipeLine(fixed_model)
     paths = [objs["seg_small"], objs["seg_big"], objs["main"]]
-    want = inference.infer_scans(paths, fixed_model, batch=2, workers=2)
-    _same(inference.infer_paths(inference.InferencePipeLine(fixed_model), paths, batch=2, workers=2), want)
+    want = [pipe(p) for p in paths]
+    stats = {}
+    _same(inference.infer_paths(pipe, paths, batch=2, workers=2, stats=stats), want)
+    assert {"load", "sample", "compute", "finish", "model"} <= set(stats)
 
 
 def test_a_mesh_one_pass_cannot_lift_fails_alone(dev, objs):
@@ -124,8 +128,10 @@ def test_a_mesh_one_pass_cannot_lift_fails_alone(dev, objs):
     got = inference.infer_paths(pipe, paths, batch=2, workers=2, staged=True, on_error="skip")
     assert set(got[1]) == {"error"} and "NotImplementedError" in got[1]["error"] and objs["too_small"] in got[1]["error"]
     _same([got[0], got[2]], [pipe(paths[0]), pipe(paths[2])])
-    semantic = inference.infer_paths(inference.InferencePipeLine(fixed_model), paths, batch=2, workers=2, on_error="skip")
-    assert set(semantic[1]) == {"error"} and set(semantic[0]) == set(semantic[2]) == {"sem", "ins"}
+    one = inference.InferencePipeLine(fixed_model)
+    semantic = inference.infer_paths(one, paths, batch=2, workers=2, on_error="skip")
+    assert set(semantic[1]) == {"error"} and "NotImplementedError" in semantic[1]["error"] and objs["too_small"] in semantic[1]["error"]
+    _same([semantic[0], semantic[2]], [one(paths[0]), one(paths[2])])
     # the pools left no stream mid-flight: the device answers, and the next run is right
     torch.cuda.synchronize()
     _same(inference.infer_paths(pipe, paths[:1], batch=2, workers=2, staged=True), [got[0]])

@@ -104,10 +104,12 @@ def test_shards_are_disjoint_and_cover_the_list(n, world):
 class Fakes:
     """Plain functions as the five stages; they record the thread and the order of every call."""
 
-    def __init__(self, n, fail=None, delay=0.0):
+    def __init__(self, n, fail=None, delay=0.0, short=None):
         self.paths = [f"scan{i:02d}" for i in range(n)]
         self.fail, self.delay = fail or {}, delay                 # {stage: index that raises there}
+        self.short = short                                        # the compute call that holds this scan answers one entry too few
         self.calls = {k: [] for k in ("load", "prepare", "sample", "compute", "finish")}
+        self.groups = []                                          # the scans of every compute call
         self.lock = threading.Lock()
 
     def _note(self, stage, what):
@@ -136,11 +138,14 @@ class Fakes:
             self._maybe_fail("sample", p // 10)
         return [p + 1 for p in prepared]
 
-    def compute(self, i, prepared, sampled):
-        assert prepared == i * 10 and sampled == i * 10 + 1
-        self._note("compute", i)
-        self._maybe_fail("compute", i)
-        return -i
+    def compute(self, scans, prepared, sampled):
+        assert prepared == [i * 10 for i in scans] and sampled == [i * 10 + 1 for i in scans]
+        self.groups.append(list(scans))
+        for i in scans:
+            self._note("compute", i)
+        for i in scans:
+            self._maybe_fail("compute", i)
+        return [-i for i in scans][:len(scans) - (self.short in scans)]
 
     def finish(self, i, sampled, computed):
         assert computed == -i
@@ -205,6 +210,49 @@ def test_engine_skip_records_the_error_and_completes_the_rest(stage):
     for i, g in enumerate(got):
         if i in lost:
             assert set(g) == {"error"} and f"scan{i:02d}" in g["error"] and f"scripted failure in {stage}" in g["error"]
+        else:
+            assert g == {"scan": i}
+    assert _pool_threads() == []
+
+
+def test_engine_computes_groups_of_a_chunks_scans_in_path_order():
+    f = Fakes(11, delay=0.001)
+    got = f.run(batch=2, workers=3, group=2)
+    assert got == [{"scan": i} for i in range(11)]
+    assert f.groups == [[0, 1], [2, 3], [4, 5], [6, 7], [8, 9], [10]]        # chunks [0, 1] [2..9] [10]: a group never spans two
+    assert {name for name, _ in f.calls["compute"]} == {threading.current_thread().name}
+    assert _pool_threads() == []
+
+
+def test_engine_groups_close_the_gap_a_failed_scan_leaves():
+    f = Fakes(11, fail={"prepare": 3})
+    got = f.run(batch=2, workers=3, group=2, on_error="skip")
+    assert f.groups == [[0, 1], [2, 4], [5, 6], [7, 8], [9], [10]]
+    assert set(got[3]) == {"error"} and "scan03: scripted failure in prepare" in got[3]["error"]
+    assert [g for i, g in enumerate(got) if i != 3] == [{"scan": i} for i in range(11) if i != 3]
+    assert _pool_threads() == []
+
+
+def test_engine_a_failing_compute_call_fails_its_group_and_no_other():
+    f = Fakes(11, fail={"compute": 5})
+    got = f.run(batch=2, workers=3, group=2, on_error="skip")
+    for i, g in enumerate(got):
+        if i in (4, 5):
+            assert set(g) == {"error"} and f"scan{i:02d}: scripted failure in compute" in g["error"] and "NotImplementedError" in g["error"]
+        else:
+            assert g == {"scan": i}
+    assert _pool_threads() == []
+    with pytest.raises(NotImplementedError, match="scan04: scripted failure in compute"):    # the group's first scan in path order
+        Fakes(11, fail={"compute": 5}).run(batch=2, workers=3, group=2)
+    assert _pool_threads() == []
+
+
+def test_engine_a_compute_call_that_answers_too_few_fails_its_group():
+    f = Fakes(11, short=7)
+    got = f.run(batch=2, workers=3, group=2, on_error="skip")
+    for i, g in enumerate(got):
+        if i in (6, 7):
+            assert set(g) == {"error"} and f"RuntimeError: scan{i:02d}: the compute stage returned 1 entries for 2 scans" in g["error"]
         else:
             assert g == {"scan": i}
     assert _pool_threads() == []

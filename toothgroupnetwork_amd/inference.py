@@ -13,7 +13,7 @@ Pinned against the reference's own class executed on CPU (tests/golden/make_gold
 everything else the reference's code): the same label on every vertex.
 Meshes with fewer than 24 000 vertices are subdivided once at their edge midpoints first, as the reference does with open3d's
 subdivide_midpoint(number_of_iterations=1) (:25-26): on the GPU (preprocess.subdivide_midpoint, csrc/subdivide.hip), inside the "sample"
-stage, and the subdivided vertices with their interpolated normals are what is sampled (`points_to_sample`).  One iteration is all the
+stage, and the subdivided vertices with their interpolated normals are what is sampled (`dense_rows`).  One iteration is all the
 pipelines use.  Parity with open3d is unpinned: the vertex order is restated from open3d's source, and neither open3d nor trimesh is
 available where the fixtures are made.  A mesh that still has no more than 24 000 points after the pass is NotImplementedError: the
 reference fails on it too (gen_utils.py:136-137).
@@ -26,8 +26,9 @@ resampling between them (tgnet.py), pinned in the same way (tests/golden/make_go
 reference's factory (inference_pipelines/inference_pipeline_maker.py) with its six model names.
 
 Each of the three classes states its stages once, as methods (_StagedPipeLine), and `__call__` composes them.  infer_paths runs many scans
-through any of them: the semantic pipelines through infer_scans, the two-stage ones through run_staged, an engine that puts the same
-stage methods on loader, sampler and finisher threads around the calling thread (measured: profiles/r18_inference.txt)."""
+through any of them on one engine, run_staged, which puts the same stage methods on loader, sampler and finisher threads around the
+calling thread: the semantic pipelines with `batch` scans per network call, the two-stage ones with one (measured:
+profiles/r18_inference.txt, profiles/inference_one_engine_before_after.txt)."""
 import time
 
 import numpy as np
@@ -71,14 +72,6 @@ def subdivided_rows(org_feats, triangles):
     return np.concatenate([sub["vertices"], sub["vertex_normals"]], axis=1)
 
 
-def points_to_sample(org_feats, triangles):
-    """The rows the pipelines sample 24 000 points from: the mesh's own (org_feats, which stays what the labels are transferred back
-    onto) or, below 24 000 vertices, the subdivided mesh's."""
-    if needs_subdivision(org_feats.shape[0], int(np.asarray(triangles).shape[0])):
-        return subdivided_rows(org_feats, triangles)
-    return org_feats
-
-
 def fdi_from_classes(cls):
     """classes 0..16 -> FDI-style numbers as the pipeline writes them (:32-34): 1..8 -> 11..18, 9..16 -> 21..28."""
     cls = np.array(cls, dtype=np.int64)
@@ -88,14 +81,24 @@ def fdi_from_classes(cls):
 
 
 class _Laps:
-    """Durations between marks: compute() of a pipeline marks the end of each of its parts."""
+    """Durations between marks: compute() of a pipeline marks the end of each of its parts; a part marked again adds up."""
 
     def __init__(self):
         self.durations, self.last = {}, time.perf_counter()
 
+    @classmethod
+    def given(cls, laps):
+        """the caller's laps, or fresh ones for a caller that wants none"""
+        return cls() if laps is None else laps
+
     def mark(self, name):
         now = time.perf_counter()
-        self.durations[name], self.last = now - self.last, now
+        self.durations[name], self.last = self.durations.get(name, 0.0) + now - self.last, now
+
+
+def network_input(*rows):
+    """(n, c) host rows of one scan each -> the networks' input: (scans, c, n) float32 on the GPU, contiguous"""
+    return torch.from_numpy(np.stack([np.asarray(r, dtype=np.float32) for r in rows])).cuda().permute(0, 2, 1).contiguous()
 
 
 class _StagedPipeLine:
@@ -106,8 +109,9 @@ class _StagedPipeLine:
       take_sample(dense, idx)          the 24 000 sampled rows, given the FPS indices of the dense rows
       compute(scan, dense, sampled)    the networks and what joins them -> what finish needs; the durations of its parts go into `laps`
       finish(scan, sampled, computed)  the label transfer onto every vertex (GPU), the FDI relabelling -> {"sem", "ins"}
-    infer_paths runs the same methods over many scans, each stage on threads of its own.  No method keeps anything about a scan on
-    the pipeline object besides `times`, which only `__call__` writes."""
+    infer_paths runs the same methods over many scans, each stage on threads of its own, and computes through compute_many: the same
+    stage for a list of scans, which a pipeline whose network takes several scans per call overrides.  No method keeps anything
+    about a scan on the pipeline object besides `times`, which only `__call__` writes."""
 
     FPS_PREFIX = True       # leave the FPS-of-an-FPS-result certificate for the network's first level (resample.fps)
 
@@ -127,6 +131,9 @@ class _StagedPipeLine:
 
     def take_sample(self, dense, idx):
         return dense[idx[:N_POINTS]]
+
+    def compute_many(self, scans, dense, sampled, laps=None):
+        return [self.compute(*one, laps) for one in zip(scans, dense, sampled)]
 
     def __call__(self, stl_path):
         t = [time.perf_counter()]
@@ -156,15 +163,18 @@ class InferencePipeLine(_StagedPipeLine):
         self.shifter = 0.8
         self.times = {}
 
-    def compute(self, scan, dense, sampled_feats, laps=None):
-        laps = _Laps() if laps is None else laps
+    def compute_many(self, scans, dense, sampled, laps=None):
+        """ONE network call on (scans, 6, 24000) -> the (24000,) classes of every scan; `model` has to be batch-capable for more than one"""
+        laps = _Laps.given(laps)
         with torch.no_grad():
-            inp = torch.from_numpy(np.ascontiguousarray(sampled_feats.astype("float32"))[None]).cuda().permute(0, 2, 1)
-            out = self.model([inp])
+            out = self.model([network_input(*sampled)])
             cls_pred = out["cls_pred"] if isinstance(out, dict) else out[0]
-            cls_pred = cls_pred.argmax(dim=1).reshape(-1).cpu().numpy()
+            cls_pred = cls_pred.argmax(dim=1).cpu().numpy()
         laps.mark("model")
-        return cls_pred
+        return list(cls_pred)
+
+    def compute(self, scan, dense, sampled_feats, laps=None):
+        return self.compute_many([scan], [dense], [sampled_feats], laps)[0]
 
     def finish(self, scan, sampled_feats, cls_pred):
         labels = fdi_from_classes(cls_pred)
@@ -190,9 +200,9 @@ class TSegNetInferencePipeLine(_StagedPipeLine):
         self.times = {}
 
     def compute(self, scan, dense, sampled_feats, laps=None):
-        laps = _Laps() if laps is None else laps
+        laps = _Laps.given(laps)
         with torch.no_grad():
-            inp = torch.from_numpy(np.ascontiguousarray(sampled_feats.astype("float32"))[None]).cuda().permute(0, 2, 1).contiguous()
+            inp = network_input(sampled_feats)
             l0_points, _, _, l3_xyz, offset_result, dist_result = self.model.cent_module(inp)
             torch.cuda.current_stream().synchronize()
             laps.mark("centroids")
@@ -228,7 +238,7 @@ class TgnInferencePipeLine(_StagedPipeLine):
     reference's own classes, or stand-ins with the same call and output dict.  Stages, with `times` holding their durations:
       load       the native reader; duplicated vertices collapse to their first occurrence (first_occurrences), as open3d's
                  remove_duplicated_vertices does, a kept vertex keeping its normal and the triangles re-indexed
-      sample     the pipeline's normalisation, one midpoint subdivision below 24 000 vertices (points_to_sample: those rows are then
+      sample     the pipeline's normalisation, one midpoint subdivision below 24 000 vertices (dense_rows: those rows are then
                  also what the boundary pass resamples, :35-39), FPS to 24 000
       first      the first module without labels, tgnet.first_instances
       resample   tgnet.boundary_resample: boundary rows by np.random.permutation of numpy's GLOBAL generator, the rest by FPS
@@ -276,15 +286,15 @@ class TgnInferencePipeLine(_StagedPipeLine):
 
     def compute(self, scan, bdl_feats, sampled_feats, laps=None):
         """(the only stage that draws from numpy's global generator: boundary_resample's permutation)"""
-        laps = _Laps() if laps is None else laps
+        laps = _Laps.given(laps)
         with torch.no_grad():
-            inp = torch.from_numpy(np.ascontiguousarray(sampled_feats.astype("float32"))[None]).cuda().permute(0, 2, 1).contiguous()
+            inp = network_input(sampled_feats)
             first = tgnet.first_instances(inp, self.first_module([inp]))
             first = {k: v.cpu().numpy() for k, v in first.items()}
             laps.mark("first")
             feats, labels, only_bdl, _ = tgnet.boundary_resample(bdl_feats, sampled_feats, first["ins"], self.boundary_sampling_info)
             laps.mark("resample")
-            inp = torch.from_numpy(np.ascontiguousarray(feats.astype("float32"))[None]).cuda().permute(0, 2, 1).contiguous()
+            inp = network_input(feats)
             lab = torch.from_numpy(tgnet.dense_rank_labels(labels)[None, None]).cuda()
             second = tgnet.second_instances(inp, lab, self.bdl_module([inp, lab], test=True))
             nb = only_bdl.shape[0]
@@ -344,76 +354,9 @@ def make_inference_pipeline(model_name, ckpt_path_ls):
 
 
 def infer_scans(paths, model, batch=8, workers=None):
-    """Many scans through the same pipeline, MI355X-shaped: what InferencePipeLine does one scan at a time (58 ms each: 17 ms of
-    parsing, 30 of sampling, 11 of an eager forward) as three overlapped stages -- loader threads (native reader + normals, no
-    interpreter lock), a sampler thread that packs 4 x `batch` scans into ONE FPS launch on its own stream, and the calling thread, which
-    runs the network on (batch, 6, 24000) and hands the label transfer to helper threads.  Same stage functions, same results per scan
-    as InferencePipeLine (tests/test_gpu_whole_nets.py); returns the list of {"sem", "ins"} in the order of `paths`.
-    A mesh below 24 000 vertices is subdivided once in the sampler stage, on that thread's stream (the loaders only decide that it
-    needs it), and joins the same FPS launch (tests/test_gpu_subdivide.py).
-    `model`: as for InferencePipeLine, batch-capable (nets.PointTransformerSeg is)."""
-    import os
-    import threading
-    from collections import deque
-    from concurrent.futures import ThreadPoolExecutor
-    step = max(int(batch), 1)
-    if workers is None:
-        workers = max(1, min(32, (os.cpu_count() or 1)))
-    loaders = ThreadPoolExecutor(max_workers=workers)
-    sampler = ThreadPoolExecutor(max_workers=1)
-    finishers = ThreadPoolExecutor(max_workers=4)
-    local = threading.local()
-
-    def on_own_stream(fn, *a):
-        st = getattr(local, "stream", None)
-        if st is None:
-            st = local.stream = torch.cuda.Stream()
-        with torch.cuda.stream(st):
-            out = fn(*a)
-            st.synchronize()
-        return out
-
-    def load(path):
-        feats, mesh = preprocess.read_txt_obj_ls(path, ret_mesh=True)
-        org = np.concatenate([normalise_for_inference(mesh["vertices"]), mesh["vertex_normals"]], axis=1)
-        if needs_subdivision(org.shape[0], mesh["triangles"].shape[0]):           # (host arithmetic only: the pass itself is the sampler's)
-            return org, None, mesh["triangles"]
-        return org, np.ascontiguousarray(org[:, :3], dtype=np.float32), None
-
-    def sample(loaded):
-        # (sampler thread) small meshes are subdivided here, on this thread's stream, then one FPS launch over the whole chunk
-        dense = [org if tri is None else on_own_stream(subdivided_rows, org, tri) for org, _, tri in loaded]
-        xyz = [x32 if tri is None else np.ascontiguousarray(d[:, :3], dtype=np.float32) for (_, x32, tri), d in zip(loaded, dense)]
-        idx = on_own_stream(resample.fps_batch, xyz, N_POINTS)
-        return [d[ix[:N_POINTS]] for d, ix in zip(dense, idx)]
-
-    def finish(sampled, cls, org):
-        return on_own_stream(preprocess.transfer_labels, sampled[:, :3], fdi_from_classes(cls), org[:, :3]).reshape(-1)
-
-    # an FPS launch costs the same for 1 or 64 scans (one workgroup each): it takes four model batches at a time
-    fstep = 4 * step
-    chunks = [paths[s:s + fstep] for s in range(0, len(paths), fstep)]
-    results, pending = [], deque()
-    try:
-        loads = [[loaders.submit(load, p) for p in chunk] for chunk in chunks]
-        sampled_f = [sampler.submit(lambda fs=fs: (lambda loaded: (loaded, sample(loaded)))([f.result() for f in fs])) for fs in loads]
-        for sf in sampled_f:
-            loaded, sampled = sf.result()
-            for b0 in range(0, len(sampled), step):
-                part = sampled[b0:b0 + step]
-                with torch.no_grad():
-                    inp = torch.from_numpy(np.stack([s_.astype("float32") for s_ in part])).cuda().permute(0, 2, 1).contiguous()
-                    out = model([inp])
-                    cls_pred = (out["cls_pred"] if isinstance(out, dict) else out[0]).argmax(dim=1).cpu().numpy()  # (B, N)
-                for (org, _, _), s_, c in zip(loaded[b0:b0 + step], part, cls_pred):
-                    pending.append(finishers.submit(finish, s_, c, org))
-        for f in pending:
-            r = f.result()
-            results.append({"sem": r, "ins": r})
-    finally:
-        for pool in (loaders, sampler, finishers):
-            pool.shutdown(wait=True, cancel_futures=True)
-    return results
+    """Many scans through the semantic pipeline around `model` (as for InferencePipeLine, batch-capable: nets.PointTransformerSeg is), the
+    network on `batch` scans per call: infer_paths' staged run of an InferencePipeLine, under the name its callers know."""
+    return infer_paths(InferencePipeLine(model), paths, batch, workers)
 
 
 def default_workers():
@@ -443,18 +386,27 @@ def _settle(results, i, path, error, on_error):
     results[i] = {"error": f"{type(named).__name__}: {named}"}
 
 
-def run_staged(paths, load, prepare, sample, compute, finish, batch=8, workers=None, on_error="raise", on_thread=None, stats=None):
+def _one_each(stage, out, n):
+    out = list(out)
+    if len(out) != n:
+        raise RuntimeError(f"the {stage} stage returned {len(out)} entries for {n} scans")
+    return out
+
+
+def run_staged(paths, load, prepare, sample, compute, finish, batch=8, workers=None, on_error="raise", on_thread=None, stats=None, group=1):
     """The engine of a staged run over many scans; the stages are the caller's:
-      load(path) -> loaded                            `workers` loader threads
-      prepare(loaded) -> prepared                     the one sampler thread, scan by scan
-      sample([prepared, ...]) -> [sampled, ...]       the sampler thread, ONE call per chunk of up to 4 x `batch` scans (the first: `batch`)
-      compute(loaded, prepared, sampled) -> computed  the CALLING thread, one scan at a time, in the order of `paths`
-      finish(loaded, sampled, computed) -> result     up to four finisher threads
+      load(path) -> loaded                                    `workers` loader threads
+      prepare(loaded) -> prepared                             the one sampler thread, scan by scan
+      sample([prepared, ...]) -> [sampled, ...]               the sampler thread, ONE call per chunk of up to 4 x `batch` scans (the first: `batch`)
+      compute([loaded, ...], [prepared, ...], [sampled, ...]) the CALLING thread, in the order of `paths`, ONE call per `group` scans: the
+          -> [computed, ...]                                  scans of a chunk that got this far, taken `group` at a time (the last: the rest)
+      finish(loaded, sampled, computed) -> result             up to four finisher threads
     -> the results in the order of `paths`.  on_thread(fn, *args) wraps what the sampler and the finishers run (infer_paths: a stream
     of the thread's own, synchronised before the result is handed on).  At most two chunks are in front of the calling thread, so a
     long list does not fill memory with loaded meshes.  A scan that fails in any stage raises its own exception with the path in
     front of the message (on_error="raise"), or leaves {"error": message} in its slot while the others go on ("skip"); a `sample`
-    call that fails as a whole fails every scan of its chunk.  All pools have ended when this returns or raises.
+    call that fails as a whole fails every scan of its chunk, a `compute` call every scan of its group (raised: the first of them).
+    A chunk's failures before compute are settled before its groups are computed.  All pools have ended when this returns or raises.
     stats: a dict that receives the mean seconds per scan in "load", "sample", "compute", "finish"."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
@@ -464,7 +416,7 @@ def run_staged(paths, load, prepare, sample, compute, finish, batch=8, workers=N
     paths = list(paths)
     # an FPS launch costs the same for 1 or 64 scans (one workgroup each), so a chunk is four batches -- but the first is one batch: the
     # calling thread has nothing to do until the first chunk is loaded and sampled
-    step, n = max(int(batch), 1), len(paths)
+    step, group, n = max(int(batch), 1), max(int(group), 1), len(paths)
     edges = [0] + list(range(min(step, n), n, 4 * step)) + [n]
     chunks = [range(lo, hi) for lo, hi in zip(edges, edges[1:]) if hi > lo]
     results = [None] * len(paths)
@@ -490,9 +442,7 @@ def run_staged(paths, load, prepare, sample, compute, finish, batch=8, workers=N
         sampled = []
         if good:
             try:
-                sampled = list(call(sample, [prepared for _, prepared in good]))
-                if len(sampled) != len(good):
-                    raise RuntimeError(f"the sample stage returned {len(sampled)} entries for {len(good)} scans")
+                sampled = _one_each("sample", call(sample, [prepared for _, prepared in good]), len(good))
             except Exception as e:  # noqa: BLE001
                 sampled = [e] * len(good)
         sampled = iter(sampled)
@@ -526,16 +476,22 @@ def run_staged(paths, load, prepare, sample, compute, finish, batch=8, workers=N
             items = ahead.popleft().result()
             if c + 2 < len(chunks):
                 ahead.append(submit(c + 2))
+            good = []
             for i, item in zip(chunks[c], items):
+                if isinstance(item, Exception):
+                    _settle(results, i, paths[i], item, on_error)
+                else:
+                    good.append((i, *item))
+            for g in range(0, len(good), group):
+                members, loaded, prepared, sampled = map(list, zip(*good[g:g + group]))
                 try:
-                    if isinstance(item, Exception):
-                        raise item
-                    loaded, prepared, sampled = item
-                    computed = timed("compute", compute, loaded, prepared, sampled)
+                    computed = _one_each("compute", timed("compute", compute, loaded, prepared, sampled), len(members))
                 except Exception as e:  # noqa: BLE001
-                    _settle(results, i, paths[i], e, on_error)
+                    for i in members:
+                        _settle(results, i, paths[i], e, on_error)
                     continue
-                pending.append((i, finishers.submit(timed, "finish", call, finish, loaded, sampled, computed)))
+                for i, *one in zip(members, loaded, sampled, computed):
+                    pending.append((i, finishers.submit(timed, "finish", call, finish, *one)))
                 collect(False)
         collect(True)
     finally:
@@ -569,6 +525,8 @@ class _OwnStreams:
 
 def _one_by_one(pipeline, paths, on_error, stats):
     """[pipeline(p) for p in paths] with the staged run's error rules"""
+    if on_error not in ("raise", "skip"):
+        raise ValueError(f"on_error is 'raise' or 'skip', not {on_error!r}")
     results, sums = [None] * len(paths), {}
     for i, path in enumerate(paths):
         try:
@@ -591,10 +549,12 @@ STAGED = {"tsegnet": True, "tgnet": True}
 
 def infer_paths(pipeline, paths, batch=8, workers=None, on_error="raise", stats=None, staged=None):
     """Many scans through any pipeline -> the list of {"sem", "ins"} in the order of `paths`.
-      InferencePipeLine            infer_scans(paths, pipeline.model, batch, workers): the network runs on `batch` scans at a time
-      TSegNetInferencePipeLine,    a staged run (run_staged) of the pipeline's own stage methods: loader threads; a sampler thread that
-      TgnInferencePipeLine         subdivides small meshes and runs ONE resample.fps_batch launch per 4 x `batch` scans; compute on the
-                                   calling thread, ONE SCAN PER NETWORK CALL in the order of `paths`; the transfer on finisher threads
+      the three pipeline classes   a staged run (run_staged) of the pipeline's own stage methods: loader threads; a sampler thread that
+                                   subdivides small meshes and runs ONE resample.fps_batch launch per 4 x `batch` scans; compute_many on
+                                   the calling thread, in the order of `paths`; the transfer on finisher threads
+        InferencePipeLine            the network runs on `batch` scans per call (its compute_many)
+        TSegNetInferencePipeLine,    ONE SCAN PER NETWORK CALL
+        TgnInferencePipeLine
       anything else callable       [pipeline(p) for p in paths]
     The two-stage results equal pipeline(path) by construction, not by tolerance: the networks see the shapes the single-scan call
     gives them (the library GEMMs pick kernels by row count, and the 0.3 filter, the DBSCAN radius and the 0.7 boundary ratio turn
@@ -603,24 +563,17 @@ def infer_paths(pipeline, paths, batch=8, workers=None, on_error="raise", stats=
     certificate only short-cuts an identical result, so no label depends on it, and none left for a later scan can reach an earlier
     scan's network.
     workers: loader threads (default_workers()).  on_error: "raise" -- a failing scan raises its own exception with its path in front
-    of the message; "skip" -- its slot holds {"error": message} and the others are answered (for InferencePipeLine, whose batched run
-    fails as a whole, the scans are then answered one at a time).  stats receives mean seconds per scan and stage.  staged: overrides
-    STAGED for a two-stage pipeline (the measurement's switch)."""
+    of the message; "skip" -- its slot holds {"error": message} and the others are answered (a network call that fails takes the
+    scans of its call with it, no others).  stats receives mean seconds per scan and stage.  staged: overrides STAGED for a
+    two-stage pipeline (the measurement's switch); InferencePipeLine is always staged."""
     paths = list(paths)
-    workers = default_workers() if workers is None else max(int(workers), 1)
-    if on_error not in ("raise", "skip"):
-        raise ValueError(f"on_error is 'raise' or 'skip', not {on_error!r}")
-    if isinstance(pipeline, InferencePipeLine):
-        if on_error == "raise":
-            return infer_scans(paths, pipeline.model, batch, workers)
-        try:
-            return infer_scans(paths, pipeline.model, batch, workers)
-        except Exception:  # noqa: BLE001  (which scan it was is not known: find it)
-            return _one_by_one(pipeline, paths, on_error, stats)
-    two_stage = isinstance(pipeline, (TSegNetInferencePipeLine, TgnInferencePipeLine))
-    if staged is None:
-        staged = two_stage and STAGED["tgnet" if isinstance(pipeline, TgnInferencePipeLine) else "tsegnet"]
-    if not (two_stage and staged):
+    if isinstance(pipeline, TgnInferencePipeLine):
+        staged = STAGED["tgnet"] if staged is None else staged
+    elif isinstance(pipeline, TSegNetInferencePipeLine):
+        staged = STAGED["tsegnet"] if staged is None else staged
+    else:
+        staged = isinstance(pipeline, InferencePipeLine)
+    if not staged:
         return _one_by_one(pipeline, paths, on_error, stats)
     laps_sum = {}
 
@@ -633,15 +586,15 @@ def infer_paths(pipeline, paths, batch=8, workers=None, on_error="raise", stats=
     def sample(dense):
         return [pipeline.take_sample(d, idx) for d, idx in zip(dense, resample.fps_batch(dense, N_POINTS))]
 
-    def compute(scan, dense, sampled):
+    def compute(scans, dense, sampled):
         laps = _Laps()
-        computed = pipeline.compute(scan, dense, sampled, laps)
+        computed = pipeline.compute_many(scans, dense, sampled, laps)
         for k, v in laps.durations.items():
             laps_sum[k] = laps_sum.get(k, 0.0) + v
         return computed
 
-    results = run_staged(paths, pipeline.load, prepare, sample, compute, pipeline.finish, batch=batch, workers=workers,
-                         on_error=on_error, on_thread=_OwnStreams(), stats=stats)
+    results = run_staged(paths, pipeline.load, prepare, sample, compute, pipeline.finish, batch=batch, workers=workers, on_error=on_error,
+                         on_thread=_OwnStreams(), stats=stats, group=batch if isinstance(pipeline, InferencePipeLine) else 1)
     if stats is not None and paths:
         stats.update({k: v / len(paths) for k, v in laps_sum.items()})
     return results
