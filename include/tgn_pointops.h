@@ -579,6 +579,40 @@ int tgn_centroid_loss_backward(int b, int m, int c, const float *offset, const f
                                float *grad_offset, float *grad_distance, tgn_stream_t stream);
 
 /*
+ * One decoder stage of the contrastive-boundary criterion (heads.ContrastHead.point_contrast) as fused kernels (csrc/cbl.hip), for
+ * neighbour lists the caller supplies.  The (m, k1, c) tensor of latent differences is never formed.  f (m, c) float32, 16-byte
+ * aligned; idx (m, k1) int32, the neighbour lists WITHOUT their column 0 (k1 = nsample - 1); labels (m) int64.  Sizes: 1 <= k1 <= 63,
+ * c a multiple of 4 with 4 <= c <= 128, m * k1 < 2^31; anything else is TGN_ERR_UNSUPPORTED naming the value, before the first HIP
+ * call.  m = 0: the forward writes loss = 0 and count = 0, the backward writes nothing.  An index outside [0, m) reads point 0 and
+ * latches bit 0 of the stream's error word, as in the gather family.  The calls launch on `stream` and neither allocate, copy nor
+ * synchronise; no atomics on floats: the same inputs give the same bits.  `workspace` (device memory, at least
+ * tgn_cbl_stage_workspace_bytes(m), which grows by one step per 16 points) is free again when the forward has run.
+ *
+ *   tgn_cbl_stage_forward: for point i and slot j < k1, all in float32 with every operation rounded:
+ *       s_q  = sum over the channels ch = q (mod 4), in channel order, of (f[i][ch] - f[idx[i][j]][ch])^2, from 0        (q = 0..3)
+ *       d_ij = sqrtf(((s_0 + s_1) + (s_2 + s_3)) + 1e-12)                   e_ij = expf(min_j d_ij - d_ij)
+ *       neg_i = sum_j e_ij, pos_i = sum_j e_ij [labels[idx[i][j]] == labels[i]]: butterflies over the 64 lanes of a wave (lane = slot,
+ *               the lanes j >= k1 hold 0), lane distances 32, 16, .., 1
+ *       r_i = pos_i / neg_i; the point contributes when 0 < #{j: labels[idx[i][j]] == labels[i]} < k1, with the value -logf(r_i + 1e-12)
+ *     count (1) int64 = the number of contributing points; loss (1) = 0.1 * (sum of their values) / max(count, 1), the sum in float64
+ *     (a workgroup's 16 points in point order, lane l of the finishing wave the workgroups l, l + 64, .., then a butterfly), rounded
+ *     to float32 once.  pair_w (m, k1) = e_ij ([labels equal] - r_i) / ((neg_i (r_i + 1e-12)) d_ij) for a contributing point, exactly
+ *     0 for every other row: dL_i / dd_ij divided by d_ij.
+ *   tgn_cbl_stage_backward: grad_f (m, c), every row stored exactly once, zeros included:
+ *       grad_f[i] = s (sum_j pair_w[i][j] (f[i] - f[idx[i][j]]) - sum over q in rev(i) of pair_w[q] (f[q / k1] - f[i]))
+ *       s = (grad_loss[0] * 0.1) / max(count, 1) in float32                              (grad_loss: 1 float in DEVICE memory)
+ *     rev(i) = the pair numbers q = i' k1 + j with idx[i'][j] == i, ascending, as rev_pair[rev_start[i] .. rev_start[i + 1]) with
+ *     rev_start (m + 1) and rev_pair (m k1) int32.  Per channel in float32: from 0, the own pairs in slot order (acc = acc + w * diff),
+ *     then the listed pairs in list order (acc = acc - w * diff), then s * acc.  A pair whose pair_w is exactly 0 is skipped, its rows
+ *     unread.  A list entry outside [0, m k1) is skipped and latches the error word.
+ */
+size_t tgn_cbl_stage_workspace_bytes(int m);
+int tgn_cbl_stage_forward(int m, int k1, int c, const float *f, const int *idx, const long long *labels, float *loss, long long *count,
+                          float *pair_w, void *workspace, size_t ws_bytes, tgn_stream_t stream);
+int tgn_cbl_stage_backward(int m, int k1, int c, const float *f, const int *idx, const float *pair_w, const long long *count,
+                           const int *rev_start, const int *rev_pair, const float *grad_loss, float *grad_f, tgn_stream_t stream);
+
+/*
  * DGCNN's neighbourhood work (models/modules/dgcnn.py).  x (B, D, N) float32 channel-first, as the network holds it.
  *   tgn_feature_knn: knn(x, k) (dgcnn.py:4-10) without the N x N matrix.  idx (B, N, k) int64 point indices local to their scan;
  *     row i holds the k smallest distances to point i, i itself included, in ascending (distance, index) order.  The distance is

@@ -8,6 +8,8 @@ respect to the latent features, time and peak memory, against the reference's fo
               Stage i holds every 4th point of stage i-1 of every cloud; the latent features are (m_i, 32) normal draws with
               requires_grad; labels run along the arch (synth.labelled_arch).
   ours        losses.contrast_boundary_loss: integer votes, torch.where, pointops.subtraction for the (m, K-1, 32) differences
+  fused       losses.contrast_boundary_loss(fused=True): the same votes and lists, every stage's distances, soft-NN sums and gradient
+              in the two kernels of csrc/cbl.hip (losses.contrast_boundary_stage_fused), without the (m, K-1, 32) tensor
   reference   the reference's steps over this package's pointops: one-hot targets averaged over the kr nearest stage-0 points, labels
               and features gathered with advanced indexing to (m, K-1, ncls) and (m, K-1, 32), arg-max, boolean-mask indexing of the
               contributing rows (a host synchronisation per stage), the broadcast difference, soft nearest neighbours, mean
@@ -64,6 +66,12 @@ def make_workload(name, dev):
 def ours(points, latents, target, ncls):
     from toothgroupnetwork_amd import losses
     loss, counts = losses.contrast_boundary_loss(points, latents, target, NSAMPLE, STRIDE)
+    return loss, torch.autograd.grad(loss.sum(), latents)
+
+
+def fused(points, latents, target, ncls):
+    from toothgroupnetwork_amd import losses
+    loss, counts = losses.contrast_boundary_loss(points, latents, target, NSAMPLE, STRIDE, fused=True)
     return loss, torch.autograd.grad(loss.sum(), latents)
 
 
@@ -133,7 +141,7 @@ def peak_bytes(fn, args):
 def run(name, steps, warmup, dev):
     args = make_workload(name, dev)
     from toothgroupnetwork_amd import pointops
-    variants = (("ours", ours), ("reference", reference_formulation), ("difference", difference_only), ("knn", knn_only))
+    variants = (("ours", ours), ("fused", fused), ("reference", reference_formulation), ("difference", difference_only), ("knn", knn_only))
     ms = {mode: {tag: [] for tag, _ in variants} for mode in ("cold", "memo")}
     for i in range(warmup + steps):
         for mode in ("cold", "memo"):
@@ -148,12 +156,12 @@ def run(name, steps, warmup, dev):
                 torch.cuda.synchronize()
                 if i >= warmup:
                     ms[mode][tag].append((time.perf_counter() - t0) * 1e3)
-    a, b = ours(*args)[0], reference_formulation(*args)[0]
+    a, b, fu = ours(*args)[0], reference_formulation(*args)[0], fused(*args)[0]
     sizes = [(lat.shape[0], k - 1) for lat, k in zip(args[1], NSAMPLE)]
     diff_bytes = sum(m * k1 * C * 4 for m, k1 in sizes)
     res = {mode: {tag: quartiles(v) for tag, v in by_tag.items()} for mode, by_tag in ms.items()}
     peak = {}
-    for tag, fn in variants[:3]:
+    for tag, fn in variants[:4]:
         pointops.knn_cache_clear()
         peak[tag] = round(peak_bytes(fn, args) / 2 ** 20, 1)
     res["peak_MiB"] = peak
@@ -161,10 +169,13 @@ def run(name, steps, warmup, dev):
     stage_knn = _stage_knn_ms(args, steps)
     diff_cold = res["cold"]["difference"]["median_ms"] - stage_knn
     res.update(stage_points=[m for m, _ in sizes], loss_ours=[round(v, 7) for v in a.tolist()], loss_reference=[round(v, 7) for v in b.tolist()],
+               loss_fused=[round(v, 7) for v in fu.tolist()],
                difference_tensor_MiB=round(diff_bytes / 2 ** 20, 1), stage_list_searches_cold_ms=round(stage_knn, 3), difference_without_its_searches_cold_ms=round(diff_cold, 3),
                difference_share_of_ours_time={"cold": round(diff_cold / res["cold"]["ours"]["median_ms"], 3),
                                               "memo": round(res["memo"]["difference"]["median_ms"] / res["memo"]["ours"]["median_ms"], 3)},
                difference_share_of_ours_peak=round(peak["difference"] / peak["ours"], 3),
+               fused_over_ours_time={mode: round(res[mode]["fused"]["median_ms"] / res[mode]["ours"]["median_ms"], 3) for mode in ("cold", "memo")},
+               fused_over_ours_peak=round(peak["fused"] / peak["ours"], 3),
                speedup_over_reference={mode: round(res[mode]["reference"]["median_ms"] / res[mode]["ours"]["median_ms"], 3) for mode in res if mode in ("cold", "memo")})
     return res
 

@@ -135,6 +135,9 @@ SIGNATURES = {
     "tgn_centroid_loss_workspace_bytes": (c_size_t, [c_int]),
     "tgn_centroid_loss_forward": (c_int, [c_int, c_int, c_int] + [_P] * 9 + [c_size_t, _P]),
     "tgn_centroid_loss_backward": (c_int, [c_int, c_int, c_int] + [_P] * 11),
+    "tgn_cbl_stage_workspace_bytes": (c_size_t, [c_int]),
+    "tgn_cbl_stage_forward": (c_int, [c_int, c_int, c_int] + [_P] * 7 + [c_size_t, _P]),
+    "tgn_cbl_stage_backward": (c_int, [c_int, c_int, c_int] + [_P] * 9),
     "tgn_feature_knn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "tgn_feature_knn": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "tgn_edgeconv2_max": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, ctypes.c_longlong, c_int, _P]),

@@ -12,6 +12,9 @@
   contrast_boundary_stage, contrast_boundary_loss         the contrastive-boundary criterion (models/modules/cbl_point_transformer/heads.py:63-253
                                                           with default.yaml's configuration): the neighbour lists are tgn_knnquery*, the
                                                           (m, K-1, 32) latent differences and their gradient tgn_subtraction_forward / _backward
+  reverse_lists, contrast_boundary_lists,                 the same stage as two fused kernels (csrc/cbl.hip: tgn_cbl_stage_forward / _backward) that
+  contrast_boundary_stage_fused                           never form the difference tensor and whose gradient is bit-reproducible: behind
+                                                          contrast_boundary_loss(fused=True), off by default
 
 The reference loops over B x 16 teeth with boolean masks (one host round trip per tooth and scan) and sorts a (B, M, C) distance
 matrix to read two columns; here a forward is the per-tooth counts and centroids (crops.label_centroids), a point pass and a finishing
@@ -356,20 +359,126 @@ def contrast_boundary_stage(p, f, o, stage_labels, nsample):
     return total / count.clamp(min=1).to(total.dtype) * CBL_WEIGHT, count
 
 
-def contrast_boundary_loss(up_points, latents, target, nsample, stride):
+CBL_FUSED_MAX_K1 = 63        # csrc/cbl.hip: kCblMaxK1, one lane of a wave per neighbour slot
+CBL_FUSED_MAX_C = 128        # kCblMaxC; and C a multiple of 4
+CBL_FUSED_BLOCK_POINTS = 16  # kCblPointsPerBlock: the points one workgroup of the forward takes (a partial sum each)
+
+
+def reverse_lists(idx):
+    """The lists the fused backward gathers along: idx (m, k1) integer neighbour lists -> (rev_start (m + 1,), rev_pair (m * k1,)),
+    int32, where rev_pair[rev_start[i] : rev_start[i + 1]] holds the pair numbers q = i' * k1 + j with idx[i', j] == i in ascending
+    order.  An index outside [0, m) counts as 0, the point the kernels read for it.  Plain torch on the tensor's device, CPU included:
+    a STABLE sort of the flattened lists (equal neighbours keep the order of their pair numbers) and the cumulative counts of the
+    m values, taken as a searchsorted over the sorted keys -- torch.bincount reads its size back from a CUDA tensor, which would
+    synchronise and cannot be captured.  No synchronisation."""
+    if not isinstance(idx, torch.Tensor) or idx.is_floating_point() or idx.is_complex() or idx.dtype == torch.bool:
+        raise TypeError(f"idx must be an integer tensor, got {getattr(idx, 'dtype', type(idx).__name__)}")
+    if idx.dim() != 2:
+        raise ValueError(f"idx must be (m, k1), got {tuple(idx.shape)}")
+    m = idx.shape[0]
+    flat = idx.reshape(-1)
+    flat = torch.where((flat < 0) | (flat >= m), torch.zeros_like(flat), flat)
+    keys, order = torch.sort(flat, stable=True)
+    rev_start = torch.searchsorted(keys, torch.arange(m + 1, dtype=keys.dtype, device=keys.device), out_int32=True)
+    return rev_start, order.to(torch.int32)
+
+
+class _CblStage(Function):
+    """(loss, count) of packed float32 f (m, C), int32 idx (m, k1) and int64 labels (m,)."""
+
+    @staticmethod
+    @_fwd
+    def forward(ctx, f, idx, labels):
+        m, c = f.shape
+        k1 = idx.shape[1]
+        L, dev = _lib.ops(), f.device
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        pair_w = torch.empty(m, k1, dtype=torch.float32, device=dev)
+        ws_bytes = L.tgn_cbl_stage_workspace_bytes(m)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        L.tgn_cbl_stage_forward(m, k1, c, f, idx, labels, loss, count, pair_w, ws, ws_bytes, _lib.stream())
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(f, idx, pair_w, count, *reverse_lists(idx))
+        n = count[0]
+        ctx.mark_non_differentiable(n)
+        return loss[0], n
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, g_loss, _g_count):
+        f, idx, pair_w, count, rev_start, rev_pair = ctx.saved_tensors
+        m, c = f.shape
+        g = g_loss.reshape(1).to(torch.float32).contiguous()
+        grad = torch.empty_like(f)
+        _lib.ops().tgn_cbl_stage_backward(m, idx.shape[1], c, f, idx, pair_w, count, rev_start, rev_pair, g, grad, _lib.stream())
+        return grad, None, None
+
+
+def _cbl_fused_supported(c, k1):
+    return 1 <= k1 <= CBL_FUSED_MAX_K1 and 4 <= c <= CBL_FUSED_MAX_C and c % 4 == 0
+
+
+def contrast_boundary_lists(f, idx, labels):
+    """One stage of the criterion on neighbour lists the caller supplies, as fused kernels: latent features f (m, C) floating, idx
+    (m, k1) integer -- the lists WITHOUT their column 0 -- and integer labels (m,) -> (loss, count) as contrast_boundary_stage defines
+    them.  The (m, k1, C) differences are never formed: the forward keeps one (m, k1) float32 weight per pair, the backward gathers
+    every row's gradient along reverse_lists(idx) without float atomics, so loss, count AND gradient are the same bits for the same
+    inputs.  1 <= k1 <= 63, C a multiple of 4 in 4..128 and m * k1 < 2^31, otherwise ValueError; an index outside [0, m) reads point 0
+    and latches _lib.INDEX_ERROR_GATHER on the stream.  No synchronisation; forward and backward can be captured in a graph."""
+    f = _lib.f32c(f, "f")
+    idx = _lib.idx32c(idx, "idx")
+    if not isinstance(labels, torch.Tensor) or labels.is_floating_point() or labels.is_complex() or labels.dtype == torch.bool:
+        raise TypeError(f"labels must be an integer tensor, got {getattr(labels, 'dtype', type(labels).__name__)}")
+    if f.dim() != 2:
+        raise ValueError(f"f must be (m, C), got {tuple(f.shape)}")
+    m, c = f.shape
+    if idx.dim() != 2 or idx.shape[0] != m:
+        raise ValueError(f"idx must be (m, k1) with m = {m} like f, got {tuple(idx.shape)}")
+    if labels.numel() != m:
+        raise ValueError(f"labels must hold one label per point ({m}), got {tuple(labels.shape)}")
+    k1 = idx.shape[1]
+    if not _cbl_fused_supported(c, k1) or m * k1 >= 2 ** 31:
+        raise ValueError(f"f (m, C) = {tuple(f.shape)} and idx (m, k1) = {tuple(idx.shape)}: the fused stage needs 1 <= k1 <= {CBL_FUSED_MAX_K1}, "
+                         f"C a multiple of 4 with 4 <= C <= {CBL_FUSED_MAX_C} and m * k1 < 2^31")
+    _lib.require_cuda(f, idx, labels)
+    return _CblStage.apply(f, idx, labels.reshape(-1).long().contiguous())
+
+
+def contrast_boundary_stage_fused(p, f, o, stage_labels, nsample):
+    """contrast_boundary_stage with the part behind the neighbour search as fused kernels (contrast_boundary_lists): the same arguments,
+    the same (loss, count), the same lists pointops.knn_indices(K, p, p, o, o)[:, 1:].  Against contrast_boundary_stage the peak memory
+    loses the (m, K-1, C) tensor it holds up to 2.5 times, and the gradient is bit-reproducible; the values agree to float32 rounding
+    (another, fixed, order of the same sums).  A latent width or an nsample outside the kernels' range (C a multiple of 4 in 4..128,
+    2 <= nsample <= 64) goes through contrast_boundary_stage."""
+    K1 = int(nsample) - 1
+    if K1 < 1:
+        raise ValueError(f"nsample must be at least 2 (one neighbour beside the dropped column 0), got {nsample}")
+    if not _cbl_fused_supported(f.shape[-1], K1):
+        return contrast_boundary_stage(p, f, o, stage_labels, nsample)
+    lab = stage_labels.reshape(-1)
+    if lab.shape[0] != p.shape[0] or f.shape[0] != p.shape[0]:
+        raise ValueError(f"p, f and stage_labels must hold the same number of points, got {p.shape[0]}, {f.shape[0]} and {lab.shape[0]}")
+    idx = pointops.knn_indices(int(nsample), p, p, o, o)[:, 1:].contiguous()            # (m, K-1) int32
+    return contrast_boundary_lists(f, idx, lab)
+
+
+def contrast_boundary_loss(up_points, latents, target, nsample, stride, fused=False):
     """heads.ContrastHead.forward over the decoder stages (`stage: Ua`): up_points = [[p_i, o_i], ...], latents = [f_i (m_i, 32), ...],
     target (n_0,) integer, already + 1 (cbl_point_transformer_module.py:200-202) -> (losses (stages,), counts (stages,) int64).  Stage 0
-    is labelled by the target itself, stage i >= 1 by stage_vote with kr = prod(stride[:i]) (get_model sets nstride = stride)."""
+    is labelled by the target itself, stage i >= 1 by stage_vote with kr = prod(stride[:i]) (get_model sets nstride = stride).
+    fused=True: every stage through contrast_boundary_stage_fused instead of contrast_boundary_stage."""
     if len(up_points) != len(latents):
         raise ValueError(f"{len(up_points)} stages of points and {len(latents)} of latent features")
     target = target.reshape(-1).long()
     p0, o0 = up_points[0]
     if target.shape[0] != p0.shape[0]:
         raise ValueError(f"target must hold one label per stage-0 point ({p0.shape[0]}), got {target.shape[0]}")
+    stage = contrast_boundary_stage_fused if fused else contrast_boundary_stage
     stage_losses, counts = [], []
     for i, ((p, o), f) in enumerate(zip(up_points, latents)):
         labels = target if i == 0 else stage_vote(p0, o0, p, o, target, int(np.prod(stride[:i])))
-        loss, count = contrast_boundary_stage(p, f, o, labels, nsample[i])
+        loss, count = stage(p, f, o, labels, nsample[i])
         stage_losses.append(loss)
         counts.append(count)
     return torch.stack(stage_losses), torch.stack(counts)

@@ -246,6 +246,7 @@ class PointTransformerSeg(nn.Module):
         self.c, self.k, self.block_num = c, k, block_num
         self.stride, self.nsample = tuple(stride)[:block_num], tuple(nsample)[:block_num]     # the criterion's nstride and nsample
         self.cbl_counts = None                                                                # see forward(contrast=True)
+        self.fused_contrast = False     # forward(contrast=True): the criterion's stages as fused kernels (contrast_boundary_loss(fused=True))
         planes = tuple(planes)[:block_num]
         in_planes = c
         for i in range(block_num):
@@ -269,7 +270,8 @@ class PointTransformerSeg(nn.Module):
         reference; all_offsets=True runs it for any B (GroupingNetworkModule's unlabelled path, one scan at a time).
 
         contrast=True: inputs = [features, labels (B, 1, N) or (B, N)] -> [cbl_loss (block_num,), cls, offset, None, x1], the reference's
-        list for two inputs (:198-204): losses.contrast_boundary_loss on target = labels + 1 with this network's nsample and stride,
+        list for two inputs (:198-204): losses.contrast_boundary_loss on target = labels + 1 with this network's nsample and stride
+        (and fused=self.fused_contrast, an attribute the trainer sets: off unless asked for),
         over the latent features the LAST head that ran left behind -- every head overwrites stage['latent'] (heads.py:57), so the
         criterion reads the offset head's when it ran (B == 1, or all_offsets) and the class head's otherwise.  Checkpoints trained
         with the reference carry that quirk, so it is kept.  `self.cbl_counts` is the number of contributing points per stage of THIS
@@ -312,7 +314,7 @@ class PointTransformerSeg(nn.Module):
             latents = []
             offset = self.offset_head(up, latents).view(B, N, 3).permute(0, 2, 1)
         cbl_loss, self.cbl_counts = _losses.contrast_boundary_loss([[pi, oi] for pi, _, oi in up], latents, inputs[1].reshape(-1).long() + 1,
-                                                                     self.nsample, self.stride)
+                                                                     self.nsample, self.stride, fused=self.fused_contrast)
         return [cbl_loss, cls, offset, None, up[0][1]]
 
 

@@ -342,7 +342,9 @@ class FpsGroupingNetworkModel(TrainingModel):
     weights and, opt-in, the contrastive-boundary terms.  tr_set["contrastive_boundary"] true and a non-zero cbl_loss_1 / cbl_loss_2
     weight: the train-phase forward runs the module with contrast=True and the train-phase LossMap gains cbl_loss_1 and cbl_loss_2,
     output[...].sum() with the configuration's weights (fps_grouping_network_model.py:58-59).  Without the key a non-zero weight is
-    refused; with the key and both weights zero or absent the criterion is not computed at all."""
+    refused; with the key and both weights zero or absent the criterion is not computed at all.  tr_set["contrastive_boundary_fused"]
+    true: both networks of the module compute the criterion's stages with the fused kernels (losses.contrast_boundary_stage_fused:
+    no (m, K-1, 32) difference tensor, a bit-reproducible gradient); off by default."""
     module_class = nets.GroupingNetworkModule
     model_name = "tgnet_fps"
     TERMS = ("tooth_class_loss_1", "tooth_class_loss_2", "offset_1_loss", "offset_1_dir_loss", "chamf_1_loss")
@@ -365,6 +367,8 @@ class FpsGroupingNetworkModel(TrainingModel):
     def __init__(self, config, module=None):
         super().__init__(config, module)
         self.contrast = bool(config["tr_set"].get("contrastive_boundary")) and bool(self.cbl_asked(config))
+        for net in (self.module.first_ins_cent_model, self.module.second_ins_cent_model):
+            net.fused_contrast = bool(config["tr_set"].get("contrastive_boundary_fused"))
 
     def forward(self, inputs):
         # self.module.training is the phase (TrainingModel._set_model): the criterion is part of the train phase only
