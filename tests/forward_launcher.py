@@ -16,12 +16,14 @@ class CpuStep:
         self.device = device
 
     def __call__(self, batch_idx, batch_item):
-        from toothgroupnetwork_amd import eval_sharded
+        from toothgroupnetwork_amd import training
         feat, seg = batch_item["feat"], batch_item["gt_seg_label"]
         assert feat.shape[:2] == (1, 6) and seg.shape[:2] == (1, 1) and int(seg.min()) >= -1
         a = float(feat.double().abs().mean()) + batch_idx
         b = float((seg + 1).double().mean())
-        return eval_sharded.print_dict({"tooth_class_loss_1": (a, 1), "aux": (b, 0.5)}, "val")
+        loss_map = training.LossMap()
+        loss_map.add_loss_by_dict({"tooth_class_loss_1": (a, 1), "aux": (b, 0.5)})
+        return loss_map.get_loss_dict_for_print("val")
 
 
 if __name__ == "__main__":

@@ -1,4 +1,4 @@
-"""GPU: the scoring kernels (csrc/metrics.hip) and their host layer (metrics.py, eval_sharded's scored steps) against the reference's
+"""GPU: the scoring kernels (csrc/metrics.hip) and their host layer (metrics.py, eval_sharded's scored ModelStep) against the reference's
 outputs (tests/golden/reference_cpu_r14_metrics.npz) and the numpy statement of the contract (tests/metrics_ref.py).  Counts are
 integers and the scores float64 arithmetic in a fixed order: every comparison here is equality."""
 import os
@@ -247,7 +247,7 @@ def test_confusion_from_logits_equals_confusion_of_the_argmax(M, dev, P, shape):
 
 
 class _Stub(torch.nn.Module):
-    """returns stored logits, whatever it is given (output 0)"""
+    """returns stored logits, whatever it is given (as "cls_pred")"""
 
     def __init__(self, table):
         super().__init__()
@@ -255,7 +255,7 @@ class _Stub(torch.nn.Module):
 
     def forward(self, inputs):
         key = int(inputs[0][0, 0, 0].item())
-        return [self.table[key].to(inputs[0].device)]
+        return {"cls_pred": self.table[key].to(inputs[0].device)}
 
 
 def _items(rng, N=512, C=17):
@@ -275,28 +275,33 @@ def _items(rng, N=512, C=17):
 
 
 def test_scored_class_step_and_eval_sharded(M, dev):
-    from toothgroupnetwork_amd import eval_sharded as E
+    from toothgroupnetwork_amd import eval_sharded as E, training
     items, table = _items(np.random.default_rng(1450))
-    step = E.ScoredClassStep(_Stub(table), dev)
-    plain = E.PointTransformerStep(_Stub(table), dev)
+    model = training.PointPpFirstModel({}, module=lambda config: _Stub(table), trainable=False)
+    step = E.ModelStep(model, scored=True)
+    plain = E.ModelStep(model)
     outs = []
     for k, item in enumerate(items):
         out = step(k, item)
-        assert tuple(out) == E.ScoredClassStep.keys
+        assert tuple(out) == step.keys
         base = plain(k, item)
+        assert tuple(base) == plain.keys == ("tooth_class_loss_1_val", "total_val")
         assert out["tooth_class_loss_1_val"] == base["tooth_class_loss_1_val"] and out["total_val"] == base["total_val"]
+        # torch itself, not the code under test
+        labels = item["gt_seg_label"] + 1
+        assert out["tooth_class_loss_1_val"] == torch.nn.functional.cross_entropy(table[k].float().to(dev), labels.view(1, -1).to(dev)).item()
         pred = torch.argmax(table[k], 1).reshape(-1).numpy()
         gt = item["gt_seg_label"].reshape(-1).numpy() + 1
         if k == 1:
-            assert [out[key] for key in E.ScoredClassStep.keys[2:]] == [0.0, 0.0, 0.0, 0.0, 1.0]
+            assert [out[key] for key in step.keys[2:]] == [0.0, 0.0, 0.0, 0.0, 1.0]
         else:
             want = M.cal_metric(gt, pred, pred)
             assert R.f64_bytes(want[:4]) == R.f64_bytes(R.cal_metric(gt, pred, pred, nlab=17)[:4])
-            assert [out[key] for key in E.ScoredClassStep.keys[2:]] == [want[0], want[1], want[2], want[3], 0.0]
+            assert [out[key] for key in step.keys[2:]] == [want[0], want[1], want[2], want[3], 0.0]
         outs.append(out)
     res = E.eval_sharded(["a", "b", "c"], step, 0, 1, device=dev, load=lambda p: items["abc".index(p)])
     assert res["steps"] == 3
-    for key in E.ScoredClassStep.keys:
+    for key in step.keys:
         assert res["avg"][key] == (outs[0][key] + outs[1][key] + outs[2][key]) / 3      # the meter's sum, in its order
         assert np.isfinite(res["avg"][key])
     assert res["avg"]["unscored_val"] == 1.0 / 3

@@ -121,10 +121,12 @@ def test_forward_sharded_rank_mismatch_is_an_error(tmp_path):
     assert out.returncode != 0 and "refusing to report" in out.stderr
 
 
-def test_loss_meter_and_print_dict_follow_the_reference():
+def test_loss_meter_and_loss_map_follow_the_reference():
     """loss_meter.py:2-23 / :50-62 semantics: weighted values, a total, sums over steps, averages by step count"""
-    from toothgroupnetwork_amd import eval_sharded as E
-    d = E.print_dict({"a": (2.0, 0.5), "b": (3.0, 1)}, "val")
+    from toothgroupnetwork_amd import eval_sharded as E, training
+    lmap = training.LossMap()
+    lmap.add_loss_by_dict({"a": (2.0, 0.5), "b": (3.0, 1)})
+    d = lmap.get_loss_dict_for_print("val")
     assert d == {"a_val": 1.0, "b_val": 3.0, "total_val": 4.0}
     m = E.LossMeter()
     m.aggr(d)
@@ -134,32 +136,87 @@ def test_loss_meter_and_print_dict_follow_the_reference():
     assert m.step_num == 0 and m.loss_meter_dict == {}
 
 
+class _FakeModel:
+    """evaluate and val_terms, what ModelStep asks of a model; step, what Trainer.test asks: two fixed functions of the item"""
+    val_terms = ("a", "b")
+
+    def evaluate(self, batch_item, phase):
+        import torch
+
+        from toothgroupnetwork_amd import training
+        assert phase == "test"
+        x = batch_item["x"]
+        lmap = training.LossMap()
+        lmap.add_loss_by_dict({"a": (torch.tensor(x * x + 0.1, dtype=torch.float32), 0.3), "b": (x / 7, 2)})
+        return {"x": x}, lmap
+
+    def step(self, batch_idx, batch_item, phase):
+        return self.evaluate(batch_item, phase)[1]
+
+
+def test_model_step_in_the_sharded_loop_equals_the_trainers_test():
+    import torch
+
+    from toothgroupnetwork_amd import eval_sharded as E, training
+    assert training.LossMeter is E.LossMeter and training.load_item is E.load_item, "one meter and one loader in the package"
+    items = [{"x": 0.3}, {"x": 1.7}, {"x": 2.9}]
+    step = E.ModelStep(_FakeModel())
+    assert step.keys == ("a_val", "b_val", "total_val")
+    got = E.eval_sharded([0, 1, 2], step, 0, 1, load=lambda i: items[i])
+    want = training.Trainer(model=_FakeModel()).test(0, items, False)
+    assert got["steps"] == 3 and list(got["avg"]) == list(want) == list(step.keys)
+    for key in want:
+        assert got["avg"][key] == want[key], key                          # float for float
+    with pytest.raises(TypeError, match="val_terms"):
+        E.ModelStep(type("NoTerms", (), {"evaluate": _FakeModel.evaluate})())
+    # a reported value: read with the terms, printed behind the total, in neither the total nor the sum
+    term, score = torch.tensor(0.1, dtype=torch.float32), torch.tensor(1.0 / 3, dtype=torch.float64)
+    lmap = training.LossMap()
+    lmap.add_loss("a", term, 0.3)
+    plain, total = lmap.get_loss_dict_for_print("val"), float(lmap.get_sum())
+    lmap.add_value("score", score)
+    printed = lmap.get_loss_dict_for_print("val")
+    assert list(printed) == ["a_val", "total_val", "score_val"]
+    assert printed == {**plain, "score_val": 1.0 / 3} and printed["a_val"] == term.item() * 0.3
+    assert float(lmap.get_sum()) == total
+    with pytest.raises(KeyError, match="score"):
+        lmap.add_value("score", score)
+
+
 @pytest.mark.parametrize("net,prefix", [("PointNetPPSeg", "first_sem_model."), ("PointTransformerSeg", "first_ins_cent_model.")])
 def test_forward_sharded_loads_a_reference_style_checkpoint(tmp_path, net, prefix):
     """the reference saves `self.module.state_dict()` of its wrapper module (base_model.py:33-37): the network's keys carry the
     wrapper's attribute name (pointnet_pp.py:78, point_transformer.py:9) and the loss's buffers ride along as `criterion.*`;
-    tools/forward_sharded.py --checkpoint must load such a file into the bare network mirror, and a bare state_dict still loads"""
+    TrainingModel.save writes the same without the criterion.  tools/forward_sharded.py --checkpoint loads both and the bare
+    network's state_dict through one function, strictly."""
     import importlib.util
 
     import torch
 
-    from toothgroupnetwork_amd import eval_sharded, nets
-    torch.manual_seed(3)
-    src = getattr(nets, net)()
-    wrapped = {prefix + k: v.clone() for k, v in src.state_dict().items()}
-    wrapped["criterion.class_weight"] = torch.ones(17)
-    stripped = eval_sharded.reference_state_dict(wrapped)
-    assert set(stripped) == set(src.state_dict()) and eval_sharded.reference_state_dict(src.state_dict()) is not None
-    path = str(tmp_path / "ckpt.h5")
-    torch.save(wrapped, path)
+    from toothgroupnetwork_amd import eval_sharded, inference, nets
     spec = importlib.util.spec_from_file_location("forward_sharded", os.path.join(REPO, "tools", "forward_sharded.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    name = "pointnetpp" if net == "PointNetPPSeg" else "pointtransformer"
-    step = mod.build_step(name, torch.device("cpu"), checkpoint=path, seed=99)       # (seed 99: other weights unless the file is loaded)
-    for k, v in src.state_dict().items():
-        assert torch.equal(step.module.state_dict()[k], v), k
-    bare = str(tmp_path / "bare.h5")
-    torch.save(src.state_dict(), bare)
-    step = mod.build_step(name, torch.device("cpu"), checkpoint=bare, seed=98)
-    assert all(torch.equal(step.module.state_dict()[k], v) for k, v in src.state_dict().items())
+    if net == "PointNetPPSeg":
+        build = lambda: nets.PointPpFirstModule({})                                                      # noqa: E731
+    else:
+        build = lambda: nets.PointTransformerModule(inference.inference_config("pointtransformer")["model_info"])   # noqa: E731
+    torch.manual_seed(3)
+    src = build()
+    own = {k: v.clone() for k, v in src.state_dict().items()}
+    assert all(k.startswith(prefix) for k in own)
+    reference = {**own, "criterion.x": torch.ones(17)}
+    bare = {k: v.clone() for k, v in getattr(src, prefix[:-1]).state_dict().items()}
+    assert type(getattr(src, prefix[:-1])).__name__ == net
+    assert set(eval_sharded.reference_state_dict(reference)) == set(bare) == set(eval_sharded.reference_state_dict(bare))
+    for form in (own, reference, bare):
+        path = str(tmp_path / "ckpt.h5")
+        torch.save(form, path)
+        torch.manual_seed(99)                                             # other weights unless the file is loaded
+        dst = build()
+        mod.load_checkpoint(dst, torch.load(path, map_location="cpu"))
+        for k, v in own.items():
+            assert torch.equal(dst.state_dict()[k], v), k
+    for wrong in ({**own, prefix + "no_such_key": torch.ones(1)}, {k: v for k, v in list(bare.items())[1:]}):
+        with pytest.raises(RuntimeError, match="state_dict"):
+            mod.load_checkpoint(dst, wrong)

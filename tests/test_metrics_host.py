@@ -136,9 +136,9 @@ def test_scoring_refuses_cpu_tensors_and_non_integer_labels():
 def test_scored_steps_declare_their_schema():
     from toothgroupnetwork_amd import eval_sharded as E
     keys = ("tooth_class_loss_1_val", "total_val", "iou_val", "f1_val", "acc_val", "sem_acc_val", "unscored_val")
-    assert E.ScoredClassStep.keys == keys
-    assert E.ScoredPointNetPPStep.keys == keys and E.ScoredPointTransformerStep.keys == keys
-    assert E.PointNetPPStep.keys == ("tooth_class_loss_1_val", "total_val")      # the unscored steps are as they were
+    fake = type("Fake", (), {"val_terms": ("tooth_class_loss_1",)})()
+    assert E.ModelStep(fake, scored=True).keys == keys
+    assert E.ModelStep(fake).keys == ("tooth_class_loss_1_val", "total_val")     # the unscored steps are as they were
 
 
 def test_product_scoring_code_does_not_import_the_test_reference():

@@ -26,20 +26,27 @@ from toothgroupnetwork_amd import eval_sharded, launch, sharding  # noqa: E402
 METRIC = "validation scans/sec (per-scan forward + loss, trainer.py:49-54)"
 
 
-def build_step(name, device, checkpoint=None, seed=0):
+def load_checkpoint(module, state):
+    """Loads `state` strictly into the network of a wrapper module (nets.PointPpFirstModule, nets.PointTransformerModule: the
+    network is their one child).  `state` is a wrapper's state_dict -- what the reference's trainer and training.TrainingModel.save
+    write, `criterion.*` entries or not -- or the bare network's."""
+    (network,) = module.children()
+    network.load_state_dict(eval_sharded.reference_state_dict(state))
+
+
+def build_step(name, checkpoint=None, seed=0):
     import torch
 
-    from toothgroupnetwork_amd import nets
+    from toothgroupnetwork_amd import inference, training
+    config = {}
+    if name == "pointtransformer":
+        config = {"model_parameter": inference.inference_config(name)["model_info"]["model_parameter"],
+                  "tr_set": {"loss": {"tooth_class_loss_1": 1}}}
     torch.manual_seed(seed)                       # every rank builds the same random-init weights when no checkpoint is given
-    if name == "pointnetpp":
-        module, step_cls = nets.PointNetPPSeg(), eval_sharded.PointNetPPStep
-    elif name == "pointtransformer":
-        module, step_cls = nets.PointTransformerSeg(), eval_sharded.PointTransformerStep
-    else:
-        raise SystemExit(f"unknown --model {name!r}")
+    model = training.make_training_model(name, config, trainable=False)
     if checkpoint:
-        module.load_state_dict(eval_sharded.reference_state_dict(torch.load(checkpoint, map_location="cpu")))
-    return step_cls(module, device)
+        load_checkpoint(model.module, torch.load(checkpoint, map_location="cpu"))
+    return eval_sharded.ModelStep(model)
 
 
 def main(argv=None, step_factory=None, script=None):
@@ -73,7 +80,7 @@ def main(argv=None, step_factory=None, script=None):
     if not root:
         launch.fail("--input_data_dir_path or --synthetic N", stage_name="setup", code=2)
     paths = eval_sharded.list_preprocessed(root)
-    step = step_factory(device) if step_factory is not None else build_step(args.model, device, args.checkpoint)
+    step = step_factory(device) if step_factory is not None else build_step(args.model, args.checkpoint)
     launch.stage("calibrate")
     if step_factory is None and paths:            # first use of the GPU by this rank (context, code objects, memoised folds): no scan's time
         step(-1, eval_sharded.load_item(paths[rank % len(paths)]))

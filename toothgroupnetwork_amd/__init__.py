@@ -14,7 +14,7 @@ Point-Transformer subtraction / aggregation operators).
     toothgroupnetwork_amd.nets              whole-network mirrors (state_dict-compatible with the reference's modules)
     toothgroupnetwork_amd.sharding          one-process-per-GPU mesh sharding + the RCCL metric gather
     toothgroupnetwork_amd.launch            starting the ranks of a multi-GPU run; rank / device / backend records
-    toothgroupnetwork_amd.eval_sharded      trainer.py's per-scan validation loop over ranks (LossMeter sums gathered once)
+    toothgroupnetwork_amd.eval_sharded      trainer.py's per-scan validation loop over ranks, on training.py's model steps (LossMeter sums gathered once)
     toothgroupnetwork_amd.infer_run         start_inference.py: the scans of a split through a pipeline into result files, sharded, scored
     toothgroupnetwork_amd.hotpath           the benchmarked launch plan (FPS -> ball query -> group over three HIP streams)
     toothgroupnetwork_amd.config            the Python-side switches, one object

@@ -10,10 +10,9 @@ loop's: sum over all scans / number of scans.
 
 The model side is a *step object*: ``step(batch_idx, batch_item) -> {name_val: float, ..., total_val: float}`` with a
 fixed ``keys`` tuple (the metric schema must be the same on every rank, also on a rank whose shard is empty).
-``PointNetPPStep`` / ``PointTransformerStep`` restate the "test" branch of models/pointnet_pp_model.py:14-39 and
-models/transformer_model.py:13-36 over this package's network mirrors (nets.py); they need the GPU like every operator
-of the package.  ``ScoredClassStep`` and its two subclasses add the segmentation scores of every scan (metrics.py: IoU, F1,
-accuracy, SEM_ACC of the predicted classes) to the same meter.  Tests of the control flow hand in their own step object.
+``ModelStep`` makes one of a trainer's model (training.TrainingModel.evaluate, phase "test") and, with ``scored=True``, adds
+the segmentation scores of every scan (metrics.py: IoU, F1, accuracy, SEM_ACC of the predicted classes) to the same meter.
+Tests of the control flow hand in their own step object.
 """
 import glob
 import os
@@ -23,25 +22,7 @@ import numpy as np
 import torch
 
 from . import launch, metrics, sharding
-
-
-class LossMeter:
-    """loss_meter.py:2-23: running sums per key and a step count; averages on request."""
-
-    def __init__(self):
-        self.init()
-
-    def init(self):
-        self.step_num = 0
-        self.loss_meter_dict = {}
-
-    def aggr(self, loss_map):
-        for key, value in loss_map.items():
-            self.loss_meter_dict[key] = self.loss_meter_dict.get(key, 0) + value
-        self.step_num += 1
-
-    def get_avg_results(self):
-        return {key: total / self.step_num for key, total in self.loss_meter_dict.items()}
+from .training import LossMeter, load_item
 
 
 def list_preprocessed(data_dir):
@@ -49,101 +30,38 @@ def list_preprocessed(data_dir):
     return sorted(glob.glob(os.path.join(data_dir, "*_sampled_points.npy")))
 
 
-def load_item(path):
-    """One validation item the way generator.py:40-66 builds it (no augmentation), already batched by the loader's
-    collate (runner.py:7-19) at batch size 1: feat (1, 6, N) fp32, gt_seg_label (1, 1, N) int64 with gingiva = -1."""
-    arr = np.load(path)
-    # (layout changes in numpy: torch's CPU kernels would fan a 144 000-element copy out over every hardware thread of the box --
-    #  25 ms per scan on a 128-thread host under a 16-core quota, against 3 ms for the forward itself)
-    feat = np.ascontiguousarray(arr[:, :6].T, dtype=np.float32)[None]
-    seg = np.ascontiguousarray(arr[:, 6:].T.astype(np.int64) - 1)[None]
-    return {"feat": torch.from_numpy(feat), "gt_seg_label": torch.from_numpy(seg), "mesh_path": [path]}
+class ModelStep:
+    """The step object of `model`: anything with training.TrainingModel's `evaluate(batch_item, phase) -> (output, LossMap)` and a
+    `val_terms` tuple, the names of its test-phase terms (training._ClassModel).  __call__ is Trainer.test's loop body:
+    evaluate(batch_item, "test") and the LossMap's get_loss_dict_for_print("val").
 
-
-def print_dict(named_losses, post_fix):
-    """LossMap.get_loss_dict_for_print (loss_meter.py:50-62): value * weight per key, and their total"""
-    out = {f"{name}_{post_fix}": float(value) * weight for name, (value, weight) in named_losses.items()}
-    out[f"total_{post_fix}"] = sum(out.values())
-    return out
-
-
-def tooth_class_loss(cls_pred, gt_cls):
-    """tgn_loss.py:355-367 without weights / smoothing: cross entropy of (B, 17, N) logits against labels shifted by one
-    (gingiva -1 -> class 0)"""
-    b = gt_cls.shape[0]
-    return torch.nn.functional.cross_entropy(cls_pred.float(), gt_cls.view(b, -1).long() + 1)
-
-
-class _ClassStep:
-    keys = ("tooth_class_loss_1_val", "total_val")
-
-    def __init__(self, module, device, weight=1, output_index=0):
-        self.module, self.device, self.weight, self.output_index = module.to(device).eval(), device, weight, output_index
-
-    def __call__(self, batch_idx, batch_item):
-        points = batch_item["feat"].to(self.device)
-        seg_label = batch_item["gt_seg_label"].to(self.device)
-        with torch.no_grad():
-            output = self.module([points, seg_label])
-        loss = tooth_class_loss(output[self.output_index], seg_label)
-        return print_dict({"tooth_class_loss_1": (loss.item(), self.weight)}, "val")
-
-
-class PointNetPPStep(_ClassStep):
-    """models/pointnet_pp_model.py:14-39, phase "test": class logits are output 6 of the network (pointnet_pp.py:63-68)"""
-
-    def __init__(self, module, device):
-        super().__init__(module, device, weight=1, output_index=6)
-
-
-class PointTransformerStep(_ClassStep):
-    """models/transformer_model.py:13-36, phase "test": `sem_1` is the first output of the segmentation network"""
-
-    def __init__(self, module, device, weight=1):
-        super().__init__(module, device, weight=weight, output_index=0)
-
-
-class ScoredClassStep:
-    """_ClassStep plus the scores of the step's prediction (metrics.confusion_from_logits on the class logits and gt_seg_label, then
-    metrics.scores): iou_val, f1_val, acc_val, sem_acc_val as cal_metric gives them for torch.argmax of the logits, with the classes
+    scored=True adds the scores of the step's prediction (metrics.confusion_from_logits on output[model.output_key] and gt_seg_label,
+    then metrics.scores): iou_val, f1_val, acc_val, sem_acc_val as cal_metric gives them for torch.argmax of the logits, with the classes
     1..C-1 as instances and gingiva -1 counted as class 0.  The scores stay out of total_val, which remains the reference's sum of
     losses.  A scan with no predicted instance (every vertex gingiva) contributes 0.0 to the four scores and 1.0 to unscored_val, so
-    the averages stay finite and the share of such scans is visible.  ONE host read per step fetches the loss and the scores."""
-    keys = ("tooth_class_loss_1_val", "total_val", "iou_val", "f1_val", "acc_val", "sem_acc_val", "unscored_val")
+    the averages stay finite and the share of such scans is visible.  They ride in the LossMap (add_value): ONE host read per step
+    fetches the loss and the scores."""
+    SCORES = ("iou", "f1", "acc", "sem_acc", "unscored")
 
-    def __init__(self, module, device, weight=1, output_index=0, is_half=False):
-        self.module, self.device, self.weight, self.output_index = module.to(device).eval(), device, weight, output_index
-        self.is_half = is_half
+    def __init__(self, model, scored=False, is_half=False):
+        if not hasattr(model, "val_terms"):
+            raise TypeError(f"{type(model).__name__} declares no val_terms: every rank of a sharded validation, also one whose shard is "
+                            "empty, needs the names of the step's terms before the first step, and this model does not name them")
+        self.model, self.scored, self.is_half = model, scored, is_half
+        self.keys = tuple(f"{t}_val" for t in model.val_terms) + ("total_val",) + (tuple(f"{n}_val" for n in self.SCORES) if scored else ())
 
     def __call__(self, batch_idx, batch_item):
-        points = batch_item["feat"].to(self.device)
-        seg_label = batch_item["gt_seg_label"].to(self.device)
-        with torch.no_grad():
-            output = self.module([points, seg_label])
-        logits = output[self.output_index]
-        loss = tooth_class_loss(logits, seg_label)
-        sc = metrics.scores(*metrics.confusion_from_logits(logits, seg_label, gt_shift=1), is_half=self.is_half)
-        per_scan = torch.stack([sc.iou, sc.f1, sc.acc, sc.sem_acc])                                # (4, B) float64
-        scored = sc.instances > 0
-        means = torch.where(scored[None], per_scan, torch.zeros_like(per_scan)).mean(1)
-        host = torch.cat([loss.double().reshape(1), means, (~scored).double().mean().reshape(1)]).tolist()    # the one host read
-        out = print_dict({"tooth_class_loss_1": (host[0], self.weight)}, "val")
-        out.update(zip(self.keys[2:], host[1:]))
-        return out
-
-
-class ScoredPointNetPPStep(ScoredClassStep):
-    """PointNetPPStep with scores: class logits are output 6 of the network"""
-
-    def __init__(self, module, device, is_half=False):
-        super().__init__(module, device, weight=1, output_index=6, is_half=is_half)
-
-
-class ScoredPointTransformerStep(ScoredClassStep):
-    """PointTransformerStep with scores: `sem_1` is the first output of the segmentation network"""
-
-    def __init__(self, module, device, weight=1, is_half=False):
-        super().__init__(module, device, weight=weight, output_index=0, is_half=is_half)
+        output, loss_map = self.model.evaluate(batch_item, "test")
+        if self.scored:
+            logits = output[self.model.output_key]
+            sc = metrics.scores(*metrics.confusion_from_logits(logits, batch_item["gt_seg_label"].to(logits.device), gt_shift=1),
+                                is_half=self.is_half)
+            per_scan = torch.stack([sc.iou, sc.f1, sc.acc, sc.sem_acc])                                # (4, B) float64
+            scored = sc.instances > 0
+            means = torch.where(scored[None], per_scan, torch.zeros_like(per_scan)).mean(1)
+            for name, value in zip(self.SCORES, [*means, (~scored).double().mean()]):
+                loss_map.add_value(name, value)
+        return loss_map.get_loss_dict_for_print("val")
 
 
 def reference_state_dict(state):

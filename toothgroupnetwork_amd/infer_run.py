@@ -115,7 +115,7 @@ def run_scans(pipeline, paths, save_path, batch=8, workers=None):
 def score_files(pred_paths, gt_dir):
     """Each result file with the ground-truth file of the same name below gt_dir (recursively), all pairs in one ragged launch.  As the
     reference's scoring script does, a prediction's "labels" serve as semantic and as instance labels.  -> [pairs, unscored, sums of iou,
-    f1, acc, sem_acc]: a scan without an instance adds 0.0 to the four sums and 1 to `unscored`, as eval_sharded.ScoredClassStep counts;
+    f1, acc, sem_acc]: a scan without an instance adds 0.0 to the four sums and 1 to `unscored`, as eval_sharded.ModelStep(scored=True) counts;
     a pair whose lengths differ is left out of `pairs`."""
     from . import metrics
     gt = {os.path.basename(p): p for p in sorted(glob.glob(os.path.join(gt_dir, "**", "*.json"), recursive=True))}

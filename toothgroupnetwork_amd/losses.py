@@ -176,6 +176,13 @@ def centroid_loss(pred_offset, sample_xyz, distance, centroid, exists=None):
     return _CentroidLoss.apply(_lib.f32c(pred_offset), _lib.f32c(sample_xyz.detach()), _lib.f32c(distance.reshape(B, M)), _lib.f32c(centroid.detach()), mask)
 
 
+def tooth_class_loss(cls_pred, gt_cls):
+    """tgn_loss.py:355-367 without weights / smoothing: cross entropy of (B, 17, N) logits against labels shifted by one
+    (gingiva -1 -> class 0)"""
+    b = gt_cls.shape[0]
+    return F.cross_entropy(cls_pred.float(), gt_cls.view(b, -1).long() + 1)
+
+
 def grouping_loss_terms(output, gt_seg_label, input_coords):
     """FpsGroupingNetworkModel.get_loss (models/fps_grouping_network_model.py:8-24) on the output dict of nets.GroupingNetworkModule:
     {"tooth_class_loss_1", "tooth_class_loss_2", "offset_1_loss", "offset_1_dir_loss", "chamf_1_loss"}, unweighted.  The two class

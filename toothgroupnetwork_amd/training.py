@@ -4,7 +4,7 @@ criteria (losses.py).  No new kernel: the hot path of a step is the module's for
 HIP already; this is the layer above them.
 
   DentalModelGenerator, collate_fn, get_generator_set   generator.py, runner.py:7-50
-  LossMap                                               loss_meter.py:26-61 (the meter is eval_sharded.LossMeter)
+  load_item, LossMeter, LossMap                         generator.py:40-66 at batch size 1, loss_meter.py
   build_optimizer, build_scheduler, CosineSchedule      BaseModel.__init__ (models/base_model.py:16-28)
   TrainingModel and one step class per model name       BaseModel and models/*_model.py
   BoundarySampler                                       models/bdl_grouping_netowrk_model.py:20-35, 56-192, over tgnet.py's device functions
@@ -40,8 +40,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from . import augment, eval_sharded, losses, nets, preprocess, tgnet
-from .eval_sharded import LossMeter  # noqa: F401
+from . import augment, losses, nets, preprocess, tgnet
 
 MODEL_NAMES = ("tgnet_fps", "tsegnet", "dgcnn", "pointnet", "pointnetpp", "pointtransformer", "tgnet_bdl")
 SCHEDULERS = ("exp", "cosine")
@@ -51,13 +50,24 @@ STACKED_KEYS = ("feat", "gt_seg_label", "uniform_feat", "uniform_gt_seg_label") 
 
 # ---- data -------------------------------------------------------------------------------------------------------------------------
 
+def load_item(path):
+    """One validation item the way generator.py:40-66 builds it (no augmentation), already batched by the loader's
+    collate (runner.py:7-19) at batch size 1: feat (1, 6, N) fp32, gt_seg_label (1, 1, N) int64 with gingiva = -1."""
+    arr = np.load(path)
+    # (layout changes in numpy: torch's CPU kernels would fan a 144 000-element copy out over every hardware thread of the box --
+    #  25 ms per scan on a 128-thread host under a 16-core quota, against 3 ms for the forward itself)
+    feat = np.ascontiguousarray(arr[:, :6].T, dtype=np.float32)[None]
+    seg = np.ascontiguousarray(arr[:, 6:].T.astype(np.int64) - 1)[None]
+    return {"feat": torch.from_numpy(feat), "gt_seg_label": torch.from_numpy(seg), "mesh_path": [path]}
+
+
 class DentalModelGenerator(Dataset):
     """generator.py:10-71: the `*_sampled_points.npy` files of data_dir, optionally only the patients of a split file (the patient id
     is the file name up to its first underscore, and must be a stripped line of the file).  An item is feat (6, N) float32,
     gt_seg_label (1, N) int64 with gingiva = -1, aug_obj (a deep copy of the augmentation as it was applied, None without) and
     mesh_path.  With an augmentation: reload_vals(), then run, per item.
 
-    The un-augmented item is eval_sharded.load_item's without its batch axis: the two build the same arrays (the columns, the float32
+    The un-augmented item is load_item's without its batch axis: the two build the same arrays (the columns, the float32
     cast, the `- 1`); load_item adds the loader's batch axis of 1 and wraps mesh_path in a list, which is what collate_fn does to
     one item.  The file order is glob's, as in the reference; eval_sharded.list_preprocessed sorts."""
 
@@ -75,7 +85,7 @@ class DentalModelGenerator(Dataset):
 
     def __getitem__(self, idx):
         path = self.mesh_paths[idx]
-        item = eval_sharded.load_item(path.strip())
+        item = load_item(path.strip())
         feat, seg_label = item["feat"][0], item["gt_seg_label"][0]
         if self.aug_obj:
             self.aug_obj.reload_vals()
@@ -109,12 +119,40 @@ def get_generator_set(config):
 
 # ---- losses of a step ---------------------------------------------------------------------------------------------------------------
 
+class LossMeter:
+    """loss_meter.py:2-23: running sums per key and a step count; averages on request."""
+
+    def __init__(self):
+        self.init()
+
+    def init(self):
+        self.step_num = 0
+        self.loss_meter_dict = {}
+
+    def aggr(self, loss_map):
+        for key, value in loss_map.items():
+            self.loss_meter_dict[key] = self.loss_meter_dict.get(key, 0) + value
+        self.step_num += 1
+
+    def get_avg_results(self):
+        return {key: total / self.step_num for key, total in self.loss_meter_dict.items()}
+
+
 class LossMap:
     """loss_meter.py:26-61: named (value, weight) terms of one step.  get_sum() is the weighted sum the step differentiates;
-    get_loss_dict_for_print(post_fix) is {"<term>_<post_fix>": value * weight, ..., "total_<post_fix>": their sum} as python floats."""
+    get_loss_dict_for_print(post_fix) is {"<term>_<post_fix>": value * weight, ..., "total_<post_fix>": their sum} as python floats.
+    add_value(name, tensor) attaches a reported value that is no loss term (a score): read with the terms, printed as
+    "<name>_<post_fix>" behind the total, part of neither get_sum() nor the total."""
 
     def __init__(self):
         self.loss_dict = {}
+        self.value_dict = {}
+        self._host = None
+
+    def add_value(self, name, value):
+        if name in self.loss_dict or name in self.value_dict:
+            raise KeyError(f"LossMap already holds {name!r}")
+        self.value_dict[name] = value
         self._host = None
 
     def add_loss(self, name, value, weight):
@@ -138,15 +176,21 @@ class LossMap:
         return summation
 
     def _values_on_host(self):
-        """Every term's value as a python float: the tensor terms are stacked on their device and read with ONE .tolist() -- one
-        copy, one synchronisation, whatever the number of terms -- and kept, because a step's map is printed under up to three
-        post-fixes (trainer.py:33-35).  A float32 value becomes the same python float that .item() gives."""
+        """Every term's and reported value's python float: the tensors are stacked on their device and read with ONE .tolist() -- one
+        copy, one synchronisation, whatever their number -- and kept, because a step's map is printed under up to three
+        post-fixes (trainer.py:33-35).  A float32 value becomes the same python float that .item() gives, also beside reported
+        values, with which the stack is float64: every float32 is a float64, and .item() widens it the same way."""
         if self._host is None:
-            names = [n for n, (v, _) in self.loss_dict.items() if isinstance(v, torch.Tensor)]
-            host = {n: float(v) for n, (v, _) in self.loss_dict.items() if not isinstance(v, torch.Tensor)}
-            if names:
-                stacked = torch.stack([self.loss_dict[n][0].detach().reshape(()) for n in names])
-                host.update(zip(names, stacked.tolist()))                                  # the one read
+            values = [(n, v) for n, (v, _) in self.loss_dict.items()] + list(self.value_dict.items())
+            tensors = [(n, v) for n, v in values if isinstance(v, torch.Tensor)]
+            host = {n: float(v) for n, v in values if not isinstance(v, torch.Tensor)}
+            if len(tensors) == 1:
+                host[tensors[0][0]] = tensors[0][1].item()                                 # a single one is read where it lies
+            elif tensors:
+                cells = [v.detach().reshape(()) for _, v in tensors]
+                if self.value_dict:
+                    cells = [c.double() for c in cells]
+                host.update(zip([n for n, _ in tensors], torch.stack(cells).tolist()))     # the one read
             self._host = host
         return self._host
 
@@ -157,6 +201,7 @@ class LossMap:
         for value in out.values():
             total += value
         out[f"total_{post_fix}"] = total
+        out.update((f"{name}_{post_fix}", host[name]) for name in self.value_dict)
         return out
 
 
@@ -224,27 +269,34 @@ def build_scheduler(tr_set, optimizer):
 class TrainingModel:
     """models/base_model.py: the module in train mode on the GPU, its optimiser and its scheduler; step / save / load.
 
-    step(batch_idx, batch_item, phase) -> LossMap: phase "train" runs forward, the weighted sum's backward and an optimiser step;
-    "val" and "test" run the forward in eval mode under torch.no_grad().  The batch moves to the device here.  A subclass names its
-    module class and gives `losses_of(output, seg_label, points)` -> {name: (value, weight)}."""
+    evaluate(batch_item, phase) -> (output, LossMap): the forward and its terms; phase "train" runs it in train mode with a graph,
+    "val" and "test" in eval mode under torch.no_grad().  The batch moves to the device here.
+    step(batch_idx, batch_item, phase) -> LossMap: evaluate and, for "train", the weighted sum's backward and an optimiser step.
+    A subclass names its module class and gives `losses_of(output, seg_label, points)` -> {name: (value, weight)}.
+
+    trainable=False is a model that is only evaluated (validation over a checkpoint): the module starts in eval mode, there is no
+    optimiser and no scheduler, the configuration needs no section for either, and step(..., "train") raises."""
 
     module_class = None
 
-    def __init__(self, config, module=None):
-        self.config = config
-        self.check_config(config)
+    def __init__(self, config, module=None, trainable=True):
+        self.config, self.trainable = config, trainable
+        self.check_config(config, trainable)
         if not torch.cuda.is_available():
             raise RuntimeError("training needs a GPU: the modules' operators are HIP kernels and have no CPU fallback")
         self.device = torch.device("cuda")
         self.module = (module or self.module_class)(config)
-        self.module.train()
+        self.module.train(trainable)
         self.module.cuda()
-        self.optimizer = build_optimizer(config["tr_set"], self.module.parameters())
-        self.scheduler = build_scheduler(config["tr_set"], self.optimizer)
+        if trainable:
+            self.optimizer = build_optimizer(config["tr_set"], self.module.parameters())
+            self.scheduler = build_scheduler(config["tr_set"], self.optimizer)
 
     @classmethod
-    def check_config(cls, config):
+    def check_config(cls, config, trainable=True):
         """What can be refused before anything is built: raises for a configuration this class does not train."""
+        if not trainable:
+            return
         check_scheduler(config["tr_set"])
         name = config["tr_set"]["optimizer"]["NAME"]
         if name not in OPTIMIZERS:
@@ -275,7 +327,9 @@ class TrainingModel:
     def losses_of(self, output, seg_label, points):
         raise NotImplementedError
 
-    def step(self, batch_idx, batch_item, phase):
+    def evaluate(self, batch_item, phase):
+        if phase == "train" and not self.trainable:
+            raise RuntimeError("this model was built with trainable=False: it has no optimiser, so it has no train phase")
         self._set_model(phase)
         points = batch_item["feat"].to(self.device)
         seg_label = batch_item["gt_seg_label"].to(self.device)
@@ -286,6 +340,10 @@ class TrainingModel:
                 output = self.forward([points, seg_label])
         loss_meter = LossMap()
         loss_meter.add_loss_by_dict(self.losses_of(output, seg_label, points))
+        return output, loss_meter
+
+    def step(self, batch_idx, batch_item, phase):
+        _, loss_meter = self.evaluate(batch_item, phase)
         if phase == "train":
             loss_sum = loss_meter.get_sum()
             self.optimizer.zero_grad()
@@ -295,12 +353,14 @@ class TrainingModel:
 
 
 class _ClassModel(TrainingModel):
-    """The four semantic models: tooth_class_loss (cross entropy on label + 1, tgn_loss.py:355-367) of one output, weight 1."""
+    """The four semantic models: tooth_class_loss (cross entropy on label + 1, tgn_loss.py:355-367) of one output, weight 1.
+    val_terms names the terms of the test phase: the fixed schema a sharded validation (eval_sharded.ModelStep) reports under."""
 
     output_key, weight = "cls_pred", 1
+    val_terms = ("tooth_class_loss_1",)
 
     def get_loss(self, gt_seg_label_1, sem_1):
-        return {"tooth_class_loss_1": (eval_sharded.tooth_class_loss(sem_1, gt_seg_label_1), self.weight)}
+        return {"tooth_class_loss_1": (losses.tooth_class_loss(sem_1, gt_seg_label_1), self.weight)}
 
     def losses_of(self, output, seg_label, points):
         return self.get_loss(seg_label, output[self.output_key])
@@ -326,9 +386,9 @@ class TransformerModel(_ClassModel):
     tr_set.loss.tooth_class_loss_1; get_loss takes (sem_1, gt_seg_label_1), the reference's order for this model."""
     module_class, output_key = nets.PointTransformerModule, "sem_1"
 
-    def __init__(self, config, module=None):
+    def __init__(self, config, module=None, trainable=True):
         self.weight = config["tr_set"]["loss"]["tooth_class_loss_1"]
-        super().__init__(config, module)
+        super().__init__(config, module, trainable)
 
     def get_loss(self, sem_1, gt_seg_label_1):
         return super().get_loss(gt_seg_label_1, sem_1)
@@ -355,8 +415,8 @@ class FpsGroupingNetworkModel(TrainingModel):
         return [n for n in cls.CBL if config["tr_set"]["loss"].get(n, 0) != 0]
 
     @classmethod
-    def check_config(cls, config):
-        super().check_config(config)
+    def check_config(cls, config, trainable=True):
+        super().check_config(config, trainable)
         asked = cls.cbl_asked(config)
         if asked and not config["tr_set"].get("contrastive_boundary"):
             raise NotImplementedError(f"{cls.model_name}: the configuration weights {' and '.join(asked)}, and the contrastive-boundary terms are "
@@ -364,8 +424,8 @@ class FpsGroupingNetworkModel(TrainingModel):
                                       "cbl_loss_2 to 0 (or leave them out) to train on the five class, offset, direction and chamfer "
                                       "terms alone")
 
-    def __init__(self, config, module=None):
-        super().__init__(config, module)
+    def __init__(self, config, module=None, trainable=True):
+        super().__init__(config, module, trainable)
         self.contrast = bool(config["tr_set"].get("contrastive_boundary")) and bool(self.cbl_asked(config))
         for net in (self.module.first_ins_cent_model, self.module.second_ins_cent_model):
             net.fused_contrast = bool(config["tr_set"].get("contrastive_boundary_fused"))
@@ -396,8 +456,8 @@ class TSegNetModel(TrainingModel):
     module_class = nets.TSegNetModule
     WEIGHTS = {"dist_loss": 1, "cent_loss": 1, "chamf_loss": 0.1, "seg_1_loss": 1, "seg_2_loss": 1, "id_pred_loss": 1}
 
-    def __init__(self, config, module=None):
-        super().__init__(config, module)
+    def __init__(self, config, module=None, trainable=True):
+        super().__init__(config, module, trainable)
         self.skipped_segmentation = 0
         if config.get("pretrained_centroid_model_path") is not None:
             self.module.load_state_dict(torch.load(config["pretrained_centroid_model_path"] + ".h5"), strict=False)
@@ -552,8 +612,8 @@ class BoundarySampler:
 
 class BdlGroupingNetworkModel(FpsGroupingNetworkModel):
     """models/bdl_grouping_netowrk_model.py ("tgnet_bdl"): the two-stage GroupingNetworkModule of config["model_parameter"], trained on
-    BoundarySampler's inputs.  step() replaces the batch's feat / gt_seg_label with self.sampler.sample(batch_item) in every phase, then
-    runs tgnet_fps's step: the five terms, and cbl_loss_1 / cbl_loss_2 in the train phase under the same tr_set.contrastive_boundary rule.
+    BoundarySampler's inputs.  evaluate() replaces the batch's feat / gt_seg_label with self.sampler.sample(batch_item) in every phase, then
+    runs tgnet_fps's evaluate: the five terms, and cbl_loss_1 / cbl_loss_2 in the train phase under the same tr_set.contrastive_boundary rule.
 
     The base model -- base_model, or nets.GroupingNetworkModule(config["fps_model_info"]) loaded from
     fps_model_info.load_ckpt_path + ".h5" with strict=True -- is frozen: eval mode, requires_grad False, in neither the optimiser nor
@@ -563,16 +623,16 @@ class BdlGroupingNetworkModel(FpsGroupingNetworkModel):
     SECTIONS = ("boundary_sampling_info", "fps_model_info")
 
     @classmethod
-    def check_config(cls, config):
+    def check_config(cls, config, trainable=True):
         missing = [section for section in cls.SECTIONS if section not in config]
         if missing:
             raise NotImplementedError(f"tgnet_bdl trains on boundary-sampled inputs and the configuration has no {' and no '.join(missing)} "
                                       "section: boundary_sampling_info names the original meshes, their labels and the cache directory, "
                                       "fps_model_info the trained tgnet_fps module that finds the boundaries (train_configs/tgnet_bdl.py)")
-        super().check_config(config)
+        super().check_config(config, trainable)
 
-    def __init__(self, config, module=None, base_model=None):
-        super().__init__(config, module)
+    def __init__(self, config, module=None, base_model=None, trainable=True):
+        super().__init__(config, module, trainable)
         if base_model is None:
             base_model = nets.GroupingNetworkModule(config["fps_model_info"])
             base_model.load_state_dict(torch.load(config["fps_model_info"]["load_ckpt_path"] + ".h5"), strict=True)
@@ -583,21 +643,22 @@ class BdlGroupingNetworkModel(FpsGroupingNetworkModel):
         self.base_model = base_model
         self.sampler = BoundarySampler(config, base_model)
 
-    def step(self, batch_idx, batch_item, phase):
+    def evaluate(self, batch_item, phase):
         feat, gt_seg_label = self.sampler.sample(batch_item)
-        return super().step(batch_idx, dict(batch_item, feat=feat, gt_seg_label=gt_seg_label), phase)
+        return super().evaluate(dict(batch_item, feat=feat, gt_seg_label=gt_seg_label), phase)
 
 
 _MODELS = {"tgnet_fps": FpsGroupingNetworkModel, "tsegnet": TSegNetModel, "dgcnn": DGCnnModel, "pointnet": PointFirstModel,
            "pointnetpp": PointPpFirstModel, "pointtransformer": TransformerModel, "tgnet_bdl": BdlGroupingNetworkModel}
 
 
-def make_training_model(model_name, config):
+def make_training_model(model_name, config, trainable=True):
     """start_train.py:22-49: the step object of a model name.  Another name is ValueError; tgnet_bdl without its boundary_sampling_info
-    and fps_model_info sections is refused (NotImplementedError) before anything else in the configuration is looked at."""
+    and fps_model_info sections is refused (NotImplementedError) before anything else in the configuration is looked at.
+    trainable=False: TrainingModel's evaluate-only form."""
     if model_name not in _MODELS:
         raise ValueError(f"undefined model {model_name!r}: the names are {', '.join(MODEL_NAMES)}")
-    return _MODELS[model_name](config)
+    return _MODELS[model_name](config, trainable=trainable)
 
 
 # ---- the loop ---------------------------------------------------------------------------------------------------------------------------
