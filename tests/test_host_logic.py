@@ -435,6 +435,38 @@ def test_config_object_is_the_one_place_for_python_side_switches():
     assert fresh.fused_sa and fresh.sa_bf16x3 and fresh.knn_grid_min_points == 3000 and fresh.index_check == "sync"
 
 
+def test_fps_prefix_is_one_switch_in_the_config_object(monkeypatch):
+    """cfg.fps_prefix (None: the call site decides; True / False: forced) is what U.FPS_PREFIX and P.FPS_PREFIX read and write, and
+    TGN_FPS_PREFIX only seeds it; the two modules share fps.py's one book."""
+    from toothgroupnetwork_amd import config, fps, pointnet2_utils as U, pointops as P
+    c = config.cfg
+    assert config.Config().fps_prefix is None
+    assert U.FPS_PREFIX is c.fps_prefix and P.FPS_PREFIX is c.fps_prefix
+    keep = c.fps_prefix
+    try:
+        for writer, value in ((U, True), (P, False), (U, None), (P, True)):
+            writer.FPS_PREFIX = value                                   # a write through either alias is seen by the other two
+            assert U.FPS_PREFIX is value and P.FPS_PREFIX is value and c.fps_prefix is value
+        with config.override(fps_prefix=False):
+            assert U.FPS_PREFIX is False and P.FPS_PREFIX is False and c.fps_prefix is False
+        assert U.FPS_PREFIX is True and P.FPS_PREFIX is True and c.fps_prefix is True
+        with monkeypatch.context() as m:                                # what the GPU tests do
+            m.setattr(U, "FPS_PREFIX", None)
+            assert P.FPS_PREFIX is None and c.fps_prefix is None
+        assert P.FPS_PREFIX is True
+    finally:
+        c.fps_prefix = keep
+    monkeypatch.delenv("TGN_FPS_PREFIX", raising=False)
+    assert config.Config.from_env().fps_prefix is None
+    for env, want in (("", None), ("0", False), ("1", True), ("yes", True)):
+        monkeypatch.setenv("TGN_FPS_PREFIX", env)
+        assert config.Config.from_env().fps_prefix is want, env
+    assert P.fps_prefix_stats is U.fps_prefix_stats is fps.stats and fps.stats is fps.book.stats
+    assert fps.book.cap == 16
+    assert U._fps_dense is fps.sample_dense and P.fps_workspace is fps.workspace and P.fps_prefix_adopt is fps.adopt
+    assert P.fps_prefix_clear == U.fps_prefix_clear == fps.clear == fps.book.clear
+
+
 def test_tuning_table_round_trip_and_retired_keys_rejected():
     """tgn_set_tuning / tgn_get_tuning (include/tgn_pointops.h): host-side table, no GPU needed.  Known keys round-trip, the context
     manager restores, an unknown key -- a retired one included -- is an error (not silently a no-op)."""

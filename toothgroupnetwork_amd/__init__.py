@@ -4,6 +4,7 @@ Point-Transformer subtraction / aggregation operators).
 
     toothgroupnetwork_amd.pointops          mirror of external_libs/pointops/functions/pointops.py
     toothgroupnetwork_amd.pointnet2_utils   mirror of external_libs/pointnet2_utils/pointnet2_utils.py
+    toothgroupnetwork_amd.fps               the one Python front end of farthest-point sampling behind both, and its FPS-of-an-FPS-result book
     toothgroupnetwork_amd.resample          gen_utils.fps / resample_pcd (preprocess_data.py's FPS)
     toothgroupnetwork_amd.preprocess        preprocess_data.py / gen_utils.read_txt_obj_ls (OBJ -> 24 000-point .npy)
     toothgroupnetwork_amd.point_transformer mirrors of the cbl_point_transformer blocks (fused eval paths)

@@ -22,11 +22,14 @@ knn_grid_min_points   TGN_KNN_GRID_MIN       ... "large enough": average points 
 knn_cache_size        TGN_KNN_CACHE          entries of the kNN memo (blocks of one stage share their neighbour lists); 0 = off
 index_check           TGN_INDEX_CHECK        "sync": gather operators read their stream's index-error flag after the launch and
                                              raise IndexError like torch's advanced indexing; "off": no check, no synchronisation
+fps_prefix            TGN_FPS_PREFIX         the FPS-of-an-FPS-result shortcut (fps.py): None (unset or ""): the call site decides;
+                                             True / False ("0": False, anything else: True): forced on / off for every FPS call
 """
 import dataclasses
 import os
 import sys
 import types
+from typing import Optional
 
 
 def _flag(name, default="1"):
@@ -42,13 +45,16 @@ class Config:
     knn_grid_min_points: int = 3000
     knn_cache_size: int = 16
     index_check: str = "sync"
+    fps_prefix: Optional[bool] = None
 
     @classmethod
     def from_env(cls):
+        fps_prefix = os.environ.get("TGN_FPS_PREFIX", "")
         return cls(fused_sa=_flag("TGN_FUSED_SA"), commute_fp=_flag("TGN_COMMUTE_FP"), sa_bf16x3=_flag("TGN_SA_BF16X3"),
                    knn_grid=_flag("TGN_KNN_GRID"), knn_grid_min_points=int(os.environ.get("TGN_KNN_GRID_MIN", "3000")),
                    knn_cache_size=int(os.environ.get("TGN_KNN_CACHE", "16")),
-                   index_check=os.environ.get("TGN_INDEX_CHECK", "sync").lower())
+                   index_check=os.environ.get("TGN_INDEX_CHECK", "sync").lower(),
+                   fps_prefix=None if fps_prefix == "" else fps_prefix != "0")
 
 
 cfg = Config.from_env()

@@ -26,9 +26,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd import Function
 
-from . import _derived, _lib, config, fold
-from . import _fps_prefix
-from ._fps_prefix import PrefixBook
+from . import _derived, _lib, config, fold, fps
 from ._lib import as_int, f32c, ops, require_cuda, stream
 from .sa_fused import (fold_first_layer, fold_second_layer, pad16, sa_all_mlp2_max,  # noqa: F401
                        sa_first_layer, sa_level_max, sa_level_mlp2_max, sa_point_transform, split_point_transform, split_second_layer)
@@ -141,57 +139,12 @@ def index_points(points, idx):
 
 
 # ---------------------------------------------------------------------------------------------
-# FPS of an FPS result is the identity (include/tgn_pointops.h, tgn_furthestsampling_dense_prefix).  Every
-# set-abstraction level after the first samples the previous level's new_xyz (pointnet2_utils.py:160 /:276), so the
-# kernel that produced new_xyz also leaves a per-cloud certificate.  A later FPS whose input has the shape of a recent
-# result is offered that result and its certificate; the kernel compares the input with the stored coordinates bit for
-# bit, per cloud, and only then writes 0..S-1 instead of iterating -- provenance by content, nothing is assumed about
-# how the tensor travelled (module round trips, index_points(xyz, fps_idx), copies).  Opt-in per call site: the
-# set-abstraction modules in eval mode ask for it, the plain operators do not (TGN_FPS_PREFIX=1 / 0 forces it on / off).
+# farthest point sampling: fps.py, shared with pointops; the names of this module stay and FPS_PREFIX is cfg.fps_prefix (below).
+# The set-abstraction modules in eval mode ask for the FPS-of-an-FPS-result shortcut (prefix=True), the plain operators do not.
 # ---------------------------------------------------------------------------------------------
-FPS_PREFIX = _fps_prefix.FORCE     # None: opt-in per call site (the modules below); True / False: forced (TGN_FPS_PREFIX)
-_fps_book = PrefixBook()
-fps_prefix_stats = _fps_book.stats
-
-
-def fps_prefix_clear():
-    _fps_book.clear()
-
-
-# ---------------------------------------------------------------------------------------------
-# farthest point sampling
-# ---------------------------------------------------------------------------------------------
-def _fps_dense(xyz, npoint, want_coords=False, cuda_compat=False, prefix=False, mode=None):
-    """mode: explicit tie-order / contraction flag bits (None: the process-wide _lib.set_fps_mode() setting)."""
-    require_cuda(xyz)
-    npoint = as_int(npoint)
-    xyz = f32c(xyz.detach())
-    B, N, _ = xyz.shape
-    mode = _lib.fps_flags(cuda_compat) if mode is None else int(mode)
-    # prefix: this call site chains sampling levels (FPS of an FPS result is the identity); the tree tie order breaks it
-    use_prefix = _fps_prefix.use_prefix(prefix, FPS_PREFIX) and not (mode & _lib.FPS_TREE_TIES)
-    idx = torch.empty(B, npoint, dtype=torch.int64, device=xyz.device)
-    new_xyz = torch.empty(B, npoint, 3, dtype=torch.float32, device=xyz.device) if (want_coords or use_prefix) else None
-    if B == 0 or npoint == 0:
-        return idx, (new_xyz if want_coords else None)
-    from .pointops import fps_workspace
-    ws, nbytes = fps_workspace(B, N, B * N, xyz.device)
-    flags = _lib.FPS_LOCAL_INDEX | _lib.FPS_INDEX64 | mode
-    if nbytes == 0 and B >= 3 * torch.cuda.get_device_properties(xyz.device).multi_processor_count:
-        # three or more clouds per CU: the L2-resident form shares a CU between four workgroups and finishes the BATCH sooner
-        # (24 000 -> 4096: 10.9 against 12.7 us per scan at 768 scans, 9.7 at 1024; profiles/r06_fps_throughput.txt); same results
-        nbytes = int(ops().tgn_fps_throughput_workspace_bytes(B, N))
-        if nbytes:
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=xyz.device)
-            flags |= _lib.FPS_THROUGHPUT
-    cert_in = ref = cert_out = None
-    if use_prefix:
-        cert_in, ref = _fps_book.offer((B, N, mode), xyz.device)
-        cert_out = torch.empty(B, dtype=torch.int32, device=xyz.device)
-    ops().tgn_furthestsampling_dense_prefix(B, N, npoint, xyz, ws, nbytes, idx, new_xyz, cert_in, ref, cert_out, flags, stream())
-    if use_prefix:
-        _fps_book.record((B, npoint, mode), xyz.device, new_xyz, cert_out, shared=want_coords)
-    return idx, (new_xyz if want_coords else None)
+_fps_dense = fps.sample_dense
+fps_prefix_stats = fps.stats
+fps_prefix_clear = fps.clear
 
 
 def farthest_point_sample(xyz, npoint):
@@ -429,7 +382,7 @@ def three_interpolate(points2, dist, idx):
 # The switches of this module live in toothgroupnetwork_amd.config (cfg.fused_sa, cfg.commute_fp -- feature propagation: first
 # convolution on the coarse points, below --, cfg.sa_bf16x3 -- sa_fused.plan_branch).  FUSED_SA / COMMUTE_FP / SA_BF16X3 remain as
 # live aliases of those fields (reads and writes).
-config.legacy_attributes(__name__, {"FUSED_SA": "fused_sa", "COMMUTE_FP": "commute_fp", "SA_BF16X3": "sa_bf16x3"})
+config.legacy_attributes(__name__, {"FUSED_SA": "fused_sa", "COMMUTE_FP": "commute_fp", "SA_BF16X3": "sa_bf16x3", "FPS_PREFIX": "fps_prefix"})
 
 
 def _can_fuse(module, *tensors):

@@ -15,9 +15,7 @@ import torch
 from torch.autograd import Function
 from torch.utils.weak import WeakTensorKeyDictionary
 
-from . import _lib, config
-from . import _fps_prefix
-from ._fps_prefix import PrefixBook
+from . import _lib, config, fps
 from ._lib import as_int, f32c, idx32c, ops, require_cuda, stream
 
 _fwd = torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
@@ -84,71 +82,17 @@ def offsets_host(*offsets):
     return out
 
 
-def _max_segment(off_h):
-    n_max, prev = 0, 0
-    for v in off_h:
-        n_max = max(n_max, v - prev)
-        prev = v
-    return n_max
-
-
-def fps_workspace(b, n_max, n_total, device):
-    """Scratch for clouds that do not fit the register-resident FPS kernels (raw scans): the cell-sorted
-    workspace of the large-cloud kernel, or -- above its 262 144-point limit -- the reference's tmp array."""
-    if n_max <= ops().tgn_fps_resident_capacity():
-        return None, 0
-    nbytes = int(ops().tgn_fps_workspace_bytes(b, n_max))
-    nbytes = max(nbytes, 4 * int(n_total))
-    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
-
-
-FPS_PREFIX = _fps_prefix.FORCE     # None: opt-in per call site (fps_with_coords(prefix=True)); True / False: forced
-_fps_book = PrefixBook()
-fps_prefix_stats = _fps_book.stats
-
-
-def fps_prefix_clear():
-    _fps_book.clear()
-
-
-def fps_prefix_adopt(from_stream, to_stream):
-    """After `to_stream` has been made to wait for `from_stream`: FPS results recorded on the latter may serve the
-    FPS-of-an-FPS-result shortcut on the former (the side-stream sampling pyramid of the Point-Transformer U-Net)."""
-    _fps_book.adopt(from_stream.device, from_stream, to_stream)
+# Farthest-point sampling lives in fps.py (one front end and one book for the packed and the dense layout); the names of this
+# module stay.  cfg.fps_prefix is aliased as FPS_PREFIX below.
+fps_workspace = fps.workspace
+fps_prefix_stats = fps.stats
+fps_prefix_clear = fps.clear
+fps_prefix_adopt = fps.adopt
 
 
 def fps_with_coords(xyz, offset, new_offset, cuda_compat=False, prefix=False):
-    """furthestsampling that also returns the sampled coordinates xyz[idx] straight from the kernel
-    (what blocks.py:69-70 computes with a second gather).  Returns (idx int32 (m,), new_xyz (m,3)).
-    prefix=True: this call site chains sampling levels -- take part in the FPS-of-an-FPS-result shortcut."""
-    require_cuda(xyz, offset, new_offset)
-    xyz = f32c(xyz.detach(), "xyz")
-    off_h, noff_h = offsets_host(offset, new_offset)   # one device->host copy, or none (register_offsets)
-    offset, new_offset = idx32c(offset, "offset"), idx32c(new_offset, "new_offset")
-    b = offset.shape[0]
-    if b == 0 or noff_h[-1] == 0:      # nothing to sample (no segments, or only empty ones): an empty result, no launch
-        return (torch.zeros(0, dtype=torch.int32, device=xyz.device),
-                torch.zeros(0, 3, dtype=torch.float32, device=xyz.device))
-    n_max = _max_segment(off_h)
-    m = noff_h[-1]
-    idx = torch.empty(m, dtype=torch.int32, device=xyz.device)
-    new_xyz = torch.empty(m, 3, dtype=torch.float32, device=xyz.device)
-    ws, nbytes = fps_workspace(b, n_max, xyz.shape[0], xyz.device)
-    flags = _lib.fps_flags(cuda_compat)
-    # FPS of an FPS result is the identity (include/tgn_pointops.h).  The reference's transition-down chain gathers
-    # n_p = p[idx] itself (blocks.py:70) and samples n_p at the next level, so provenance is established by CONTENT:
-    # a previous result with the same segment layout is offered as prefix_ref and the kernel takes the shortcut for a
-    # cloud only if its coordinates equal that result bit for bit.
-    use_prefix = _fps_prefix.use_prefix(prefix, FPS_PREFIX) and not (flags & _lib.FPS_TREE_TIES)
-    cert_in = ref = cert_out = None
-    if use_prefix:
-        cert_in, ref = _fps_book.offer((tuple(off_h), xyz.shape[0], flags), xyz.device)
-        cert_out = torch.empty(b, dtype=torch.int32, device=xyz.device)
-    ops().tgn_furthestsampling_prefix(b, n_max, xyz, offset, new_offset, ws, nbytes, idx, new_xyz, cert_in, ref, cert_out, flags, stream())
-    if use_prefix:
-        _fps_book.record((tuple(noff_h), m, flags), xyz.device, new_xyz, cert_out, shared=True)
-    return idx, new_xyz
-
+    """fps.sample_packed with the host offsets from this module: one device->host copy, or none (register_offsets)."""
+    return fps.sample_packed(xyz, offset, new_offset, cuda_compat, prefix, host=offsets_host(offset, new_offset))
 
 
 class FurthestSampling(Function):
@@ -195,7 +139,8 @@ def _knn_raw(nsample, xyz, new_xyz, offset, new_offset):
 
 # cfg.knn_grid / cfg.knn_grid_min_points (average points per segment) / cfg.knn_cache_size: toothgroupnetwork_amd.config; the
 # module-level names of rounds 1-4 stay as live aliases
-config.legacy_attributes(__name__, {"KNN_GRID": "knn_grid", "KNN_GRID_MIN_POINTS": "knn_grid_min_points", "_KNN_CACHE_SIZE": "knn_cache_size"})
+config.legacy_attributes(__name__, {"KNN_GRID": "knn_grid", "KNN_GRID_MIN_POINTS": "knn_grid_min_points", "_KNN_CACHE_SIZE": "knn_cache_size",
+                                    "FPS_PREFIX": "fps_prefix"})
 
 
 # kNN memo.  The reference recomputes identical neighbour lists again and again: PointTransformerLayer calls
