@@ -441,6 +441,8 @@ int tgn_clear_index_error(tgn_stream_t stream);
  *   tgn_label_centroids: counts (b, nlab) int32 and cent (b, nlab, 3) float32 over the labels 0..nlab-1 (-1 = gingiva is skipped), cent
  *     bit-equal to numpy's xyz[label == t].mean(axis=0): a sequential float32 sum in point order divided by the count (NaN for an absent
  *     label).  1 <= nlab <= 64.  A label outside [-1, nlab) is ignored and latches bit 1 of the stream's error word (tgn_take_index_error).
+ *   tgn_label_centroids_f64: the same counts, and cent from a float64 sum in point order, divided by the count and rounded to float32
+ *     once: the mean itself to half an ulp, where the float32 sum above drifts with the number of points (the training losses' centroids).
  *   tgn_crop_knn: for crop t (centroid cent (t_total, 3), scan crop_scan[t]) the k nearest points of that scan, idx_out (t_total, k)
  *     int64, ascending in the float64 squared distance ((0 + dx*dx) + dy*dy) + dz*dz (dx = double(x) - double(cx), unfused: sklearn's
  *     euclidean rdist on KDTree's float64 copy), equal distances by ascending point index (KDTree leaves their order unspecified).
@@ -453,6 +455,8 @@ int tgn_clear_index_error(tgn_stream_t stream);
  */
 int tgn_label_centroids(int b, int n, int c_stride, const float *feats, const long long *labels, int nlab, int *counts, float *cent,
                         tgn_stream_t stream);
+int tgn_label_centroids_f64(int b, int n, int c_stride, const float *feats, const long long *labels, int nlab, int *counts, float *cent,
+                            tgn_stream_t stream);
 int tgn_crop_knn(int b, int n, int c_stride, const float *feats, int t_total, const int *crop_scan, const float *cent, int k,
                  long long *idx_out, tgn_stream_t stream);
 int tgn_crop_gather_center(int b, int n, int c, int t_total, int k, const float *feats, const int *crop_scan, const long long *idx,
@@ -539,7 +543,7 @@ int tgn_tsg_paint(int b, int n, int t_total, int k, const int *crop_scan, const 
  *
  *   tgn_offset_loss_forward: batch_center_offset_loss and batch_chamfer_distance_loss of tgnet_fps (models/tgn_loss.py:6-61, 263-302).
  *     labels (b, n) int64 in -1..15 (-1 = gingiva; another value counts as gingiva and latches bit 1 of the stream's error word),
- *     counts (b, 16) int32 and cent (b, 16, 3) the per-tooth point counts and centroids of tgn_label_centroids with nlab = 16.  A tooth
+ *     counts (b, 16) int32 and cent (b, 16, 3) the per-tooth point counts and centroids of tgn_label_centroids_f64 (or tgn_label_centroids) with nlab = 16.  A tooth
  *     is valid when its count is >= 5.  With m = p + o, c_t the centroid of the point's tooth:
  *       losses[0] = (sum over valid (s, t) of (sum_i |m_i - c_t|^2) / n_st) / #valid
  *       losses[1] = (sum over valid (s, t) with k_st > 0 of (sum over kept i of (d_i . o_i/|o_i| - 1)^2) / k_st) / #those,

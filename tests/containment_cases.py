@@ -623,6 +623,8 @@ def _centroid_build(shape):
 
 row("tgn_label_centroids", ["tgn_label_centroids"], _CROP, _centroid_build,
     lambda s: lambda L, v, st: L.tgn_label_centroids(s[0], s[1], 6, P(v["feats"]), P(v["labels"]), s[2], P(v["counts"]), P(v["cent"]), st))
+row("tgn_label_centroids_f64", ["tgn_label_centroids_f64"], _CROP, _centroid_build,
+    lambda s: lambda L, v, st: L.tgn_label_centroids_f64(s[0], s[1], 6, P(v["feats"]), P(v["labels"]), s[2], P(v["counts"]), P(v["cent"]), st))
 
 
 def _crop_common(g, b, n, t):

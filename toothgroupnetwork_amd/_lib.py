@@ -118,6 +118,7 @@ SIGNATURES = {
     "tgn_clear_index_error": (c_int, [_P]),
     "tgn_square_distance": (c_int, [c_int, c_int, c_int, _P, _P, _P, _P]),
     "tgn_label_centroids": (c_int, [c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P]),
+    "tgn_label_centroids_f64": (c_int, [c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P]),
     "tgn_crop_knn": (c_int, [c_int, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P]),
     "tgn_crop_gather_center": (c_int, [c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
     "tgn_dbscan_workspace_bytes": (c_size_t, [c_int, c_int]),

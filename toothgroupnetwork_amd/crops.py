@@ -89,15 +89,17 @@ def crop_knn(feats, scan, cent, k):
     return idx
 
 
-def label_centroids(feats, labels, nlab):
+def label_centroids(feats, labels, nlab, f64_sum=False):
     """feats (B, C >= 3, N) float32 and labels (B, N) int64, contiguous -> (counts (B, nlab) int32, cent (B, nlab, 3) float32): per scan
-    and label 0..nlab-1 its point count and float32 mean, bit-equal to numpy's xyz[label == t].mean(axis=0).  -1 is skipped; another label
-    outside [0, nlab) latches _lib.INDEX_ERROR_CROP, which is neither cleared nor read here.  No synchronisation."""
+    and label 0..nlab-1 its point count and float32 mean, bit-equal to numpy's xyz[label == t].mean(axis=0); with f64_sum the mean of a
+    float64 sum rounded once (tgn_label_centroids_f64: the mean to half an ulp however many points a label has).  -1 is skipped; another
+    label outside [0, nlab) latches _lib.INDEX_ERROR_CROP, which is neither cleared nor read here.  No synchronisation."""
     _operand(feats, "feats", torch.float32), _operand(labels, "labels", torch.int64)
     B, C, N = feats.shape
     counts = torch.empty(B, nlab, dtype=torch.int32, device=feats.device)
     cent = torch.empty(B, nlab, 3, dtype=torch.float32, device=feats.device)
-    _lib.ops().tgn_label_centroids(B, N, C, feats, labels, nlab, counts, cent, _lib.stream())
+    launch = _lib.ops().tgn_label_centroids_f64 if f64_sum else _lib.ops().tgn_label_centroids
+    launch(B, N, C, feats, labels, nlab, counts, cent, _lib.stream())
     return counts, cent
 
 

@@ -2,6 +2,7 @@
 // (models/modules/grouping_network_module.py:45-72): label centroids, the k nearest points of every centroid, the centred crops.
 // The reference does this on the host (numpy means, an sklearn KDTree, python gathers); these kernels reproduce its results:
 //   tgn_label_centroids     numpy's xyz[label == t].mean(axis=0): a sequential float32 sum in point order, divided by the count
+//   tgn_label_centroids_f64 the same mean from a float64 sum, rounded once: for consumers that want the mean, not numpy's bits
 //   tgn_crop_knn            KDTree.query(k) order: ascending float64 squared distance, equal distances by ascending index
 //   tgn_crop_gather_center  feats[b][:, idx] with xyz centred by a float64 mean rounded once (ops_utils.centering_object)
 // Inputs the kernels cannot trust (labels, scan numbers, crop indices) latch bit 1 of the launch stream's error word
@@ -14,9 +15,11 @@ namespace tgn {
 // One workgroup per scan walks the scan in chunks of kCentThreads points.  Per chunk: a stable counting sort of the chunk's points by
 // label into LDS (ballot per label and wave; the rank inside a wave is mbcnt, so point order is kept within a label), then lane
 // (label, axis) adds that label's coordinates of the chunk, in point order, to its running float32 sum.  The dependent chain of a
-// label is its point count; no lane scans points of other labels.
+// label is its point count; no lane scans points of other labels.  Acc = float is numpy's sum; Acc = double (tgn_label_centroids_f64)
+// keeps the sum exact to 2^-53 of its terms and rounds the mean once: a float32 sum of n terms drifts by about sqrt(n) roundings.
 constexpr int kCentThreads = 1024, kCentWaves = kCentThreads / kWave, kCentMaxLab = 64;
 
+template <typename Acc>
 __global__ void __launch_bounds__(kCentThreads) label_centroids_kernel(int n, int c_stride, const float *__restrict__ feats,
                                                                        const long long *__restrict__ labels, int nlab,
                                                                        int *__restrict__ counts, float *__restrict__ cent,
@@ -30,7 +33,7 @@ __global__ void __launch_bounds__(kCentThreads) label_centroids_kernel(int n, in
     const long long *L = labels + (long long)b * n;
     const int my_l = tid / 3, my_ax = tid % 3;          // summing lanes: tid < 3 * nlab
     const bool summer = tid < 3 * nlab;
-    float acc = 0.0f;
+    Acc acc = 0;
     int total = 0;
     bool bad_seen = false;
     for (int base = 0; base < n; base += kCentThreads) {
@@ -77,14 +80,14 @@ __global__ void __launch_bounds__(kCentThreads) label_centroids_kernel(int n, in
         __syncthreads();
         if (summer) {
             const int lo = s_lbase[my_l], hi = s_lbase[my_l + 1];
-            for (int p = lo; p < hi; ++p) acc = acc + s_xyz[my_ax][p];
+            for (int p = lo; p < hi; ++p) acc = acc + (Acc)s_xyz[my_ax][p];
             total += hi - lo;
         }
         __syncthreads();
     }
     if (__any(bad_seen) && lane == 0 && err) atomicOr(err, kIndexErrCrop);
     if (summer) {
-        cent[((long long)b * nlab + my_l) * 3 + my_ax] = acc / (float)total;   // 0 / 0 = NaN for an absent label, as numpy's mean
+        cent[((long long)b * nlab + my_l) * 3 + my_ax] = (float)(acc / (Acc)total);   // 0 / 0 = NaN for an absent label, as numpy's mean
         if (my_ax == 0) counts[(long long)b * nlab + my_l] = total;
     }
 }
@@ -171,6 +174,13 @@ __global__ void __launch_bounds__(kKnnThreads) crop_knn_kernel(int nscan, int n,
         s_eqbase = 0;
     }
     __syncthreads();
+    // Three barriers per chunk.  Before the first: the slot counter's atomics and the per-wave tie counts.  Between the first and the
+    // second: every thread takes s_slot into `filled` -- final for this chunk, since the chunk's atomics are behind the first barrier
+    // and the next chunk's come after the third -- and places its tie from s_eqbase as the previous chunk left it.  Between the second
+    // and the third: thread 0 alone advances s_eqbase, which is next written two barriers after the third.  The exit test after the
+    // third barrier therefore reads the same two values in every thread: the exit is uniform.  (Reading s_slot itself there is not:
+    // a wave already in the next chunk may be raising it to nless while a slower wave still reads, and the two would leave the loop
+    // one chunk apart, with their barriers mispaired through the whole sort below.)
     for (int base = 0; base < n; base += kKnnThreads) {   // index order: the ties kept are the lowest-index ones
         const int i = base + tid;
         const unsigned long long key = i < n ? crop_key(X, n, i, cx, cy, cz) : ~0ull;
@@ -184,6 +194,7 @@ __global__ void __launch_bounds__(kKnnThreads) crop_knn_kernel(int nscan, int n,
         if (lane == 0) s_weq[wave] = __popcll(m);
         __syncthreads();
         int before = s_eqbase;
+        const int filled = s_slot;
         for (int w = 0; w < wave; ++w) before += s_weq[w];
         if (eq) {
             const int r = before + mbcnt(m);
@@ -199,7 +210,7 @@ __global__ void __launch_bounds__(kKnnThreads) crop_knn_kernel(int nscan, int n,
             s_eqbase += all;
         }
         __syncthreads();
-        if (s_eqbase >= need_eq && s_slot >= nless) break;   // uniform: every slot filled
+        if (s_eqbase >= need_eq && filled >= nless) break;   // every slot filled
     }
     int P = 1;
     while (P < k) P <<= 1;
@@ -284,21 +295,32 @@ __global__ void __launch_bounds__(kGatherThreads) crop_gather_center_kernel(
 
 using namespace tgn;
 
-TGN_API int tgn_label_centroids(int b, int n, int c_stride, const float *feats, const long long *labels, int nlab, int *counts,
-                                float *cent, tgn_stream_t stream) {
+template <typename Acc>
+static int launch_label_centroids(const char *who, int b, int n, int c_stride, const float *feats, const long long *labels, int nlab,
+                                  int *counts, float *cent, tgn_stream_t stream) {
     if (b < 1 || n < 1 || c_stride < 3 || nlab < 1 || nlab > kCentMaxLab || !feats || !labels || !counts || !cent) {
-        set_error("tgn_label_centroids: bad arguments (b=%d n=%d c_stride=%d nlab=%d; need b, n >= 1, c_stride >= 3, 1 <= nlab <= %d, "
-                  "non-NULL pointers)", b, n, c_stride, nlab, kCentMaxLab);
+        set_error("%s: bad arguments (b=%d n=%d c_stride=%d nlab=%d; need b, n >= 1, c_stride >= 3, 1 <= nlab <= %d, "
+                  "non-NULL pointers)", who, b, n, c_stride, nlab, kCentMaxLab);
         return TGN_ERR_INVALID_ARGUMENT;
     }
     int *err = index_error_word((hipStream_t)stream);
     if (!err) {
-        set_error("tgn_label_centroids: cannot allocate the error word");
+        set_error("%s: cannot allocate the error word", who);
         return TGN_ERR_LAUNCH;
     }
-    hipLaunchKernelGGL(label_centroids_kernel, dim3(b), dim3(kCentThreads), 0, (hipStream_t)stream, n, c_stride, feats, labels, nlab,
+    hipLaunchKernelGGL(label_centroids_kernel<Acc>, dim3(b), dim3(kCentThreads), 0, (hipStream_t)stream, n, c_stride, feats, labels, nlab,
                        counts, cent, err);
-    return check_launch("tgn_label_centroids");
+    return check_launch(who);
+}
+
+TGN_API int tgn_label_centroids(int b, int n, int c_stride, const float *feats, const long long *labels, int nlab, int *counts,
+                                float *cent, tgn_stream_t stream) {
+    return launch_label_centroids<float>("tgn_label_centroids", b, n, c_stride, feats, labels, nlab, counts, cent, stream);
+}
+
+TGN_API int tgn_label_centroids_f64(int b, int n, int c_stride, const float *feats, const long long *labels, int nlab, int *counts,
+                                    float *cent, tgn_stream_t stream) {
+    return launch_label_centroids<double>("tgn_label_centroids_f64", b, n, c_stride, feats, labels, nlab, counts, cent, stream);
 }
 
 TGN_API int tgn_crop_knn(int b, int n, int c_stride, const float *feats, int t_total, const int *crop_scan, const float *cent,

@@ -61,7 +61,9 @@ class _TgnOffsetLosses(Function):
     def forward(ctx, pred_offset, sample_xyz, labels):
         B, _, N = pred_offset.shape
         L, dev = _lib.ops(), pred_offset.device
-        counts, cent = crops.label_centroids(sample_xyz, labels, crops.NUM_LABELS)
+        # the float64-summed mean: numpy's float32 sum is off by about sqrt(points of the tooth) roundings, which the gradients
+        # 2 (m - c) see magnified by |c| / |m - c| (the reference takes torch's mean, a tree sum)
+        counts, cent = crops.label_centroids(sample_xyz, labels, crops.NUM_LABELS, f64_sum=True)
         losses = torch.empty(3, dtype=torch.float32, device=dev)
         scales = torch.empty(B, _SCALES, dtype=torch.float32, device=dev)
         ws_bytes = L.tgn_offset_loss_workspace_bytes(B, N)
