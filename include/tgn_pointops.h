@@ -231,7 +231,8 @@ int tgn_aggregation_backward(int n, int nsample, int c, int w_c, const float *in
  *   neighbours of logit (n,nsample,g) -> sm (kept for backward), out[n,ch] = sum_j (x_v[idx[n,j],ch] + p_r[n,j,ch]) *
  *   sm[n,j,ch % g]; the backward writes grad_pr (n,nsample,c), grad_logit (n,nsample,g) and ACCUMULATES into grad_xv
  *   (n_v,c; pre-zeroed).  This is the reference's `aggregation` (aggregation_cuda_kernel.cu:5-39) with the softmax
- *   fused in front.
+ *   fused in front.  grad_xv == NULL: the scatter is left out (a kernel instantiation without it) and nothing is written for it;
+ *   the caller sums grad_pr along reverse lists instead (tgn_scatter_ordered below).
  */
 int tgn_pt_attention_forward(int n, int nsample, int c, int g, const float *p, const float *xq, const float *xk,
                              const float *xv, const int *idx, const float *Wp1, const float *bp1, const float *Wp2,
@@ -243,6 +244,36 @@ int tgn_pt_softmax_aggregate_forward(int n, int nsample, int c, int g, const flo
 int tgn_pt_softmax_aggregate_backward(int n, int nsample, int c, int g, const float *xv, const float *pr, const float *sm,
                                       const int *idx, const float *grad_out, float *grad_xv, float *grad_pr,
                                       float *grad_logit, tgn_stream_t stream);
+
+/*
+ * The gather family's backward without float atomics (csrc/scatter_ordered.hip): a scatter-add out[idx[q]] += term(q) turned
+ * round, so that one lane group owns an output row and adds that row's terms in a fixed order.  The same inputs give the same
+ * bits.  Both calls launch on `stream` and neither allocate, copy, nor synchronise: they can be captured in a graph.
+ *
+ *   tgn_reverse_lists: idx holds b * pairs_per_batch indices (int32, or int64 with idx_is64); pair q = bi * pairs_per_batch + t
+ *     targets row bi * n + idx[q]; an index outside [0, n) counts as row 0 of its batch.  rev_start (b * n + 1) and rev_pair
+ *     (b * pairs_per_batch) int32: rev_pair[rev_start[r] .. rev_start[r + 1]) holds the pair numbers that target row r in ascending
+ *     order, rev_start[b * n] = b * pairs_per_batch.  The packed operators call it with b = 1, the dense layout with its B, N and
+ *     S * K.  Every entry of both outputs is written; `ws` (device memory, at least tgn_reverse_lists_workspace_bytes bytes, any
+ *     contents) is free again when the call has run.  b * n and b * pairs_per_batch must be below 2^31 (else
+ *     TGN_ERR_INVALID_ARGUMENT with a message, and the size function returns 0).  Integer atomics only; a segment longer than 64
+ *     pairs is sorted by one workgroup in len^2 / 256 steps per thread: slow for a row that very many pairs target, bounded, exact.
+ *
+ *   tgn_scatter_ordered: out (n_rows, c); out[r][ch] is the float32 sum, starting from +0.0f and taken sequentially in list order
+ *     over the pairs q of row r, of term(q, ch); every term is rounded to float32 before it is added and nothing is contracted.
+ *       coef == NULL (pair rows):   term = sign * src[q * c + ch]                                  src (pairs, c)
+ *       coef != NULL (query rows):  term = (sign * src[(q / k) * c + ch]) * coef[q * g + ch % g]   src (pairs / k, c), coef (pairs, g),
+ *                                                                                                   g dividing c
+ *     sign is +1 or -1, k >= 1.  The pairs of row r are rev_pair[rev_start[r] .. rev_start[r + 1]) -- lists as tgn_reverse_lists
+ *     writes them; they are trusted: an entry is a pair number of src / coef -- or, with rev_start == NULL and rev_pair == NULL,
+ *     the identity segments r * k .. r * k + k - 1.  Every element of out is written (a row without pairs gets +0.0f): the caller
+ *     does not pre-zero it.
+ */
+size_t tgn_reverse_lists_workspace_bytes(int b, int n, long long pairs_per_batch);
+int tgn_reverse_lists(int b, int n, long long pairs_per_batch, const void *idx, int idx_is64, int *rev_start, int *rev_pair,
+                      void *ws, size_t ws_bytes, tgn_stream_t stream);
+int tgn_scatter_ordered(long long n_rows, int c, int k, int g, const int *rev_start, const int *rev_pair, const float *src,
+                        const float *coef, float sign, float *out, tgn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * 3. pointnet2_utils operators as single kernels (dense (B,N,*) layout).

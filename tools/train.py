@@ -12,7 +12,9 @@ reference's own train_configs/*.py files work as they are.  tr_set.contrastive_b
 on the cbl_loss_1 / cbl_loss_2 weights its file names (losses.contrast_boundary_loss); --no_contrastive_boundary leaves the key
 out, and a non-zero cbl weight is then refused (training.py).  --fused_contrastive_boundary sets tr_set.contrastive_boundary_fused:
 the criterion's stages run as the fused kernels of csrc/cbl.hip (no (m, K-1, 32) difference tensor, a bit-reproducible gradient;
-off by default).  tgnet_bdl (train_configs/tgnet_bdl.py with its four paths edited)
+off by default).  --ordered_backward sets tr_set.ordered_backward, which switches config.cfg.ordered_backward on: every gradient that
+flows through a neighbour list is summed along reverse lists instead of with float atomics (ordered.py; off by default; the
+BatchNorm kernels' float64 atomics remain).  tgnet_bdl (train_configs/tgnet_bdl.py with its four paths edited)
 trains tgnet's boundary module from a tgnet_fps checkpoint: see training.BoundarySampler for the three directories it needs.
 Prints the trainer's JSON lines: one per scheduler step, one per epoch.  Checkpoints: ckpts/<experiment_name>.h5 after every epoch,
 ckpts/<experiment_name>_val.h5 at every best validation total; both load into inference.make_inference_pipeline."""
@@ -58,6 +60,8 @@ def main(argv=None):
                     help="do not set tr_set.contrastive_boundary: tgnet_fps then refuses non-zero cbl_loss_1 / cbl_loss_2 weights")
     ap.add_argument("--fused_contrastive_boundary", action="store_true",
                     help="set tr_set.contrastive_boundary_fused: tgnet_fps / tgnet_bdl compute the criterion with the fused stage kernels")
+    ap.add_argument("--ordered_backward", action="store_true",
+                    help="set tr_set.ordered_backward: the gather family's backward without float atomics (config.cfg.ordered_backward)")
     args = ap.parse_args(argv)
 
     import numpy as np
@@ -72,6 +76,8 @@ def main(argv=None):
         config["tr_set"].setdefault("contrastive_boundary", True)
     if args.fused_contrastive_boundary and "tr_set" in config:
         config["tr_set"]["contrastive_boundary_fused"] = True
+    if args.ordered_backward:
+        config.setdefault("tr_set", {})["ordered_backward"] = True
     model = training.make_training_model(args.model_name, config)
     gen_set = [training.get_generator_set(config["generator"])]
     print("train_set", len(gen_set[0][0]), file=sys.stderr)

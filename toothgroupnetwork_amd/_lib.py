@@ -81,6 +81,9 @@ SIGNATURES = {
     "tgn_pt_attention_forward": (c_int, [c_int, c_int, c_int, c_int] + [_P] * 18 + [_P]),
     "tgn_pt_softmax_aggregate_forward": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
     "tgn_pt_softmax_aggregate_backward": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "tgn_reverse_lists_workspace_bytes": (c_size_t, [c_int, c_int, ctypes.c_longlong]),
+    "tgn_reverse_lists": (c_int, [c_int, c_int, ctypes.c_longlong, _P, c_int, _P, _P, _P, c_size_t, _P]),
+    "tgn_scatter_ordered": (c_int, [ctypes.c_longlong, c_int, c_int, c_int, _P, _P, _P, _P, c_float, _P, _P]),
     # section 3
     "tgn_ball_query_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "tgn_ball_query": (c_int, [c_int, c_int, c_int, c_int, c_float, _P, _P, _P, c_int, _P, c_size_t, _P]),

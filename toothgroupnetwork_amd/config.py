@@ -24,6 +24,10 @@ index_check           TGN_INDEX_CHECK        "sync": gather operators read their
                                              raise IndexError like torch's advanced indexing; "off": no check, no synchronisation
 fps_prefix            TGN_FPS_PREFIX         the FPS-of-an-FPS-result shortcut (fps.py): None (unset or ""): the call site decides;
                                              True / False ("0": False, anything else: True): forced on / off for every FPS call
+ordered_backward      TGN_ORDERED_BACKWARD   the gather family's backward (grouping, queryandgroup, subtraction, interpolation, the
+                      =0/1, default 0        Point-Transformer tail, index_points / group_points / three_interpolate) along reverse
+                                             lists instead of float atomics (ordered.py): the same bits every time.  Read at call time
+                                             in each backward.  Off: the atomic kernels, unchanged
 """
 import dataclasses
 import os
@@ -46,6 +50,7 @@ class Config:
     knn_cache_size: int = 16
     index_check: str = "sync"
     fps_prefix: Optional[bool] = None
+    ordered_backward: bool = False
 
     @classmethod
     def from_env(cls):
@@ -54,7 +59,8 @@ class Config:
                    knn_grid=_flag("TGN_KNN_GRID"), knn_grid_min_points=int(os.environ.get("TGN_KNN_GRID_MIN", "3000")),
                    knn_cache_size=int(os.environ.get("TGN_KNN_CACHE", "16")),
                    index_check=os.environ.get("TGN_INDEX_CHECK", "sync").lower(),
-                   fps_prefix=None if fps_prefix == "" else fps_prefix != "0")
+                   fps_prefix=None if fps_prefix == "" else fps_prefix != "0",
+                   ordered_backward=_flag("TGN_ORDERED_BACKWARD", "0"))
 
 
 cfg = Config.from_env()

@@ -198,6 +198,9 @@ __global__ __launch_bounds__(256) void pt_softmax_aggregate_fwd_kernel(int n, in
 //   d_xv[idx,ch]  += go[n,ch] * sm[n,j,g]                                   (atomic scatter)
 //   d_sm[n,j,g]    = sum_{ch % g_ == g} go[n,ch] * (xv[idx,ch] + pr[n,j,ch])
 //   d_logit[n,j,g] = sm[n,j,g] * (d_sm[n,j,g] - sum_j' sm[n,j',g] * d_sm[n,j',g])
+// SCATTER = false leaves the d_xv scatter out (d_xv is not touched): the caller sums d_pr along reverse lists instead
+// (scatter_ordered.hip).
+template <bool SCATTER>
 __global__ __launch_bounds__(256) void pt_softmax_aggregate_bwd_kernel(int n, int nsample, int c, int g_,
                                                                         const float *__restrict__ xv,
                                                                         const float *__restrict__ pr,
@@ -247,7 +250,7 @@ __global__ __launch_bounds__(256) void pt_softmax_aggregate_bwd_kernel(int n, in
                             if (in) {
                                 const float w = gch * srow[j * g_ + g];
                                 d_pr[((size_t)pt * nsample + j) * c + ch] = w;
-                                atomicAdd(d_xv + (size_t)nb * c + ch, w);
+                                if (SCATTER) atomicAdd(d_xv + (size_t)nb * c + ch, w);
                             }
                             float t = gch * (a[u] + b[u]);
                             for (int off = g_; off < 64; off <<= 1) t += __shfl_xor(t, off);
@@ -264,7 +267,7 @@ __global__ __launch_bounds__(256) void pt_softmax_aggregate_bwd_kernel(int n, in
                 const int nb = idx[(size_t)pt * nsample + j];
                 const float w = gch * srow[j * g_ + g];
                 d_pr[((size_t)pt * nsample + j) * c + ch] = w;
-                atomicAdd(d_xv + (size_t)nb * c + ch, w);
+                if (SCATTER) atomicAdd(d_xv + (size_t)nb * c + ch, w);
             }
         }
         // d_sm: lanes over (j, g) pairs, each sums its share_planes channels
@@ -354,7 +357,7 @@ TGN_API int tgn_pt_softmax_aggregate_backward(int n, int nsample, int c, int g, 
                                               const float *sm, const int *idx, const float *grad_out, float *grad_xv,
                                               float *grad_pr, float *grad_logit, tgn_stream_t stream) {
     if (n <= 0) return TGN_OK;
-    if (!xv || !pr || !sm || !idx || !grad_out || !grad_xv || !grad_pr || !grad_logit || nsample < 1 || g < 1 || c % g) {
+    if (!xv || !pr || !sm || !idx || !grad_out || !grad_pr || !grad_logit || nsample < 1 || g < 1 || c % g) {
         set_error("tgn_pt_softmax_aggregate_backward: bad argument");
         return TGN_ERR_INVALID_ARGUMENT;
     }
@@ -365,7 +368,9 @@ TGN_API int tgn_pt_softmax_aggregate_backward(int n, int nsample, int c, int g, 
     }
     long long blocks = ((long long)n + 3) / 4;
     if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(pt_softmax_aggregate_bwd_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, n, nsample, c,
-                       g, xv, pr, sm, idx, grad_out, grad_xv, grad_pr, grad_logit);
+    dispatch_bool(grad_xv != nullptr, [&](auto scatter) {
+        hipLaunchKernelGGL((pt_softmax_aggregate_bwd_kernel<decltype(scatter)::value>), dim3((unsigned)blocks), dim3(256), lds,
+                           (hipStream_t)stream, n, nsample, c, g, xv, pr, sm, idx, grad_out, grad_xv, grad_pr, grad_logit);
+    });
     return check_launch("pt_softmax_aggregate_bwd_kernel");
 }

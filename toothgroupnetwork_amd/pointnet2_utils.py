@@ -26,7 +26,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd import Function
 
-from . import _derived, _lib, config, fold, fps
+from . import _derived, _lib, config, fold, fps, ordered
 from ._lib import as_int, f32c, ops, require_cuda, stream
 from .sa_fused import (fold_first_layer, fold_second_layer, pad16, sa_all_mlp2_max,  # noqa: F401
                        sa_first_layer, sa_level_max, sa_level_mlp2_max, sa_point_transform, split_point_transform, split_second_layer)
@@ -119,6 +119,8 @@ class _IndexPoints(Function):
         idx, = ctx.saved_tensors
         B, N, M, C = ctx.shape
         g = g.contiguous().float()
+        if config.cfg.ordered_backward:
+            return ordered.scatter(g.view(B * M, C), B * N, ordered.reverse_lists(idx, N, B, wrap=True)).view(B, N, C), None
         grad = torch.zeros(B, N, C, dtype=torch.float32, device=g.device)
         ops().tgn_scatter_add_points(B, N, M, C, g, idx, int(idx.dtype == torch.int64), grad, stream())
         return grad, None
@@ -244,6 +246,16 @@ class _GroupPoints(Function):
         g_rel = (g[..., :3] if xyz_first else g[..., D:]).contiguous()
         is64 = int(idx.dtype == torch.int64)
         g_xyz = g_new = g_pts = None
+        if config.cfg.ordered_backward:
+            lists = ordered.reverse_lists(idx, N, B, wrap=True)
+            if ctx.needs_input_grad[0]:
+                g_xyz = ordered.scatter(g_rel.view(B * S * K, 3), B * N, lists).view(B, N, 3)
+            if ctx.needs_input_grad[1]:
+                g_new = -g_rel.sum(2)
+            if D and ctx.needs_input_grad[2]:
+                g_f = (g[..., 3:] if xyz_first else g[..., :D]).contiguous()
+                g_pts = ordered.scatter(g_f.view(B * S * K, D), B * N, lists).view(B, N, D)
+            return g_xyz, g_new, g_pts, None, None
         if ctx.needs_input_grad[0]:
             g_xyz = torch.zeros(B, N, 3, dtype=torch.float32, device=g.device)
             ops().tgn_scatter_add_points(B, N, S * K, 3, g_rel, idx, is64, g_xyz, stream())
@@ -329,6 +341,9 @@ class _ThreeInterpolate(Function):
         idx, weight = ctx.saved_tensors
         B, N, S, C = ctx.dims
         g = g.contiguous().float()
+        if config.cfg.ordered_backward:
+            grad = ordered.scatter(g.view(B * N, C), B * S, ordered.reverse_lists(idx, S, B), coef=weight.view(B * N * 3, 1), k=3)
+            return grad.view(B, S, C), None, None
         # global row indices into the flattened (B*S, C) support features
         gidx = (idx + (torch.arange(B, device=idx.device, dtype=idx.dtype) * S).view(B, 1, 1)).to(torch.int32)
         grad = torch.zeros(B * S, C, dtype=torch.float32, device=g.device)

@@ -15,7 +15,7 @@ import torch
 from torch.autograd import Function
 from torch.utils.weak import WeakTensorKeyDictionary
 
-from . import _lib, config, fps
+from . import _lib, config, fps, ordered
 from ._lib import as_int, f32c, idx32c, ops, require_cuda, stream
 
 _fwd = torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
@@ -236,6 +236,8 @@ class Grouping(Function):
         idx, = ctx.saved_tensors
         grad_output = grad_output.contiguous().float()
         m, nsample, c = grad_output.shape
+        if config.cfg.ordered_backward:
+            return ordered.scatter(grad_output.view(m * nsample, c), n, ordered.reverse_lists(idx, n)), None
         grad_input = torch.zeros(n, c, dtype=torch.float32, device=grad_output.device)
         ops().tgn_grouping_backward(m, nsample, c, grad_output, idx, grad_input, stream())
         return grad_input, None
@@ -283,6 +285,17 @@ class _QueryGroup(Function):
         n = ctx.n
         grad_out = grad_out.contiguous().float()
         g_xyz = g_new = None
+        if config.cfg.ordered_backward:
+            lists = ordered.reverse_lists(idx, n)
+            g_feat = grad_out
+            if ctx.use_xyz:
+                g_rel = grad_out[:, :, :3].contiguous().view(m * nsample, 3)
+                g_feat = grad_out[:, :, 3:].contiguous()
+                if ctx.needs_input_grad[0]:
+                    g_xyz = ordered.scatter(g_rel, n, lists)
+                if ctx.needs_input_grad[1]:
+                    g_new = ordered.scatter(g_rel, m, None, k=nsample, sign=-1.0)
+            return g_xyz, g_new, ordered.scatter(g_feat.view(m * nsample, g_feat.shape[2]), n, lists), None, None
         if ctx.use_xyz:
             g_rel = grad_out[:, :, :3].contiguous()
             g_feat = grad_out[:, :, 3:].contiguous()
@@ -354,6 +367,10 @@ class Subtraction(Function):
         idx, = ctx.saved_tensors
         grad_output = grad_output.contiguous().float()
         n, nsample, c = grad_output.shape
+        if config.cfg.ordered_backward:
+            pair_rows = grad_output.view(n * nsample, c)
+            return (ordered.scatter(pair_rows, n, None, k=nsample),
+                    ordered.scatter(pair_rows, ctx.n2, ordered.reverse_lists(idx, ctx.n2), sign=-1.0), None)
         grad_input1 = torch.zeros(n, c, dtype=torch.float32, device=grad_output.device)
         grad_input2 = torch.zeros(ctx.n2, c, dtype=torch.float32, device=grad_output.device)
         ops().tgn_subtraction_backward(n, nsample, c, idx, grad_output, grad_input1, grad_input2, stream())
@@ -440,6 +457,8 @@ class _WeightedGather(Function):
         grad_output = grad_output.contiguous().float()
         n, c = grad_output.shape
         k = idx.shape[1]
+        if config.cfg.ordered_backward:
+            return ordered.scatter(grad_output, ctx.m, ordered.reverse_lists(idx, ctx.m), coef=weight.view(n * k, 1), k=k), None, None
         grad_input = torch.zeros(ctx.m, c, dtype=torch.float32, device=grad_output.device)
         ops().tgn_interpolation_backward(n, c, k, grad_output, idx, weight, grad_input, stream())
         return grad_input, None, None
@@ -486,6 +505,8 @@ class Interpolation(Function):
         idx, weight = ctx.saved_tensors
         grad_output = grad_output.contiguous().float()
         n, c = grad_output.shape
+        if config.cfg.ordered_backward:
+            return None, None, ordered.scatter(grad_output, m, ordered.reverse_lists(idx, m), coef=weight.view(n * k, 1), k=k), None, None, None
         grad_input = torch.zeros(m, c, dtype=torch.float32, device=grad_output.device)
         ops().tgn_interpolation_backward(n, c, k, grad_output, idx, weight, grad_input, stream())
         return None, None, grad_input, None, None, None

@@ -40,7 +40,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from . import augment, losses, nets, preprocess, tgnet
+from . import augment, config as switches, losses, nets, preprocess, tgnet
 
 MODEL_NAMES = ("tgnet_fps", "tsegnet", "dgcnn", "pointnet", "pointnetpp", "pointtransformer", "tgnet_bdl")
 SCHEDULERS = ("exp", "cosine")
@@ -275,13 +275,19 @@ class TrainingModel:
     A subclass names its module class and gives `losses_of(output, seg_label, points)` -> {name: (value, weight)}.
 
     trainable=False is a model that is only evaluated (validation over a checkpoint): the module starts in eval mode, there is no
-    optimiser and no scheduler, the configuration needs no section for either, and step(..., "train") raises."""
+    optimiser and no scheduler, the configuration needs no section for either, and step(..., "train") raises.
+
+    tr_set["ordered_backward"] true sets config.cfg.ordered_backward for the process (ordered.py; tools/train.py --ordered_backward)."""
 
     module_class = None
 
     def __init__(self, config, module=None, trainable=True):
         self.config, self.trainable = config, trainable
         self.check_config(config, trainable)
+        if config.get("tr_set", {}).get("ordered_backward"):
+            # the package's switch (config.cfg.ordered_backward): every gather-family backward from here on sums along reverse
+            # lists, without float atomics.  Only ever switched ON from a configuration: absent or false leaves the switch as it is
+            switches.cfg.ordered_backward = True
         if not torch.cuda.is_available():
             raise RuntimeError("training needs a GPU: the modules' operators are HIP kernels and have no CPU fallback")
         self.device = torch.device("cuda")
