@@ -1,11 +1,16 @@
 """The contract of csrc/scatter_ordered.hip in numpy (include/tgn_pointops.h: tgn_reverse_lists, tgn_scatter_ordered).
 
-reverse_lists: a stable argsort of the target rows, the restatement of losses.reverse_lists for `batch` runs over n rows each.
+reverse_lists: a stable argsort of the target rows, for `batch` runs over n rows each.
+reverse_lists_torch: the same contract for one square list (m, k1) onto its own m rows as plain torch, on whatever device the tensor
+is on: the lists the fused contrastive-boundary stage saves for its backward (ordered.reverse_lists(idx, m)), stated without the
+kernel -- what tgn_reverse_lists is compared with on the device (tests/test_gpu_ordered_backward.py) and timed against
+(tools/ordered_backward_bench.py).
 scatter: out[r, ch] is the float32 sum, from +0.0f, taken SEQUENTIALLY in list order over the pairs of row r of term(q, ch), every
 term rounded to float32 before it is added.  numpy's float32 arithmetic rounds every operation, so the loop below -- one add per
 list position, all rows that are that long at once -- is that sum bit for bit.
 """
 import numpy as np
+import torch
 
 F32 = np.float32
 
@@ -19,6 +24,25 @@ def reverse_lists(idx, n, batch=1):
     order = np.argsort(keys, kind="stable")
     rev_start = np.searchsorted(keys[order], np.arange(batch * n + 1), side="left")
     return rev_start.astype(np.int32), order.astype(np.int32)
+
+
+def reverse_lists_torch(idx):
+    """The lists the fused backward gathers along: idx (m, k1) integer neighbour lists -> (rev_start (m + 1,), rev_pair (m * k1,)),
+    int32, where rev_pair[rev_start[i] : rev_start[i + 1]] holds the pair numbers q = i' * k1 + j with idx[i', j] == i in ascending
+    order.  An index outside [0, m) counts as 0, the point the kernels read for it.  Plain torch on the tensor's device, CPU included:
+    a STABLE sort of the flattened lists (equal neighbours keep the order of their pair numbers) and the cumulative counts of the
+    m values, taken as a searchsorted over the sorted keys -- torch.bincount reads its size back from a CUDA tensor, which would
+    synchronise and cannot be captured.  No synchronisation."""
+    if not isinstance(idx, torch.Tensor) or idx.is_floating_point() or idx.is_complex() or idx.dtype == torch.bool:
+        raise TypeError(f"idx must be an integer tensor, got {getattr(idx, 'dtype', type(idx).__name__)}")
+    if idx.dim() != 2:
+        raise ValueError(f"idx must be (m, k1), got {tuple(idx.shape)}")
+    m = idx.shape[0]
+    flat = idx.reshape(-1)
+    flat = torch.where((flat < 0) | (flat >= m), torch.zeros_like(flat), flat)
+    keys, order = torch.sort(flat, stable=True)
+    rev_start = torch.searchsorted(keys, torch.arange(m + 1, dtype=keys.dtype, device=keys.device), out_int32=True)
+    return rev_start, order.to(torch.int32)
 
 
 def identity_lists(n_rows, k):

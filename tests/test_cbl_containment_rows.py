@@ -12,13 +12,14 @@ the check.
 
 Operands: latent features are multiples of 1/64 in [-1, 1], neighbour indices and labels are valid, the workspace is exactly
 tgn_cbl_stage_workspace_bytes(m), every output exactly what the header states.  The backward's pair weights are multiples of 1/1024
-with exact zeros among them (a skipped pair), its lists are losses.reverse_lists of the same indices, built on the CPU.  Neither call
+with exact zeros among them (a skipped pair), its lists are ordered_ref.reverse_lists_torch of the same indices, built on the CPU.  Neither call
 has a float atomic, so the three runs compare bytes.  Shapes (m, k1, c): the smallest of everything; one point past a workgroup of the
 forward at the criterion's own width; the widest list at the two-pieces-per-lane-group width with several workgroups; the widest row,
 35 slots (the first stage's list) and a last workgroup that is not full."""
 import torch
 
 import containment_cases as T
+import ordered_ref
 from operator_forms import gen_for, q16
 
 F32, I32, I64 = torch.float32, torch.int32, torch.int64
@@ -44,10 +45,9 @@ def _fwd_build(shape):
 
 
 def _bwd_build(shape):
-    from toothgroupnetwork_amd import losses
     m, k1, c = shape
     g, ops = _inputs(shape)
-    rev_start, rev_pair = losses.reverse_lists(ops[1][2])
+    rev_start, rev_pair = ordered_ref.reverse_lists_torch(ops[1][2])
     return ops + [T.I("pair_w", q16(g, m, k1) / 64), T.I("count", torch.tensor([max(m // 2, 1)], dtype=I64)), T.I("rev_start", rev_start),
                   T.I("rev_pair", rev_pair), T.I("grad_loss", torch.tensor([0.75], dtype=F32)), T.O("grad_f", (m, c))]
 

@@ -3,7 +3,7 @@
   * the closed form the kernels compute (tests/cbl_fused_ref.py: the per-pair weights and the gradient along the reverse lists, float64
     numpy) equals the float64 restatement tests/cbl_ref.py, whose gradient is autograd's, on the hand-made cases over the CPU oracle's
     neighbour lists: within 1e-12 of cbl_ref's own scales (float64 rounding of two orders of the same sums; a scale of 0 means exact);
-  * losses.reverse_lists on CPU tensors against a Python loop;
+  * the torch statement of the reverse lists (tests/ordered_ref.reverse_lists_torch) on CPU tensors against a Python loop;
   * the entry points refuse the sizes they have no kernel for before any HIP call, naming the value;
   * the new kernels use no scratch; the points a workgroup takes are what losses.CBL_FUSED_BLOCK_POINTS says;
   * the switch is off by default at every layer, and tools/train.py --fused_contrastive_boundary sets the key."""
@@ -25,6 +25,7 @@ sys.path.insert(0, GOLDEN)
 import cbl_cases as CC  # noqa: E402
 import cbl_fused_ref as FR  # noqa: E402
 import cbl_ref  # noqa: E402
+import ordered_ref  # noqa: E402
 
 TOL = 1e-12
 
@@ -56,7 +57,6 @@ def _loop_lists(idx):
 
 @pytest.mark.parametrize("case", ["repeats", "hub", "one"])
 def test_reverse_lists_on_cpu_tensors(case):
-    from toothgroupnetwork_amd import losses
     g = torch.Generator().manual_seed(7)
     if case == "repeats":
         idx = torch.randint(0, 23, (23, 9), generator=g, dtype=torch.int32)
@@ -67,7 +67,7 @@ def test_reverse_lists_on_cpu_tensors(case):
     else:
         idx = torch.zeros(1, 5, dtype=torch.int32)
     m, k1 = idx.shape
-    rev_start, rev_pair = losses.reverse_lists(idx)
+    rev_start, rev_pair = ordered_ref.reverse_lists_torch(idx)
     assert rev_start.dtype == torch.int32 and tuple(rev_start.shape) == (m + 1,)
     assert rev_pair.dtype == torch.int32 and tuple(rev_pair.shape) == (m * k1,)
     assert int(rev_start[0]) == 0 and int(rev_start[-1]) == m * k1
@@ -81,11 +81,10 @@ def test_reverse_lists_on_cpu_tensors(case):
 
 
 def test_reverse_lists_checks_its_argument():
-    from toothgroupnetwork_amd import losses
     with pytest.raises(TypeError, match="idx"):
-        losses.reverse_lists(torch.zeros(3, 2))
+        ordered_ref.reverse_lists_torch(torch.zeros(3, 2))
     with pytest.raises(ValueError, match="idx"):
-        losses.reverse_lists(torch.zeros(6, dtype=torch.int32))
+        ordered_ref.reverse_lists_torch(torch.zeros(6, dtype=torch.int32))
 
 
 @pytest.mark.parametrize("k1,c,named", [(0, 32, "k1 = 0"), (64, 32, "k1 = 64"), (8, 0, "c = 0"), (8, 6, "c = 6"), (8, 132, "c = 132")])

@@ -1,7 +1,7 @@
 """GPU: the atomic-free backward of the gather family (csrc/scatter_ordered.hip, toothgroupnetwork_amd/ordered.py).
 
 1. tgn_reverse_lists equals tests/ordered_ref.reverse_lists element for element (tests/test_ordered_host.py ties that reference to
-   losses.reverse_lists), and losses.reverse_lists itself on the device wherever that function can state the case: square lists, and
+   the torch statement, ordered_ref.reverse_lists_torch), and that torch statement itself on the device wherever it can state the case: square lists, and
    lists whose rows index a SHORTER cloud with valid indices (its first n + 1 starts are then the same).
 2. tgn_scatter_ordered equals tests/ordered_ref.scatter bit for bit: every lane width, both forms, both signs, identity segments,
    a hub, empty rows into an output pre-filled with NaN.
@@ -81,7 +81,7 @@ LIST_PARAMS = [(name, torch.int64 if name == "dense_b3_int64" else torch.int32) 
 
 @pytest.mark.parametrize("name,itype", LIST_PARAMS, ids=[f"{n}-{'i64' if t == torch.int64 else 'i32'}" for n, t in LIST_PARAMS])
 def test_lists_equal_the_reference_and_losses_reverse_lists(dev, name, itype):
-    from toothgroupnetwork_amd import losses, ordered
+    from toothgroupnetwork_amd import ordered
     idx, n, batch = _list_case(name)
     want_start, want_pair = R.reverse_lists(idx.numpy(), n, batch)
     d_idx = idx.to(itype).to(dev)
@@ -91,8 +91,8 @@ def test_lists_equal_the_reference_and_losses_reverse_lists(dev, name, itype):
     assert np.array_equal(rev_start.cpu().numpy(), want_start), name
     assert np.array_equal(rev_pair.cpu().numpy(), want_pair), name
     if batch == 1 and idx.dim() == 2 and idx.shape[0] >= n and (idx.shape[0] == n or bool(((idx >= 0) & (idx < n)).all())):
-        l_start, l_pair = losses.reverse_lists(d_idx)
-        assert torch.equal(l_start[:n + 1], rev_start) and torch.equal(l_pair, rev_pair), f"{name}: against losses.reverse_lists on the device"
+        l_start, l_pair = R.reverse_lists_torch(d_idx)
+        assert torch.equal(l_start[:n + 1], rev_start) and torch.equal(l_pair, rev_pair), f"{name}: against the torch statement on the device"
 
 
 def test_lists_are_memoised_per_tensor_version_and_not_across_writes(dev):

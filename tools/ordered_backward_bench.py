@@ -2,12 +2,12 @@
 """What the atomic-free backward of the gather family costs (config.cfg.ordered_backward, ordered.py, csrc/scatter_ordered.hip).
 
 The baseline is the atomic path exactly as the operators run it with the switch off (the pre-zeroed gradient included) and, for the
-lists, losses.reverse_lists; never the new code against itself.  On one 24 000-point synthetic arch scan with its real k-NN lists:
+lists, the stable torch sort below (sorted_reverse_lists); never the new code against itself.  On one 24 000-point synthetic arch scan with its real k-NN lists:
 
   grouping backward            (24 000, 16, 32) and (24 000, 36, 32)      zeros + tgn_grouping_backward  |  tgn_scatter_ordered
   interpolation backward       6 000 -> 24 000 rows, k = 3, c = 64        zeros + tgn_interpolation_backward  |  tgn_scatter_ordered, query rows
   Point-Transformer tail       (24 000, 16, 32, g = 4)                    zeros + the kernel with its scatter  |  the kernel without + tgn_scatter_ordered
-  list build                   (24 000, 16) and (24 000, 36)              losses.reverse_lists  |  tgn_reverse_lists
+  list build                   (24 000, 16) and (24 000, 36)              sorted_reverse_lists (torch)  |  tgn_reverse_lists
 
 Every ordered figure comes twice: `lists cached` (the memo hit every block of a stage after the first sees) and `lists built` (the
 list build in the timed window).  The variants of a row alternate call by call in one process; device events around each call;
@@ -48,8 +48,19 @@ def alternate(variants, reps, warmup):
     return {tag: quartiles(v) for tag, v in ms.items()}
 
 
+def sorted_reverse_lists(idx):
+    """The lists of ordered.reverse_lists(idx, m) for square idx (m, k1) as plain torch: a stable sort of the flattened lists and a
+    searchsorted over the sorted keys (tests/ordered_ref.reverse_lists_torch).  The baseline of the `list build` rows."""
+    m = idx.shape[0]
+    flat = idx.reshape(-1)
+    flat = torch.where((flat < 0) | (flat >= m), torch.zeros_like(flat), flat)
+    keys, order = torch.sort(flat, stable=True)
+    rev_start = torch.searchsorted(keys, torch.arange(m + 1, dtype=keys.dtype, device=keys.device), out_int32=True)
+    return rev_start, order.to(torch.int32)
+
+
 def micro(points, reps, warmup, dev):
-    from toothgroupnetwork_amd import _lib, losses, ordered, pointops as P, synth
+    from toothgroupnetwork_amd import _lib, config, ordered, pointops as P, synth
     O, st = _lib.ops(), _lib.stream
     rows, _ = synth.labelled_arch(points, 14, seed=3)
     xyz = torch.from_numpy(np.ascontiguousarray(rows[:, :3])).to(dev)
@@ -77,7 +88,7 @@ def micro(points, reps, warmup, dev):
             {"atomic": atomic, "ordered, lists cached": lambda: ordered.scatter(flat, points, lists),
              "ordered, lists built": built(lambda l: ordered.scatter(flat, points, l), idx, points)}, reps, warmup)
         out[f"list build ({points}, {k})"] = alternate(
-            {"losses.reverse_lists": lambda: losses.reverse_lists(idx), "tgn_reverse_lists": built(lambda l: None, idx, points)}, reps, warmup)
+            {"sorted_reverse_lists": lambda: sorted_reverse_lists(idx), "tgn_reverse_lists": built(lambda l: None, idx, points)}, reps, warmup)
 
     # interpolation: a quarter of the points as the coarse cloud, every point interpolates from its 3 nearest coarse points
     coarse = points // 4
@@ -111,9 +122,10 @@ def micro(points, reps, warmup, dev):
         ordered.lists_cache_clear()
         ordered.softmax_aggregate_backward(xv, pr, sm, idx, go)
     ordered.reverse_lists(idx, points)
-    out[f"tail backward ({points}, {k}, {c}, g = {g_})"] = alternate(
-        {"atomic": tail_atomic, "ordered, lists cached": lambda: ordered.softmax_aggregate_backward(xv, pr, sm, idx, go),
-         "ordered, lists built": tail_built}, reps, warmup)
+    with config.override(ordered_backward=True):        # ordered.softmax_aggregate_backward reads the switch; tail_atomic is the raw kernel
+        out[f"tail backward ({points}, {k}, {c}, g = {g_})"] = alternate(
+            {"atomic": tail_atomic, "ordered, lists cached": lambda: ordered.softmax_aggregate_backward(xv, pr, sm, idx, go),
+             "ordered, lists built": tail_built}, reps, warmup)
     return out
 
 

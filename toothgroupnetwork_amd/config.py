@@ -26,8 +26,8 @@ fps_prefix            TGN_FPS_PREFIX         the FPS-of-an-FPS-result shortcut (
                                              True / False ("0": False, anything else: True): forced on / off for every FPS call
 ordered_backward      TGN_ORDERED_BACKWARD   the gather family's backward (grouping, queryandgroup, subtraction, interpolation, the
                       =0/1, default 0        Point-Transformer tail, index_points / group_points / three_interpolate) along reverse
-                                             lists instead of float atomics (ordered.py): the same bits every time.  Read at call time
-                                             in each backward.  Off: the atomic kernels, unchanged
+                                             lists instead of float atomics: the same bits every time.  Read at call time, in
+                                             ordered.py only, which states every such gradient in both forms.  Off: the atomic kernels
 """
 import dataclasses
 import os

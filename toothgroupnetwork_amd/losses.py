@@ -12,9 +12,9 @@
   contrast_boundary_stage, contrast_boundary_loss         the contrastive-boundary criterion (models/modules/cbl_point_transformer/heads.py:63-253
                                                           with default.yaml's configuration): the neighbour lists are tgn_knnquery*, the
                                                           (m, K-1, 32) latent differences and their gradient tgn_subtraction_forward / _backward
-  reverse_lists, contrast_boundary_lists,                 the same stage as two fused kernels (csrc/cbl.hip: tgn_cbl_stage_forward / _backward) that
-  contrast_boundary_stage_fused                           never form the difference tensor and whose gradient is bit-reproducible: behind
-                                                          contrast_boundary_loss(fused=True), off by default
+  contrast_boundary_lists,                                the same stage as two fused kernels (csrc/cbl.hip: tgn_cbl_stage_forward / _backward) that
+  contrast_boundary_stage_fused                           never form the difference tensor and whose gradient is bit-reproducible (summed along
+                                                          ordered.reverse_lists): behind contrast_boundary_loss(fused=True), off by default
 
 The reference loops over B x 16 teeth with boolean masks (one host round trip per tooth and scan) and sorts a (B, M, C) distance
 matrix to read two columns; here a forward is the per-tooth counts and centroids (crops.label_centroids), a point pass and a finishing
@@ -39,7 +39,7 @@ import torch
 import torch.nn.functional as F
 from torch.autograd import Function
 
-from . import _lib, crops, pointops
+from . import _lib, crops, ordered, pointops
 
 _fwd = torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
 _bwd = torch.amp.custom_bwd(device_type="cuda")
@@ -373,25 +373,6 @@ CBL_FUSED_MAX_C = 128        # kCblMaxC; and C a multiple of 4
 CBL_FUSED_BLOCK_POINTS = 16  # kCblPointsPerBlock: the points one workgroup of the forward takes (a partial sum each)
 
 
-def reverse_lists(idx):
-    """The lists the fused backward gathers along: idx (m, k1) integer neighbour lists -> (rev_start (m + 1,), rev_pair (m * k1,)),
-    int32, where rev_pair[rev_start[i] : rev_start[i + 1]] holds the pair numbers q = i' * k1 + j with idx[i', j] == i in ascending
-    order.  An index outside [0, m) counts as 0, the point the kernels read for it.  Plain torch on the tensor's device, CPU included:
-    a STABLE sort of the flattened lists (equal neighbours keep the order of their pair numbers) and the cumulative counts of the
-    m values, taken as a searchsorted over the sorted keys -- torch.bincount reads its size back from a CUDA tensor, which would
-    synchronise and cannot be captured.  No synchronisation."""
-    if not isinstance(idx, torch.Tensor) or idx.is_floating_point() or idx.is_complex() or idx.dtype == torch.bool:
-        raise TypeError(f"idx must be an integer tensor, got {getattr(idx, 'dtype', type(idx).__name__)}")
-    if idx.dim() != 2:
-        raise ValueError(f"idx must be (m, k1), got {tuple(idx.shape)}")
-    m = idx.shape[0]
-    flat = idx.reshape(-1)
-    flat = torch.where((flat < 0) | (flat >= m), torch.zeros_like(flat), flat)
-    keys, order = torch.sort(flat, stable=True)
-    rev_start = torch.searchsorted(keys, torch.arange(m + 1, dtype=keys.dtype, device=keys.device), out_int32=True)
-    return rev_start, order.to(torch.int32)
-
-
 class _CblStage(Function):
     """(loss, count) of packed float32 f (m, C), int32 idx (m, k1) and int64 labels (m,)."""
 
@@ -406,9 +387,11 @@ class _CblStage(Function):
         pair_w = torch.empty(m, k1, dtype=torch.float32, device=dev)
         ws_bytes = L.tgn_cbl_stage_workspace_bytes(m)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        # the lists the backward gathers along: row i's are the pair numbers q = i' * k1 + j with idx[i', j] == i, ascending
+        lists = ordered.reverse_lists(idx, m) if ctx.needs_input_grad[0] else ()
         L.tgn_cbl_stage_forward(m, k1, c, f, idx, labels, loss, count, pair_w, ws, ws_bytes, _lib.stream())
-        if ctx.needs_input_grad[0]:
-            ctx.save_for_backward(f, idx, pair_w, count, *reverse_lists(idx))
+        if lists:
+            ctx.save_for_backward(f, idx, pair_w, count, *lists)
         n = count[0]
         ctx.mark_non_differentiable(n)
         return loss[0], n
@@ -432,7 +415,7 @@ def contrast_boundary_lists(f, idx, labels):
     """One stage of the criterion on neighbour lists the caller supplies, as fused kernels: latent features f (m, C) floating, idx
     (m, k1) integer -- the lists WITHOUT their column 0 -- and integer labels (m,) -> (loss, count) as contrast_boundary_stage defines
     them.  The (m, k1, C) differences are never formed: the forward keeps one (m, k1) float32 weight per pair, the backward gathers
-    every row's gradient along reverse_lists(idx) without float atomics, so loss, count AND gradient are the same bits for the same
+    every row's gradient along ordered.reverse_lists(idx, m) without float atomics, so loss, count AND gradient are the same bits for the same
     inputs.  1 <= k1 <= 63, C a multiple of 4 in 4..128 and m * k1 < 2^31, otherwise ValueError; an index outside [0, m) reads point 0
     and latches _lib.INDEX_ERROR_GATHER on the stream.  No synchronisation; forward and backward can be captured in a graph."""
     f = _lib.f32c(f, "f")

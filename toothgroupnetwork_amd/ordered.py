@@ -1,11 +1,14 @@
-"""The atomic-free backward of the gather family: every raw-pointer call of csrc/scatter_ordered.hip.
+"""The backward of the gather family, both forms: every gradient that flows through a neighbour list is stated here, once.
 
 A scatter-add ``out[idx[q]] += term(q)`` with float atomics gives other bits from launch to launch.  Turned round it does not:
 ``reverse_lists`` builds, per target row, the ascending list of the pair numbers that target it (tgn_reverse_lists), and ``scatter``
 lets one lane group own a row and add that row's terms in list order (tgn_scatter_ordered; include/tgn_pointops.h states both
-contracts).  The ``backward`` methods of pointops, pointnet2_utils and point_transformer call the two when
-``config.cfg.ordered_backward`` is set (TGN_ORDERED_BACKWARD=1, ``tools/train.py --ordered_backward``); it is read at call time and
-off by default.  No CPU path, no fallback.
+contracts, csrc/scatter_ordered.hip holds the kernels).  The ``*_backward`` functions at the end of this module each state one
+gradient in its atomic form (a zero-filled accumulator and the operator's own backward kernel) and in its ordered form (the two
+calls above) and choose by ``config.cfg.ordered_backward`` (TGN_ORDERED_BACKWARD=1, ``tools/train.py --ordered_backward``; off by
+default), which is read here and nowhere else, at call time.  The ``backward`` methods of pointops, pointnet2_utils and
+point_transformer call them; the fused contrastive-boundary stage (losses.py) takes its lists from ``reverse_lists`` too.  No CPU
+path, no fallback.
 
 The lists are memoised per index tensor -- the blocks of a Point-Transformer stage share one ``knn_indices`` tensor, and inside a
 layer ``_QueryGroup`` and the attention tail share one too -- keyed like the kNN memo of pointops on the tensor's identity (held
@@ -17,6 +20,7 @@ replayed on new indices.
 import torch
 from torch.utils.weak import WeakTensorKeyDictionary
 
+from . import config
 from ._lib import ops, require_cuda, stream
 
 _LISTS = WeakTensorKeyDictionary()     # idx tensor -> {(n, batch, wrap, stream): (version, rev_start, rev_pair)}
@@ -48,8 +52,8 @@ def _build(idx, n, batch, wrap):
 def reverse_lists(idx, n, batch=1, wrap=False):
     """idx: `batch` equal runs of indices into [0, n) (any shape; int32 or int64, contiguous) -> (rev_start (batch * n + 1,),
     rev_pair (idx.numel(),)) int32: rev_pair[rev_start[r] : rev_start[r + 1]] holds, ascending, the pair numbers q with
-    (q // pairs_per_batch) * n + idx.flatten()[q] == r.  An index outside [0, n) counts as row 0 of its batch, as in
-    losses.reverse_lists; wrap=True first maps a negative index i to i + n.  No synchronisation."""
+    (q // pairs_per_batch) * n + idx.flatten()[q] == r.  An index outside [0, n) counts as row 0 of its batch;
+    wrap=True first maps a negative index i to i + n.  No synchronisation."""
     require_cuda(idx)
     if idx.dtype not in (torch.int32, torch.int64) or not idx.is_contiguous():
         raise ValueError(f"idx must be int32 or int64 and contiguous here, got {idx.dtype} with strides {tuple(idx.stride())}")
@@ -108,12 +112,75 @@ def scatter(src, n_rows, lists=None, coef=None, k=1, sign=1.0):
     return out
 
 
+# ---- the gradients, each in both forms ---------------------------------------------------------------------------------------------
+def gather_lists(idx, n, dense=None):
+    """What gather_backward sums along, for a backward that calls it twice on one idx (None in the atomic form, which needs none)."""
+    if config.cfg.ordered_backward:
+        return reverse_lists(idx, n) if dense is None else reverse_lists(idx, n, dense[0], wrap=True)
+
+
+def gather_backward(src, idx, n, dense=None, lists=None):
+    """The gradient of the plain gather out[q] = x[idx[q]] from src (..., c) float32 contiguous, one row per index.
+    Packed (dense None): idx (m, nsample) int32 onto n rows -> (n, c).  Dense = (batch, indices per cloud): `batch` clouds (0 too) of
+    n rows, idx int32 or int64 with a cloud's own row numbers, negative ones wrapping as in the forward -> (batch, n, c)."""
+    c = src.shape[-1]
+    if config.cfg.ordered_backward:
+        grad = scatter(src.flatten(0, -2), n if dense is None else dense[0] * n, lists or gather_lists(idx, n, dense))
+        return grad if dense is None else grad.view(dense[0], n, c)
+    if dense is None:
+        grad = torch.zeros(n, c, dtype=torch.float32, device=src.device)
+        ops().tgn_grouping_backward(idx.shape[0], idx.shape[1], c, src, idx, grad, stream())
+    else:
+        grad = torch.zeros(dense[0], n, c, dtype=torch.float32, device=src.device)
+        ops().tgn_scatter_add_points(dense[0], n, dense[1], c, src, idx, int(idx.dtype == torch.int64), grad, stream())
+    return grad
+
+
+def weighted_gather_backward(src, idx, weight, n, batch=None):
+    """The gradient of the weighted gather out[q] = sum_j f[idx[q, j]] * weight[q, j] onto f, from src (..., c), one row per query.
+    Packed (batch None): idx (queries, k) int32 onto n rows -> (n, c).  Dense: idx (batch, queries, k) int32 or int64 with a cloud's
+    own row numbers -> (batch, n, c); the atomic kernel reads them as global int32 rows of the flattened (batch * n, c) features."""
+    c, k, b = src.shape[-1], idx.shape[-1], 1 if batch is None else batch        # (an empty batch, 0, is still the dense form)
+    if config.cfg.ordered_backward:
+        grad = scatter(src.flatten(0, -2), b * n, reverse_lists(idx, n, b), coef=weight.view(-1, 1), k=k)
+    else:
+        if batch is not None:
+            idx = (idx + (torch.arange(batch, device=idx.device, dtype=idx.dtype) * n).view(batch, 1, 1)).to(torch.int32).contiguous()
+        grad = torch.zeros(b * n, c, dtype=torch.float32, device=src.device)
+        ops().tgn_interpolation_backward(idx.shape[:-1].numel(), c, k, src, idx, weight, grad, stream())
+    return grad if batch is None else grad.view(batch, n, c)
+
+
+def subtraction_backward(src, idx, n2):
+    """Both gradients of out[i, j] = a[i] - b[idx[i, j]] from src (n, nsample, c) -> (g_a (n, c), g_b (n2, c)): one atomic launch, or
+    the identity segments for a and the signed sum along the lists for b."""
+    n, nsample, c = src.shape
+    if config.cfg.ordered_backward:
+        pair_rows = src.view(n * nsample, c)
+        return scatter(pair_rows, n, None, k=nsample), scatter(pair_rows, n2, reverse_lists(idx, n2), sign=-1.0)
+    g_a, g_b = src.new_zeros(n, c), src.new_zeros(n2, c)
+    ops().tgn_subtraction_backward(n, nsample, c, idx, src, g_a, g_b, stream())
+    return g_a, g_b
+
+
+def centres_backward(g_rel):
+    """The gradient of the centres of pointops._QueryGroup, out[i, j] = xyz[idx[i, j]] - new_xyz[i], from g_rel (m, nsample, 3)
+    -> (m, 3): torch's sum beside the atomic kernels, the identity segments with sign -1 in the ordered form."""
+    if config.cfg.ordered_backward:
+        m, nsample, c = g_rel.shape
+        return scatter(g_rel.view(m * nsample, c), m, None, k=nsample, sign=-1.0)
+    return -g_rel.sum(1)
+
+
 def softmax_aggregate_backward(x_v, p_r, sm, idx, grad_out):
-    """The Point-Transformer tail's backward with its d_xv scatter left out of the kernel and summed along the lists instead, over
-    the d_pr the kernel writes anyway -> (g_xv, g_pr, g_logit)."""
+    """The Point-Transformer tail's backward -> (g_xv, g_pr, g_logit): the kernel with its atomic d_xv scatter into a zero-filled
+    g_xv, or the kernel with that scatter left out and d_xv summed along the lists instead, over the d_pr the kernel writes anyway."""
     n, nsample, c = p_r.shape
+    on = config.cfg.ordered_backward
+    g_xv = None if on else torch.zeros_like(x_v)
     g_pr = torch.empty_like(p_r)
     g_lg = torch.empty_like(sm)
-    ops().tgn_pt_softmax_aggregate_backward(n, nsample, c, sm.shape[2], x_v, p_r, sm, idx, grad_out, None, g_pr, g_lg, stream())
-    g_xv = scatter(g_pr.view(n * nsample, c), x_v.shape[0], reverse_lists(idx, x_v.shape[0]))
+    ops().tgn_pt_softmax_aggregate_backward(n, nsample, c, sm.shape[2], x_v, p_r, sm, idx, grad_out, g_xv, g_pr, g_lg, stream())
+    if on:
+        g_xv = scatter(g_pr.view(n * nsample, c), x_v.shape[0], reverse_lists(idx, x_v.shape[0]))
     return g_xv, g_pr, g_lg

@@ -25,7 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd import Function
 
-from . import _derived, _lib, config, fold, ordered, pointnet2_utils as _U, pointops
+from . import _derived, _lib, fold, ordered, pointnet2_utils as _U, pointops
 from ._lib import f32c, idx32c, ops, stream
 from .sa_fused import pack_first_layer
 
@@ -54,16 +54,7 @@ class _SoftmaxAggregate(Function):
     @_bwd
     def backward(ctx, grad_out):
         x_v, p_r, sm, idx = ctx.saved_tensors
-        n, nsample, c = p_r.shape
-        g = sm.shape[2]
-        grad_out = grad_out.contiguous().float()
-        if config.cfg.ordered_backward:
-            return ordered.softmax_aggregate_backward(x_v, p_r, sm, idx, grad_out) + (None,)
-        g_xv = torch.zeros_like(x_v)
-        g_pr = torch.empty_like(p_r)
-        g_lg = torch.empty_like(sm)
-        ops().tgn_pt_softmax_aggregate_backward(n, nsample, c, g, x_v, p_r, sm, idx, grad_out, g_xv, g_pr, g_lg, stream())
-        return g_xv, g_pr, g_lg, None
+        return ordered.softmax_aggregate_backward(x_v, p_r, sm, idx, grad_out.contiguous().float()) + (None,)
 
 
 def pt_softmax_aggregate(x_v, p_r, logit, idx):

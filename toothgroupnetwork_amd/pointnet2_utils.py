@@ -109,7 +109,7 @@ class _IndexPoints(Function):
         _lib.begin_index_check()
         ops().tgn_gather_points(B, N, M, C, points, idx, int(idx.dtype == torch.int64), out, stream())
         _lib.raise_on_index_error("index_points")
-        ctx.shape = (B, N, M, C)
+        ctx.shape = (B, N, M)
         ctx.save_for_backward(idx)
         return out
 
@@ -117,13 +117,8 @@ class _IndexPoints(Function):
     @_bwd
     def backward(ctx, g):
         idx, = ctx.saved_tensors
-        B, N, M, C = ctx.shape
-        g = g.contiguous().float()
-        if config.cfg.ordered_backward:
-            return ordered.scatter(g.view(B * M, C), B * N, ordered.reverse_lists(idx, N, B, wrap=True)).view(B, N, C), None
-        grad = torch.zeros(B, N, C, dtype=torch.float32, device=g.device)
-        ops().tgn_scatter_add_points(B, N, M, C, g, idx, int(idx.dtype == torch.int64), grad, stream())
-        return grad, None
+        B, N, M = ctx.shape
+        return ordered.gather_backward(g.contiguous().float(), idx, N, (B, M)), None
 
 
 def index_points(points, idx):
@@ -233,7 +228,7 @@ class _GroupPoints(Function):
         _lib.begin_index_check()
         ops().tgn_group_points(B, N, S, K, D, xyz, new_xyz, points, idx, int(idx.dtype == torch.int64), int(xyz_first), out, stream())
         _lib.raise_on_index_error("group_points")
-        ctx.dims = (B, N, S, K, D, bool(xyz_first))
+        ctx.dims = (B, N, S * K, D, bool(xyz_first))
         ctx.save_for_backward(idx)
         return out
 
@@ -241,30 +236,17 @@ class _GroupPoints(Function):
     @_bwd
     def backward(ctx, g):
         idx, = ctx.saved_tensors
-        B, N, S, K, D, xyz_first = ctx.dims
+        B, N, M, D, xyz_first = ctx.dims
         g = g.contiguous().float()
         g_rel = (g[..., :3] if xyz_first else g[..., D:]).contiguous()
-        is64 = int(idx.dtype == torch.int64)
+        lists = ordered.gather_lists(idx, N, (B, M))    # xyz and features share them
         g_xyz = g_new = g_pts = None
-        if config.cfg.ordered_backward:
-            lists = ordered.reverse_lists(idx, N, B, wrap=True)
-            if ctx.needs_input_grad[0]:
-                g_xyz = ordered.scatter(g_rel.view(B * S * K, 3), B * N, lists).view(B, N, 3)
-            if ctx.needs_input_grad[1]:
-                g_new = -g_rel.sum(2)
-            if D and ctx.needs_input_grad[2]:
-                g_f = (g[..., 3:] if xyz_first else g[..., :D]).contiguous()
-                g_pts = ordered.scatter(g_f.view(B * S * K, D), B * N, lists).view(B, N, D)
-            return g_xyz, g_new, g_pts, None, None
         if ctx.needs_input_grad[0]:
-            g_xyz = torch.zeros(B, N, 3, dtype=torch.float32, device=g.device)
-            ops().tgn_scatter_add_points(B, N, S * K, 3, g_rel, idx, is64, g_xyz, stream())
+            g_xyz = ordered.gather_backward(g_rel, idx, N, (B, M), lists)
         if ctx.needs_input_grad[1]:
-            g_new = -g_rel.sum(2)
+            g_new = -g_rel.sum(2)       # torch's sum in both forms (pointops._QueryGroup takes ordered.centres_backward for its centres)
         if D and ctx.needs_input_grad[2]:
-            g_f = (g[..., 3:] if xyz_first else g[..., :D]).contiguous()
-            g_pts = torch.zeros(B, N, D, dtype=torch.float32, device=g.device)
-            ops().tgn_scatter_add_points(B, N, S * K, D, g_f, idx, is64, g_pts, stream())
+            g_pts = ordered.gather_backward((g[..., 3:] if xyz_first else g[..., :D]).contiguous(), idx, N, (B, M), lists)
         return g_xyz, g_new, g_pts, None, None
 
 
@@ -331,7 +313,7 @@ class _ThreeInterpolate(Function):
         out = torch.empty(B, N, C, dtype=torch.float32, device=points2.device)
         weight = torch.empty(B, N, 3, dtype=torch.float32, device=points2.device)
         ops().tgn_three_interpolate(B, N, S, C, points2, dist, idx, int(idx.dtype == torch.int64), out, weight, stream())
-        ctx.dims = (B, N, S, C)
+        ctx.dims = (B, S)
         ctx.save_for_backward(idx, weight)
         return out
 
@@ -339,16 +321,8 @@ class _ThreeInterpolate(Function):
     @_bwd
     def backward(ctx, g):
         idx, weight = ctx.saved_tensors
-        B, N, S, C = ctx.dims
-        g = g.contiguous().float()
-        if config.cfg.ordered_backward:
-            grad = ordered.scatter(g.view(B * N, C), B * S, ordered.reverse_lists(idx, S, B), coef=weight.view(B * N * 3, 1), k=3)
-            return grad.view(B, S, C), None, None
-        # global row indices into the flattened (B*S, C) support features
-        gidx = (idx + (torch.arange(B, device=idx.device, dtype=idx.dtype) * S).view(B, 1, 1)).to(torch.int32)
-        grad = torch.zeros(B * S, C, dtype=torch.float32, device=g.device)
-        ops().tgn_interpolation_backward(B * N, C, 3, g, gidx.contiguous(), weight, grad, stream())
-        return grad.view(B, S, C), None, None
+        B, S = ctx.dims
+        return ordered.weighted_gather_backward(g.contiguous().float(), idx, weight, S, B), None, None
 
 
 def linear_relu(x, W, b):

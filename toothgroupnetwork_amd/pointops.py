@@ -210,6 +210,14 @@ class Grouping(Function):
     # .apply takes packed operands only -- float32 features, int32 indices, contiguous -- and raises ValueError otherwise (the
     # reference's kernels read int32 too); the function of the same name in lower case casts and packs any dtype and layout
     @staticmethod
+    def gather_rows(input, idx):
+        """The launch, shared with _QueryGroup without use_xyz: input (n, c), idx (m, nsample), packed -> input[idx] (m, nsample, c)"""
+        m, nsample, c = idx.shape[0], idx.shape[1], input.shape[1]
+        output = torch.empty(m, nsample, c, dtype=torch.float32, device=input.device)
+        ops().tgn_grouping_forward(m, nsample, c, input, idx, output, stream())
+        return output
+
+    @staticmethod
     @_fwd
     def forward(ctx, input, idx):
         """
@@ -218,12 +226,9 @@ class Grouping(Function):
         """
         require_cuda(input, idx)
         _packed(input, "input"), _packed_idx(idx, "idx")
-        m, nsample, n, c = idx.shape[0], idx.shape[1], input.shape[0], input.shape[1]
-        output = torch.empty(m, nsample, c, dtype=torch.float32, device=input.device)
-        ops().tgn_grouping_forward(m, nsample, c, input, idx, output, stream())
-        ctx.n = n
+        ctx.n = input.shape[0]
         ctx.save_for_backward(idx)
-        return output
+        return Grouping.gather_rows(input, idx)
 
     @staticmethod
     @_bwd
@@ -232,15 +237,8 @@ class Grouping(Function):
         input: grad_out: (m, nsample, c)
         output: (n, c), None        [pointops.py:63-74]
         """
-        n = ctx.n
         idx, = ctx.saved_tensors
-        grad_output = grad_output.contiguous().float()
-        m, nsample, c = grad_output.shape
-        if config.cfg.ordered_backward:
-            return ordered.scatter(grad_output.view(m * nsample, c), n, ordered.reverse_lists(idx, n)), None
-        grad_input = torch.zeros(n, c, dtype=torch.float32, device=grad_output.device)
-        ops().tgn_grouping_backward(m, nsample, c, grad_output, idx, grad_input, stream())
-        return grad_input, None
+        return ordered.gather_backward(grad_output.contiguous().float(), idx, ctx.n), None
 
 
 def grouping(input, idx):
@@ -269,9 +267,7 @@ class _QueryGroup(Function):
         ctx.n, ctx.use_xyz = n, use_xyz
         ctx.save_for_backward(idx)
         if not use_xyz:
-            out = torch.empty(m, nsample, c, dtype=torch.float32, device=feat.device)
-            ops().tgn_grouping_forward(m, nsample, c, feat, idx, out, stream())
-            return out
+            return Grouping.gather_rows(feat, idx)
         out = torch.empty(m, nsample, 3 + c, dtype=torch.float32, device=feat.device)
         # packed layout == dense layout with B=1: rows of new_xyz are the S "centres", K = nsample
         ops().tgn_group_points(1, n, m, nsample, c, xyz, new_xyz, feat, idx, 0, 1, out, stream())
@@ -281,35 +277,17 @@ class _QueryGroup(Function):
     @_bwd
     def backward(ctx, grad_out):
         idx, = ctx.saved_tensors
-        m, nsample = idx.shape
-        n = ctx.n
-        grad_out = grad_out.contiguous().float()
+        g_feat = grad_out.contiguous().float()
+        lists = ordered.gather_lists(idx, ctx.n)        # xyz and features share them
         g_xyz = g_new = None
-        if config.cfg.ordered_backward:
-            lists = ordered.reverse_lists(idx, n)
-            g_feat = grad_out
-            if ctx.use_xyz:
-                g_rel = grad_out[:, :, :3].contiguous().view(m * nsample, 3)
-                g_feat = grad_out[:, :, 3:].contiguous()
-                if ctx.needs_input_grad[0]:
-                    g_xyz = ordered.scatter(g_rel, n, lists)
-                if ctx.needs_input_grad[1]:
-                    g_new = ordered.scatter(g_rel, m, None, k=nsample, sign=-1.0)
-            return g_xyz, g_new, ordered.scatter(g_feat.view(m * nsample, g_feat.shape[2]), n, lists), None, None
         if ctx.use_xyz:
-            g_rel = grad_out[:, :, :3].contiguous()
-            g_feat = grad_out[:, :, 3:].contiguous()
+            g_rel, g_feat = g_feat[:, :, :3].contiguous(), g_feat[:, :, 3:].contiguous()
             if ctx.needs_input_grad[0]:
-                g_xyz = torch.zeros(n, 3, dtype=torch.float32, device=grad_out.device)
-                ops().tgn_grouping_backward(m, nsample, 3, g_rel, idx, g_xyz, stream())
+                g_xyz = ordered.gather_backward(g_rel, idx, ctx.n, lists=lists)
             if ctx.needs_input_grad[1]:
-                g_new = -g_rel.sum(1)
-        else:
-            g_feat = grad_out
-        c = g_feat.shape[2]
-        g_in = torch.zeros(n, c, dtype=torch.float32, device=grad_out.device)
-        ops().tgn_grouping_backward(m, nsample, c, g_feat, idx, g_in, stream())
-        return g_xyz, g_new, g_in, None, None
+                # (the ordered form is a kernel's sum; pointnet2_utils._GroupPoints keeps torch's sum for its centres in both forms)
+                g_new = ordered.centres_backward(g_rel)
+        return g_xyz, g_new, ordered.gather_backward(g_feat, idx, ctx.n, lists=lists), None, None
 
 
 def queryandgroup(nsample, xyz, new_xyz, feat, idx, offset, new_offset, use_xyz=True):
@@ -365,16 +343,7 @@ class Subtraction(Function):
         output: grad_input1: (n, c), grad_input2: (n, c)    [pointops.py:118-128]
         """
         idx, = ctx.saved_tensors
-        grad_output = grad_output.contiguous().float()
-        n, nsample, c = grad_output.shape
-        if config.cfg.ordered_backward:
-            pair_rows = grad_output.view(n * nsample, c)
-            return (ordered.scatter(pair_rows, n, None, k=nsample),
-                    ordered.scatter(pair_rows, ctx.n2, ordered.reverse_lists(idx, ctx.n2), sign=-1.0), None)
-        grad_input1 = torch.zeros(n, c, dtype=torch.float32, device=grad_output.device)
-        grad_input2 = torch.zeros(ctx.n2, c, dtype=torch.float32, device=grad_output.device)
-        ops().tgn_subtraction_backward(n, nsample, c, idx, grad_output, grad_input1, grad_input2, stream())
-        return grad_input1, grad_input2, None
+        return ordered.subtraction_backward(grad_output.contiguous().float(), idx, ctx.n2) + (None,)
 
 
 def subtraction(input1, input2, idx):
@@ -439,9 +408,8 @@ class _WeightedGather(Function):
     interpolation kernel (interpolation_cuda_kernel.cu:5-18) with its atomic backward (:20-33)."""
 
     @staticmethod
-    @_fwd
-    def forward(ctx, feat, idx, weight):
-        _packed(feat, "feat"), _packed_idx(idx, "idx"), _packed(weight, "weight")
+    def launch(ctx, feat, idx, weight):
+        """The forward launch, shared with Interpolation, and what the backward needs on ctx."""
         n, k = idx.shape
         m, c = feat.shape
         output = torch.zeros(n, c, dtype=torch.float32, device=feat.device)
@@ -451,17 +419,15 @@ class _WeightedGather(Function):
         return output
 
     @staticmethod
+    @_fwd
+    def forward(ctx, feat, idx, weight):
+        _packed(feat, "feat"), _packed_idx(idx, "idx"), _packed(weight, "weight")
+        return _WeightedGather.launch(ctx, feat, idx, weight)
+
+    @staticmethod
     @_bwd
     def backward(ctx, grad_output):
-        idx, weight = ctx.saved_tensors
-        grad_output = grad_output.contiguous().float()
-        n, c = grad_output.shape
-        k = idx.shape[1]
-        if config.cfg.ordered_backward:
-            return ordered.scatter(grad_output, ctx.m, ordered.reverse_lists(idx, ctx.m), coef=weight.view(n * k, 1), k=k), None, None
-        grad_input = torch.zeros(ctx.m, c, dtype=torch.float32, device=grad_output.device)
-        ops().tgn_interpolation_backward(n, c, k, grad_output, idx, weight, grad_input, stream())
-        return grad_input, None, None
+        return ordered.weighted_gather_backward(grad_output.contiguous().float(), *ctx.saved_tensors, ctx.m), None, None
 
 
 def interpolation(xyz, new_xyz, feat, offset, new_offset, k=3):
@@ -478,6 +444,7 @@ def interpolation(xyz, new_xyz, feat, offset, new_offset, k=3):
 
 
 class Interpolation(Function):
+    # _WeightedGather behind an uncached k-NN and its inverse-distance weights (and, unlike it, without the autocast decorators)
     @staticmethod
     def forward(ctx, xyz, new_xyz, input, offset, new_offset, k=3):
         """
@@ -489,27 +456,14 @@ class Interpolation(Function):
         k = as_int(k)
         idx, dist2 = _knn_raw(k, xyz, new_xyz, offset, new_offset)      # (normalises xyz, new_xyz and the offsets itself)
         weight = _inverse_distance_weights(torch.sqrt(dist2)).contiguous()
-        n, c, m = new_xyz.shape[0], input.shape[1], input.shape[0]
-        output = torch.zeros(n, c, dtype=torch.float32, device=input.device)
-        ops().tgn_interpolation_forward(n, c, k, input, idx, weight, output, stream())
-        ctx.m, ctx.k = m, k
-        ctx.save_for_backward(idx, weight)
-        return output
+        return _WeightedGather.launch(ctx, input, idx, weight)
 
     @staticmethod
     def backward(ctx, grad_output):
         """
         output: None, None, grad_input (m, c), None, None, None     [pointops.py:203-214]
         """
-        m, k = ctx.m, ctx.k
-        idx, weight = ctx.saved_tensors
-        grad_output = grad_output.contiguous().float()
-        n, c = grad_output.shape
-        if config.cfg.ordered_backward:
-            return None, None, ordered.scatter(grad_output, m, ordered.reverse_lists(idx, m), coef=weight.view(n * k, 1), k=k), None, None, None
-        grad_input = torch.zeros(m, c, dtype=torch.float32, device=grad_output.device)
-        ops().tgn_interpolation_backward(n, c, k, grad_output, idx, weight, grad_input, stream())
-        return None, None, grad_input, None, None, None
+        return None, None, ordered.weighted_gather_backward(grad_output.contiguous().float(), *ctx.saved_tensors, ctx.m), None, None, None
 
 
 def interpolation2(xyz, new_xyz, input, offset, new_offset, k=3):
