@@ -428,6 +428,33 @@ int tgn_bn_rows_forward(long long rows, int C, const float *x, const float *gamm
 int tgn_bn_rows_backward(long long rows, int C, const float *x, const float *y, const float *dy, const float *gamma,
                          const float *save_mean, const float *save_invstd, int relu, float *dx, float *dgamma, float *dbeta,
                          void *workspace, tgn_stream_t stream);
+/*
+ * The same two calls with ORDERED reductions: no float or double atomic (and no integer one either), so every output has the same
+ * bits on every call, whatever else runs on the device.  Operands, limits and status codes as above, plus workspace_bytes: less
+ * than tgn_bn_rows_ordered_workspace_bytes(rows, C) (0 for unsupported rows / C) is TGN_ERR_INVALID_ARGUMENT before any launch.
+ * The workspace may hold ANYTHING on entry (as for tgn_reverse_lists) and holds the partial sums afterwards; calls that share one
+ * must be ordered on one stream.  Three launches per call, no host synchronisation, capturable.
+ * The summation order is a function of (rows, C) only.  With total = rows * C, m = C / gcd(256, C) and
+ * B = min(1024, max(1, ceil(total / 8192))) rounded up to a multiple of m, the reduction runs B blocks of 256 threads, T = 256 B:
+ *   1. thread t = 256 b + i adds the terms of elements t, t + T, t + 2 T, ... (all in column t % C) in ascending order from +0.0.
+ *      forward: s1 += (double)x, s2 += (double)x * (double)x.  backward, with g = dy (0 where relu and y <= 0) and all of
+ *      g * ((x - mean) * invstd) in float: s1 += (double)g, s2 += (double)that product;
+ *   2. in block b the thread i < min(C, 256) adds to its own sums those of threads i + C, i + 2 C, ... < 256, ascending: the block's
+ *      partial for column (256 b + i) % C.  A column none of its threads keeps (C > 256) gets +0.0;
+ *   3. per column, chain j < 64 adds the partials of blocks j, j + 64, j + 128, ... in ascending order from +0.0;
+ *   4. the chains j = 0 .. min(B, 64) - 1 are added in ascending order from +0.0.
+ * All sums are double, the library is built with -ffp-contract=off, and what follows is the arithmetic of the atomic form: mean =
+ * s1 / rows, var = max(0, s2 / rows - mean * mean), invstd = 1 / sqrt(var + eps), the running statistics in double with var * (rows /
+ * (rows - 1)), dbeta = (float)s1, dgamma = (float)s2.  tests/bn_ordered_ref.py restates all of it in numpy.
+ */
+size_t tgn_bn_rows_ordered_workspace_bytes(long long rows, int C);
+int tgn_bn_rows_forward_ordered(long long rows, int C, const float *x, const float *gamma, const float *beta, float eps,
+                                float momentum, float *running_mean, float *running_var, long long *num_batches_tracked, int relu,
+                                float *y, float *save_mean, float *save_invstd, void *workspace, size_t workspace_bytes,
+                                tgn_stream_t stream);
+int tgn_bn_rows_backward_ordered(long long rows, int C, const float *x, const float *y, const float *dy, const float *gamma,
+                                 const float *save_mean, const float *save_invstd, int relu, float *dx, float *dgamma, float *dbeta,
+                                 void *workspace, size_t workspace_bytes, tgn_stream_t stream);
 /* index_points (pointnet2_utils.py:44-61): out[b,j,:] = points[b, idx[b,j], :], idx flattened to (B,M). */
 int tgn_gather_points(int B, int N, int M, int C, const float *points, const void *idx, int idx_is_int64, float *out,
                       tgn_stream_t stream);

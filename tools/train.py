@@ -14,7 +14,11 @@ out, and a non-zero cbl weight is then refused (training.py).  --fused_contrasti
 the criterion's stages run as the fused kernels of csrc/cbl.hip (no (m, K-1, 32) difference tensor, a bit-reproducible gradient;
 off by default).  --ordered_backward sets tr_set.ordered_backward, which switches config.cfg.ordered_backward on: every gradient that
 flows through a neighbour list is summed along reverse lists instead of with float atomics (ordered.py; off by default; the
-BatchNorm kernels' float64 atomics remain).  tgnet_bdl (train_configs/tgnet_bdl.py with its four paths edited)
+BatchNorm kernels' float64 atomics remain: that is config.cfg.ordered_bn).  --reproducible sets tr_set.reproducible: with --seed, the
+same data and the same machine, two runs end in the same bits.  It switches on both ordered forms, torch.use_deterministic_algorithms
+(an operator torch knows to be non-deterministic raises and names itself) and the deterministic solver choice, adds "digest" (a
+sha256 over the module's state) to the epoch line so that two runs can be compared without their checkpoints, and refuses a model
+whose step is known not to repeat (training.NOT_REPRODUCIBLE; DESIGN.md section 4.2 has the audit).  tgnet_bdl (train_configs/tgnet_bdl.py with its four paths edited)
 trains tgnet's boundary module from a tgnet_fps checkpoint: see training.BoundarySampler for the three directories it needs.
 Prints the trainer's JSON lines: one per scheduler step, one per epoch.  Checkpoints: ckpts/<experiment_name>.h5 after every epoch,
 ckpts/<experiment_name>_val.h5 at every best validation total; both load into inference.make_inference_pipeline."""
@@ -62,6 +66,8 @@ def main(argv=None):
                     help="set tr_set.contrastive_boundary_fused: tgnet_fps / tgnet_bdl compute the criterion with the fused stage kernels")
     ap.add_argument("--ordered_backward", action="store_true",
                     help="set tr_set.ordered_backward: the gather family's backward without float atomics (config.cfg.ordered_backward)")
+    ap.add_argument("--reproducible", action="store_true",
+                    help="set tr_set.reproducible: ordered backward, ordered BatchNorm sums, torch's deterministic algorithms, a digest per epoch")
     args = ap.parse_args(argv)
 
     import numpy as np
@@ -78,6 +84,8 @@ def main(argv=None):
         config["tr_set"]["contrastive_boundary_fused"] = True
     if args.ordered_backward:
         config.setdefault("tr_set", {})["ordered_backward"] = True
+    if args.reproducible:
+        config.setdefault("tr_set", {})["reproducible"] = True
     model = training.make_training_model(args.model_name, config)
     gen_set = [training.get_generator_set(config["generator"])]
     print("train_set", len(gen_set[0][0]), file=sys.stderr)

@@ -2,7 +2,8 @@
 """What the training entry point's bookkeeping costs: one training step of `training`'s tgnet_fps and pointnetpp models on ONE
 24 000-point scan, batch 1, fp32, against a bare loop in the same process.  `tgnet_fps_cbl` is tgnet_fps with the contrastive-boundary
 criterion on (tr_set.contrastive_boundary, both cbl weights 1): what the criterion adds to a step is its difference to `tgnet_fps`;
-`tgnet_fps_cbl_fused` is the same with tr_set.contrastive_boundary_fused (the criterion's stages as the kernels of csrc/cbl.hip).
+`tgnet_fps_cbl_fused` is the same with tr_set.contrastive_boundary_fused (the criterion's stages as the kernels of csrc/cbl.hip);
+`tgnet_fps_reproducible` is tgnet_fps with tr_set.reproducible, to be run in a process of its own.
 
   trainer   model.step(batch_idx, batch_item, "train") and the three get_loss_dict_for_print calls Trainer.train makes per batch: the
             host-to-device copy of the item, forward, losses, backward, optimiser, LossMap, ONE device read.
@@ -38,7 +39,11 @@ CONFIGS["tgnet_fps_cbl"]["tr_set"]["loss"].update(cbl_loss_1=1, cbl_loss_2=1)
 CONFIGS["tgnet_fps_cbl"]["tr_set"]["contrastive_boundary"] = True
 CONFIGS["tgnet_fps_cbl_fused"] = copy.deepcopy(CONFIGS["tgnet_fps_cbl"])
 CONFIGS["tgnet_fps_cbl_fused"]["tr_set"]["contrastive_boundary_fused"] = True
-MODEL_NAME = {"tgnet_fps_cbl": "tgnet_fps", "tgnet_fps_cbl_fused": "tgnet_fps"}
+# tgnet_fps with tr_set.reproducible (ordered backward, ordered BatchNorm sums, torch's deterministic algorithms).  The flags are the
+# process's and are never switched off again: measure it in a process of its own, `--models tgnet_fps_reproducible`
+CONFIGS["tgnet_fps_reproducible"] = copy.deepcopy(CONFIGS["tgnet_fps"])
+CONFIGS["tgnet_fps_reproducible"]["tr_set"]["reproducible"] = True
+MODEL_NAME = {"tgnet_fps_cbl": "tgnet_fps", "tgnet_fps_cbl_fused": "tgnet_fps", "tgnet_fps_reproducible": "tgnet_fps"}
 
 
 def quartiles(ms):

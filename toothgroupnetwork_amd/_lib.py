@@ -103,6 +103,9 @@ SIGNATURES = {
     "tgn_bn_rows_workspace_bytes": (c_size_t, [c_int]),
     "tgn_bn_rows_forward": (c_int, [ctypes.c_longlong, c_int, _P, _P, _P, c_float, c_float, _P, _P, _P, c_int, _P, _P, _P, _P, _P]),
     "tgn_bn_rows_backward": (c_int, [ctypes.c_longlong, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P]),
+    "tgn_bn_rows_ordered_workspace_bytes": (c_size_t, [ctypes.c_longlong, c_int]),
+    "tgn_bn_rows_forward_ordered": (c_int, [ctypes.c_longlong, c_int, _P, _P, _P, c_float, c_float, _P, _P, _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "tgn_bn_rows_backward_ordered": (c_int, [ctypes.c_longlong, c_int, _P, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "tgn_sa_mlp2_max": (c_int, [c_int] * 7 + [_P] * 7 + [c_int, _P, _P, _P, c_int, _P]),
     "tgn_sa_mlp2_split_bytes": (ctypes.c_size_t, [c_int, c_int]),
     "tgn_sa_mlp2_split_weights": (c_int, [c_int, c_int, _P, _P, _P]),

@@ -28,6 +28,10 @@ ordered_backward      TGN_ORDERED_BACKWARD   the gather family's backward (group
                       =0/1, default 0        Point-Transformer tail, index_points / group_points / three_interpolate) along reverse
                                              lists instead of float atomics: the same bits every time.  Read at call time, in
                                              ordered.py only, which states every such gradient in both forms.  Off: the atomic kernels
+ordered_bn            TGN_ORDERED_BN         the column sums of the fused BatchNorm over rows (point_transformer.bn_rows: batch statistics,
+                      =0/1, default 0        dgamma, dbeta) in the fixed order of tgn_bn_rows_*_ordered instead of with float64 atomics: the
+                                             same bits every time.  A switch of its own: ordered_backward alone leaves every BatchNorm
+                                             launch as it was.  Read in ordered.py only, when the forward is called; its backward follows
 """
 import dataclasses
 import os
@@ -51,6 +55,7 @@ class Config:
     index_check: str = "sync"
     fps_prefix: Optional[bool] = None
     ordered_backward: bool = False
+    ordered_bn: bool = False
 
     @classmethod
     def from_env(cls):
@@ -60,7 +65,7 @@ class Config:
                    knn_cache_size=int(os.environ.get("TGN_KNN_CACHE", "16")),
                    index_check=os.environ.get("TGN_INDEX_CHECK", "sync").lower(),
                    fps_prefix=None if fps_prefix == "" else fps_prefix != "0",
-                   ordered_backward=_flag("TGN_ORDERED_BACKWARD", "0"))
+                   ordered_backward=_flag("TGN_ORDERED_BACKWARD", "0"), ordered_bn=_flag("TGN_ORDERED_BN", "0"))
 
 
 cfg = Config.from_env()

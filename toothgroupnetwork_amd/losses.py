@@ -178,11 +178,20 @@ def centroid_loss(pred_offset, sample_xyz, distance, centroid, exists=None):
     return _CentroidLoss.apply(_lib.f32c(pred_offset), _lib.f32c(sample_xyz.detach()), _lib.f32c(distance.reshape(B, M)), _lib.f32c(centroid.detach()), mask)
 
 
+def _class_cross_entropy(logits, target):
+    """Cross entropy of (B, C, N) logits against (B, N) classes.  torch's CUDA kernel for this layout (nll_loss2d) adds its terms with
+    float atomics and has no deterministic form: under torch.use_deterministic_algorithms (training.set_reproducible) it raises.  There
+    the same mean is taken over the (B N, C) rows, whose kernel reduces in a fixed order: the same value up to the order of its sum."""
+    if torch.are_deterministic_algorithms_enabled():
+        return F.cross_entropy(logits.permute(0, 2, 1).reshape(-1, logits.shape[1]), target.reshape(-1))
+    return F.cross_entropy(logits, target)
+
+
 def tooth_class_loss(cls_pred, gt_cls):
     """tgn_loss.py:355-367 without weights / smoothing: cross entropy of (B, 17, N) logits against labels shifted by one
     (gingiva -1 -> class 0)"""
     b = gt_cls.shape[0]
-    return F.cross_entropy(cls_pred.float(), gt_cls.view(b, -1).long() + 1)
+    return _class_cross_entropy(cls_pred.float(), gt_cls.view(b, -1).long() + 1)
 
 
 def grouping_loss_terms(output, gt_seg_label, input_coords):
@@ -199,8 +208,8 @@ def grouping_loss_terms(output, gt_seg_label, input_coords):
     crop_labels = output["cluster_gt_seg_label"].reshape(output["sem_2"].shape[0], -1).long()
     crop_labels = torch.where(crop_labels >= 0, torch.zeros_like(crop_labels), crop_labels)
     offset_loss, dir_loss, chamf_loss = tgn_offset_losses(output["offset_1"], input_coords, labels)
-    return {"tooth_class_loss_1": F.cross_entropy(output["sem_1"].float(), half + 1),
-            "tooth_class_loss_2": F.cross_entropy(output["sem_2"].float(), crop_labels + 1),
+    return {"tooth_class_loss_1": _class_cross_entropy(output["sem_1"].float(), half + 1),
+            "tooth_class_loss_2": _class_cross_entropy(output["sem_2"].float(), crop_labels + 1),
             "offset_1_loss": offset_loss, "offset_1_dir_loss": dir_loss, "chamf_1_loss": chamf_loss}
 
 

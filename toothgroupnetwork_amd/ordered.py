@@ -16,6 +16,12 @@ weakly: the entry goes with the tensor), its version counter (an in-place write 
 cannot see (``.data``, raw pointers) do not bump the version: call ``lists_cache_clear()`` after them.  While a stream is being
 captured the memo is neither read nor written: a graph must own every buffer it replays from, and rebuilds the lists when it is
 replayed on new indices.
+
+The other reduction of a training step with an arrival order is stated here too, in both forms: the per-column sums of the fused
+BatchNorm over rows (``bn_rows_forward`` / ``bn_rows_backward``, csrc/bnorm.hip; ``point_transformer._BNRows`` calls them), with
+float64 atomics or, with ``config.cfg.ordered_bn`` (TGN_ORDERED_BN=1; off by default, a switch of its own), thread by thread and block
+by block in the order include/tgn_pointops.h states.  ``tr_set["reproducible"]`` (training.py, ``tools/train.py --reproducible``)
+sets both switches.
 """
 import torch
 from torch.utils.weak import WeakTensorKeyDictionary
@@ -184,3 +190,63 @@ def softmax_aggregate_backward(x_v, p_r, sm, idx, grad_out):
     if on:
         g_xv = scatter(g_pr.view(n * nsample, c), x_v.shape[0], reverse_lists(idx, x_v.shape[0]))
     return g_xv, g_pr, g_lg
+
+
+# ---- BatchNorm over rows, both forms (csrc/bnorm.hip) ---------------------------------------------------------------------------------
+def _bn_workspace(bn, rows, C, device, on):
+    """A module's workspace for the current (device, stream), parked on the module (DataParallel replicas share its __dict__ entries,
+    two streams must never meet in one buffer).  Atomic form: accumulators + ticket, zero-filled once and left zeroed by the kernels.
+    Ordered form: the blocks' partial sums, any contents, grown to the largest `rows` seen; while a stream is being captured a
+    buffer of the capture's own, as for the lists above."""
+    zeroed = bn.__dict__.setdefault("_tgn_bn_ws", {})
+    key = (device.index, torch.cuda.current_stream().cuda_stream)
+    if not on:
+        ws = zeroed.get(key)
+        if ws is None:
+            ws = zeroed[key] = torch.zeros(int(ops().tgn_bn_rows_workspace_bytes(C)), dtype=torch.uint8, device=device)
+        return ws
+    nbytes = int(ops().tgn_bn_rows_ordered_workspace_bytes(rows, C))
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    partials = bn.__dict__.setdefault("_tgn_bn_ws_ordered", {})
+    ws = partials.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = partials[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
+def bn_rows_forward(bn, x, weight, bias, relu):
+    """Training-mode BatchNorm1d [+ ReLU] of module `bn` over the rows of x (rows, C) float32 contiguous -> (y, save_mean, save_invstd,
+    ws); the running statistics and num_batches_tracked are updated by the kernel.  The statistics are summed with float64 atomics, or,
+    with config.cfg.ordered_bn, in the fixed order include/tgn_pointops.h states.  ws is what bn_rows_backward takes: the zeroed
+    workspace of the atomic form, None for the ordered one -- the backward follows the form its forward took."""
+    rows, C = x.shape
+    on = config.cfg.ordered_bn
+    y = torch.empty_like(x)
+    stat = torch.empty(2, C, dtype=torch.float32, device=x.device)             # batch mean, 1 / sqrt(var + eps)
+    mean, invstd = stat[0], stat[1]
+    ws = _bn_workspace(bn, rows, C, x.device, on)
+    track = bn.track_running_stats and bn.running_mean is not None
+    head = (rows, C, x, weight, bias, float(bn.eps), float(bn.momentum), bn.running_mean if track else None,
+            bn.running_var if track else None, bn.num_batches_tracked if track else None, int(relu), y, mean, invstd, ws)
+    if on:
+        ops().tgn_bn_rows_forward_ordered(*head, ws.numel(), stream())
+    else:
+        ops().tgn_bn_rows_forward(*head, stream())
+    return y, mean, invstd, None if on else ws
+
+
+def bn_rows_backward(bn, ws, x, y, dy, weight, mean, invstd, relu):
+    """-> (dx, dgamma, dbeta) of bn_rows_forward from dy (rows, C) float32 contiguous; y is read under ReLU only (the mask is y > 0).
+    ws None: dbeta and dgamma summed in the fixed order, else with float64 atomics into that workspace."""
+    rows, C = x.shape
+    dx = torch.empty_like(x)
+    dwb = torch.empty(2, C, dtype=torch.float32, device=x.device)
+    dgamma, dbeta = dwb[0], dwb[1]
+    head = (rows, C, x, y, dy, weight, mean, invstd, int(relu), dx, dgamma, dbeta)
+    if ws is None:
+        ws = _bn_workspace(bn, rows, C, x.device, True)
+        ops().tgn_bn_rows_backward_ordered(*head, ws, ws.numel(), stream())
+    else:
+        ops().tgn_bn_rows_backward(*head, ws, stream())
+    return dx, dgamma, dbeta

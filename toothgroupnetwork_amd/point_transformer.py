@@ -139,38 +139,21 @@ class _BNRows(Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, bn, relu):
-        rows, C = x.shape
-        y = torch.empty_like(x)
-        stat = torch.empty(2, C, dtype=torch.float32, device=x.device)             # batch mean, 1 / sqrt(var + eps)
-        mean, invstd = stat[0], stat[1]
-        # accumulators + ticket, left zeroed by the kernels: one per (module, device, stream), so that two streams (or DataParallel
-        # replicas, which share the module's __dict__ entries) never meet in one workspace
-        wss = bn.__dict__.setdefault("_tgn_bn_ws", {})
-        wkey = (x.device.index, torch.cuda.current_stream().cuda_stream)
-        ws = wss.get(wkey)
-        if ws is None:
-            ws = wss[wkey] = torch.zeros(int(ops().tgn_bn_rows_workspace_bytes(C)), dtype=torch.uint8, device=x.device)
-        track = bn.track_running_stats and bn.running_mean is not None
-        ops().tgn_bn_rows_forward(rows, C, x, weight, bias, float(bn.eps), float(bn.momentum),
-                                  bn.running_mean if track else None, bn.running_var if track else None,
-                                  bn.num_batches_tracked if track else None, int(relu), y, mean, invstd, ws, stream())
-        if track:   # written through raw pointers: tell torch (the fold memo of the eval paths keys on these counters)
+        # the two launches, their workspace and the choice between atomic and ordered column sums: ordered.bn_rows_forward
+        y, mean, invstd, ws = ordered.bn_rows_forward(bn, x, weight, bias, relu)
+        if bn.track_running_stats and bn.running_mean is not None:
+            # written through raw pointers: tell torch (the fold memo of the eval paths keys on these counters)
             for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked):
                 if t is not None:
                     torch.autograd.graph.increment_version(t)
         ctx.save_for_backward(x, y if relu else None, weight, mean, invstd)
-        ctx.relu, ctx.ws = bool(relu), ws
+        ctx.relu, ctx.bn, ctx.ws = bool(relu), bn, ws
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, y, weight, mean, invstd = ctx.saved_tensors
-        rows, C = x.shape
-        dy = dy.contiguous()
-        dx = torch.empty_like(x)
-        dwb = torch.empty(2, C, dtype=torch.float32, device=x.device)
-        dgamma, dbeta = dwb[0], dwb[1]
-        ops().tgn_bn_rows_backward(rows, C, x, y, dy, weight, mean, invstd, int(ctx.relu), dx, dgamma, dbeta, ctx.ws, stream())
+        dx, dgamma, dbeta = ordered.bn_rows_backward(ctx.bn, ctx.ws, x, y, dy.contiguous(), weight, mean, invstd, ctx.relu)
         return dx, dgamma, dbeta, None, None
 
 

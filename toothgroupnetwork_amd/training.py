@@ -31,6 +31,7 @@ Where it differs from the reference on purpose:
 """
 import copy
 import glob
+import hashlib
 import json
 import math
 import os
@@ -264,6 +265,37 @@ def build_scheduler(tr_set, optimizer):
     return CosineSchedule(optimizer, sched["full_steps"], sched["min_lr"])
 
 
+# ---- the same bits from the same seed -------------------------------------------------------------------------------------------------------
+
+# model name -> the operator that stands between it and a bit-reproducible step, found by tools/reproducible_audit.py (DESIGN.md
+# section 4.2 has the method and the per-model outcome).  make_training_model refuses these names when tr_set["reproducible"] is set.
+NOT_REPRODUCIBLE = {}
+
+
+def set_reproducible(seed=None, warn_only=False):
+    """Switch the process to the forms that give the same bits on every run (same machine, same build, same seed, same data order):
+    the gather family's backward along reverse lists (config.cfg.ordered_backward) and the fused BatchNorm's column sums in a fixed
+    order (config.cfg.ordered_bn), both in ordered.py; torch.use_deterministic_algorithms, under which a torch operator that torch
+    knows to be non-deterministic raises and names itself (warn_only: warns); torch.backends.cudnn.deterministic on and .benchmark
+    off, which torch-ROCm hands to MIOpen's choice of solver.  seed: torch's generators on every device (numpy's is the caller's).
+    Only ever switches ON; tr_set["reproducible"] and tools/train.py --reproducible end here."""
+    switches.cfg.ordered_backward = True
+    switches.cfg.ordered_bn = True
+    torch.use_deterministic_algorithms(True, warn_only=warn_only)
+    torch.backends.cudnn.deterministic = True
+    torch.backends.cudnn.benchmark = False
+    if seed is not None:
+        torch.manual_seed(seed)
+
+
+def state_digest(model):
+    """sha256 over the tensors of model.module.state_dict(), in key order, each as its bytes: what two runs compare instead of
+    loading each other's checkpoints.  One device-to-host copy (the tensors are packed into one byte buffer on the device first)."""
+    tensors = [v.detach().contiguous().view(-1).view(torch.uint8) for _, v in sorted(model.module.state_dict().items()) if v.numel()]
+    packed = torch.cat(tensors) if tensors else torch.empty(0, dtype=torch.uint8)
+    return hashlib.sha256(packed.cpu().numpy().tobytes()).hexdigest()
+
+
 # ---- model steps ------------------------------------------------------------------------------------------------------------------------
 
 class TrainingModel:
@@ -277,7 +309,8 @@ class TrainingModel:
     trainable=False is a model that is only evaluated (validation over a checkpoint): the module starts in eval mode, there is no
     optimiser and no scheduler, the configuration needs no section for either, and step(..., "train") raises.
 
-    tr_set["ordered_backward"] true sets config.cfg.ordered_backward for the process (ordered.py; tools/train.py --ordered_backward)."""
+    tr_set["ordered_backward"] true sets config.cfg.ordered_backward for the process (ordered.py; tools/train.py --ordered_backward).
+    tr_set["reproducible"] true is set_reproducible() for the process: same seed, same data order, same bits."""
 
     module_class = None
 
@@ -288,6 +321,8 @@ class TrainingModel:
             # the package's switch (config.cfg.ordered_backward): every gather-family backward from here on sums along reverse
             # lists, without float atomics.  Only ever switched ON from a configuration: absent or false leaves the switch as it is
             switches.cfg.ordered_backward = True
+        if config.get("tr_set", {}).get("reproducible"):
+            set_reproducible()
         if not torch.cuda.is_available():
             raise RuntimeError("training needs a GPU: the modules' operators are HIP kernels and have no CPU fallback")
         self.device = torch.device("cuda")
@@ -664,6 +699,9 @@ def make_training_model(model_name, config, trainable=True):
     trainable=False: TrainingModel's evaluate-only form."""
     if model_name not in _MODELS:
         raise ValueError(f"undefined model {model_name!r}: the names are {', '.join(MODEL_NAMES)}")
+    if config.get("tr_set", {}).get("reproducible") and model_name in NOT_REPRODUCIBLE:
+        raise NotImplementedError(f"{model_name}: tr_set.reproducible is set and this model's step is not bit-reproducible: "
+                                  f"{NOT_REPRODUCIBLE[model_name]}.  Nothing here trains under that flag without keeping its promise")
     return _MODELS[model_name](config, trainable=trainable)
 
 
@@ -676,7 +714,8 @@ class Trainer:
     last batch of an epoch in which it has not stepped yet, each time with the running step count; save("train") after every training
     epoch; save("val") whenever total_val improves.  Instead of wandb, `stream` (default stdout) gets one JSON line per scheduler
     step -- the step meter's averages (`*_step`), `step_lr`, `step` -- and run() one per epoch: the epoch's `*_train` and `*_val`
-    averages, `epoch`, `step` and, for a model that counts them, `skipped_segmentation`."""
+    averages, `epoch`, `step`, for a model that counts them `skipped_segmentation`, and with tr_set["reproducible"] `digest`
+    (state_digest of the model after the epoch)."""
 
     def __init__(self, config=None, model=None, gen_set=None, stream=None):
         self.config, self.model, self.gen_set = config, model, gen_set
@@ -731,4 +770,6 @@ class Trainer:
             record["step"] = self.step_count
             if hasattr(self.model, "skipped_segmentation"):
                 record["skipped_segmentation"] = self.model.skipped_segmentation
+            if self.config.get("tr_set", {}).get("reproducible"):
+                record["digest"] = state_digest(self.model)
             self._emit(record)
